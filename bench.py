@@ -14,8 +14,14 @@ per GPU (torchrun sets RANK/LOCAL_RANK/WORLD_SIZE), the image is cut into bands 
 and grows with N at fixed 16:9 aspect (weak scaling; N = 4 is configs[3]'s 3840x2160); the bands
 are timed and their boundaries moved before the measurement (--balance-rounds).
 Consecutive frames go to --frames-in-flight renderers with their own contexts and streams (every
-frame is complete: all grids rebuilt); the time of a frame that has the GPU to itself is reported
-beside the rate as ms_per_step_one_frame_in_flight.  Prints ONE JSON line on rank 0.
+frame is complete: all grids rebuilt).  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, ...).
+--full adds everything else behind the timed steps: the spread of the figure, the time of a frame that
+has the GPU to itself (ms_per_step_one_frame_in_flight), stage tables, the roofline of the dominant
+tracer, the check against one sequential context (verify), the CPU baseline, the C++ driver and the
+other BASELINE configurations.
+--dump-outputs DIR writes the buffers of the last timed frame as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import gc
@@ -109,6 +115,42 @@ def cpp_driver_leg(ugrt, torch, s, W, H, image, frames=40, time_from=10):
     got = np.array(tok[4:], dtype=np.int64).astype(np.uint8)
     res["ppm_equals_the_timed_renderers_image"] = bool(np.array_equal(got, image.cpu().numpy()))
     return res
+
+
+DUMP_SAMPLE_PIXELS = 1 << 18  # --dump-outputs: the per-pixel buffers at a fixed sample of this many pixels
+DUMP_IMAGE_LIMIT = 32 << 20  # --dump-outputs: the image whole while its float32 form fits (1920x1080: 24.9 MB)
+
+
+def dump_outputs(d, rr, reflect, world):
+    """--dump-outputs: the buffers renderer `rr` holds from the last timed frame, as a caller of display() receives
+    them, written as d/<name>.npy.  image: the RGB image [H, W, 3], whole while its float32 form is at most
+    DUMP_IMAGE_LIMIT bytes, else at the sampled pixels.  N = 1 also: t, intersect_id, is_shadowed, normal, dir and,
+    with the bounce, hit_t, hit_id, active, at DUMP_SAMPLE_PIXELS pixels drawn with seed 0 (their ids: pixels).
+    32-bit integers are written as float64, everything else as float32 (all exact): at most 32 MiB + 72 B per
+    sampled pixel (52 MB; 1920x1080: 44 MB)."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    W, H = rr.ctx.width, rr.ctx.height
+    n = W * H
+    pix = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE_PIXELS), replace=False))
+
+    def host(x, per_pixel, sample=True):
+        a = x.cpu().numpy().reshape(n, per_pixel)
+        a = a[pix] if sample else a
+        return a.astype(np.float64 if a.dtype.itemsize > 2 and a.dtype.kind != "f" else np.float32)
+
+    image = host(rr.image, 3, sample=12 * n > DUMP_IMAGE_LIMIT)
+    out = {"image": image.reshape(H, W, 3) if len(image) == n else image, "pixels": pix.astype(np.float64)}
+    if world == 1:
+        for k, c in (("t", 1), ("intersect_id", 1), ("is_shadowed", 1), ("normal", 3), ("dir", 3)):
+            out[k] = host(getattr(rr, k), c)
+        if reflect:
+            for k in ("hit_t", "hit_id", "active"):
+                out[k] = host(getattr(rr, k), 1)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), a.squeeze(-1) if a.ndim == 2 and a.shape[1] == 1 else a)
+    log("[bench] --dump-outputs: %s in %s (%.1f MB)" % (", ".join(sorted(out)), d, sum(a.nbytes for a in out.values()) / 1e6))
 
 
 def load_scene(ugrt, workload, scale, rank, keep_files=False):
@@ -333,13 +375,19 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="triangle-count scale of the scene (1.0 = BASELINE)")
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline sample budget (0 = skip)")
-    ap.add_argument("--stages-json", default="", help="also write the per-stage table to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: spread, one-frame latency, stage tables, roofline, verify, CPU baseline, "
+                         "C++ driver, other BASELINE configurations (default: the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the buffers of the last timed frame to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: CPU baseline sample budget (0 = skip)")
+    ap.add_argument("--stages-json", default="", help="--full: also write the per-stage table to this file")
     ap.add_argument("--no-reflect", action="store_true", help="primary + shadow only (BASELINE configs[1])")
     ap.add_argument("--no-overlap", action="store_true",
                     help="one stream: every stage after the other (default: light/uniform grid builds and the bounce "
                          "on a second stream beside the camera and shadow passes)")
-    ap.add_argument("--repeats", type=int, default=4, help="extra untimed repetitions of the K steps (spread of the figure)")
+    ap.add_argument("--repeats", type=int, default=4,
+                    help="--full: extra untimed repetitions of the K steps (spread of the figure)")
     ap.add_argument("--stream-order", default="A",
                     help="order in which the renderers' streams are created (the runtime deals hardware queues in that order): "
                          "A main0 side0 main1 side1 ...; B the main streams, then the side streams starting at frame 1; "
@@ -360,9 +408,10 @@ def main():
     ap.add_argument("--no-static-geometry", action="store_true",
                     help="rebuild the per-triangle records in every grid build, as a caller that rewrites the vertex array "
                          "behind the library's back must (default: UGRT_FLAG_STATIC_GEOMETRY, the renderer is the only writer)")
-    ap.add_argument("--verify", dest="verify", action="store_true", default=True, help="(the default; kept for older command lines)")
+    ap.add_argument("--verify", dest="verify", action="store_true", default=None,
+                    help="check behind the timed region (the default with --full; this option runs it without --full too)")
     ap.add_argument("--no-verify", dest="verify", action="store_false",
-                    help="skip the check behind the timed region (default: on).  N = 1: the buffers every renderer in flight "
+                    help="skip the check behind the timed region (default: on with --full).  N = 1: the buffers every renderer in flight "
                          "holds from its last frame (image, shadow flags, ids, t, normals, directions, bounce hits) are "
                          "compared bit for bit with ONE sequential context whose builds wait (one stream, one frame, no "
                          "estimates); N > 1: rank 0 renders the whole frame that way and compares the gathered image")
@@ -373,7 +422,7 @@ def main():
     ap.add_argument("--balance-rounds", type=int, default=4,
                     help="N > 1: rounds of timing the bands and moving their boundaries before the measurement (0 = equal bands)")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false", default=True,
-                    help="N = 1, default workload: skip the other BASELINE configurations behind the headline measurement "
+                    help="--full, N = 1, default workload: skip the other BASELINE configurations behind the headline measurement "
                          "(hall 1024x1024 primary + shadow = configs[1], the 3840x2160 frame on this one GPU = configs[3]'s "
                          "per-GPU ceiling, the animated rebuild = configs[4]; ~10 verified steps each, reported under "
                          "other_configs; the profile passes skip them so that their kernel averages are the headline's)")
@@ -382,13 +431,17 @@ def main():
                          "(ugrt_grid_build_batch_begin / _end: three radix launches less per frame; measured 2 %% slower with "
                          "four frames in flight, profiles/r04_batched_builds.txt; default: one after the other)")
     ap.add_argument("--bands-in-frame", type=int, nargs="*", default=[],
-                    help="N = 1: also time ONE frame at a time cut into this many bands of tile rows on streams of their own "
+                    help="--full, N = 1: also time ONE frame at a time cut into this many bands of tile rows on streams of their own "
                          "(BandedRenderer; reported under one_frame_in_bands).  Default: none -- measured: 2 bands 1.45 against "
                          "1.46 ms, 3 and 4 bands 2.0 ms (the one host thread then enqueues 160-200 launches a frame at ~6 us "
                          "each: profiles/r04_banded_frame.txt)")
     ap.add_argument("--animate", action="store_true",
                     help="BASELINE configs[4]: transform the animated sub-range every frame (rot = 1.81 + 0.05*frame)")
     args = ap.parse_args()
+    if not args.full and (args.stages_json or args.bands_in_frame):
+        ap.error("--stages-json and --bands-in-frame are measurements of --full")
+    if args.verify is None:
+        args.verify = args.full
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))  # before anything that could initialise the GPU in this process
 
@@ -439,7 +492,7 @@ def main():
     if args.uniform_grid:
         udims = tuple(args.uniform_grid)
 
-    s = load_scene(ugrt, args.workload, args.scale, rank, keep_files=(world == 1 and args.other_configs))
+    s = load_scene(ugrt, args.workload, args.scale, rank, keep_files=(world == 1 and args.full and args.other_configs))
     setup = ugrt.FrameSetup.from_scene(s)
     # the renderer is the only writer of the vertex array (ugrt_animate): triangle records survive between builds
     flags = ugrt.FLAG_SHADOW_ALL_CHUNKS | (0 if args.no_static_geometry else ugrt.FLAG_STATIC_GEOMETRY)
@@ -572,19 +625,25 @@ def main():
             rr.display(setup, frame_cnt=1, shadows=True, reflect=reflect)
             gather.gather(rr.image)
 
-    # the tracers' event pairs are bracketed from the first warm-up step on; after the W warm-up steps every context
-    # is run until its pool holds the pairs K timed steps take (hipEventCreate inside the timed region cost ~4 %)
     tracers = ("trace_primary", "shadow_cull", "trace_shadow", "trace_dda")
     profiled = [c for rr in renderers for c in [rr.ctx] + ([rr.aux] if rr.aux is not None else [])]
-    for c in profiled:
-        c.prof_enable(True, stages=tracers)
-    warm = max(1, args.warmup)
-    for _ in range(warm):
-        step()
-    if not os.environ.get("UGRT_BENCH_COLD_EVENTS"):
-        for _ in range(max(0, args.steps - warm)):
+    if args.full:
+        # the tracers' event pairs are bracketed from the first warm-up step on; after the W warm-up steps every context
+        # is run until its pool holds the pairs K timed steps take (hipEventCreate inside the timed region cost ~4 %)
+        for c in profiled:
+            c.prof_enable(True, stages=tracers)
+        warm = max(1, args.warmup)
+        for _ in range(warm):
             step()
-            warm += 1
+        if not os.environ.get("UGRT_BENCH_COLD_EVENTS"):
+            for _ in range(max(0, args.steps - warm)):
+                step()
+                warm += 1
+    else:
+        # the W warm-up steps, and at least two frames on every renderer in flight (its first frames size its buffers)
+        warm = max(args.warmup, 2 * len(renderers))
+        for _ in range(warm):
+            step()
     gather.finish()
     for rr in renderers:
         rr.synchronize()
@@ -595,29 +654,6 @@ def main():
     active = int(r.active[ctx.p0:ctx.p0 + ctx.npix].sum().item()) if reflect else 0
     rays_rank = 2 * ctx.npix + active
 
-    # work counters for the DDA's algorithmic bytes: a counting context, outside the timed region
-    cctx = ugrt.Context(W, H, device=local, light_grid=lg, rows=rows, flags=flags | ugrt.FLAG_COUNT_WORK,
-                        uniform_dims=udims)
-    cr = ugrt.Renderer(cctx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
-    cr.d_verts.copy_(r.d_verts)  # same geometry as the timed renderer (matters with --animate)
-    cctx.geometry_changed()
-    cr.display(setup, frame_cnt=1, shadows=True, reflect=reflect)
-    cctx.synchronize()
-    st = cctx.stats()
-    dda_counts = (st[3], st[4], st[5]) if reflect else (0, 0, 0)
-    if reflect and not args.animate:
-        assert st[5] == active, (st[5], active)
-    del cr, cctx
-    gc.collect()  # the counting context's buffers are freed HERE (hipFree synchronises the device), not by a collection inside the timed region
-    torch.cuda.synchronize()
-    abytes = algorithmic_bytes(torch, ugrt, ctx, r, dda_counts)
-
-    # ---- timed region: exactly K steps between barrier + synchronize pairs -------------------
-    # hipEvent pairs bracket the four tracer kernels inside the timed loop (the roofline figure needs the
-    # dominant kernel's live launch time); every other stage is timed in a separate, untimed pass below,
-    # because ~40 event pairs per frame would themselves cost about 7 % of the frame.
-    # events are recorded on the stream a kernel runs on
-
     def merged_prof():
         out = {}
         for c in profiled:
@@ -626,19 +662,45 @@ def main():
                 out[k] = (a[0] + v[0], a[1] + v[1])
         return out
 
-    # (the counting pass above ran other work and left the chip idle while the host summed up: a few more untimed
-    # frames bring the pipeline of frames in flight back to its steady state before the clock starts)
+    if args.full:
+        # work counters for the DDA's algorithmic bytes: a counting context, outside the timed region
+        cctx = ugrt.Context(W, H, device=local, light_grid=lg, rows=rows, flags=flags | ugrt.FLAG_COUNT_WORK,
+                            uniform_dims=udims)
+        cr = ugrt.Renderer(cctx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
+        cr.d_verts.copy_(r.d_verts)  # same geometry as the timed renderer (matters with --animate)
+        cctx.geometry_changed()
+        cr.display(setup, frame_cnt=1, shadows=True, reflect=reflect)
+        cctx.synchronize()
+        st = cctx.stats()
+        dda_counts = (st[3], st[4], st[5]) if reflect else (0, 0, 0)
+        if reflect and not args.animate:
+            assert st[5] == active, (st[5], active)
+        del cr, cctx
+        gc.collect()  # the counting context's buffers are freed HERE (hipFree synchronises the device), not by a collection inside the timed region
+        torch.cuda.synchronize()
+        abytes = algorithmic_bytes(torch, ugrt, ctx, r, dda_counts)
+
+    # after the synchronisation above (and --full's counting pass, which left the chip idle while the host summed up) a
+    # few more untimed frames bring the pipeline of frames in flight to its steady state before the clock starts
+    # (a plain run without them: 1.00 against 0.97 ms per step)
     for _ in range(2 * len(renderers)):
         step()
         warm += 1
     gather.finish()
-    for c in profiled:
-        c.prof_enable(True, stages=tracers)
-        c.prof_reset()
+    if args.full:
+        for c in profiled:
+            c.prof_enable(True, stages=tracers)
+            c.prof_reset()
+
+    # ---- timed region: exactly K steps between barrier + synchronize pairs -------------------
+    # --full: hipEvent pairs bracket the four tracer kernels inside the timed loop (the roofline figure needs the
+    # dominant kernel's live launch time); every other stage is timed in a separate, untimed pass below,
+    # because ~40 event pairs per frame would themselves cost about 7 % of the frame.
+    # events are recorded on the stream a kernel runs on
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
-    radix0 = sum(c.get_state("radix_launches") for c in profiled)
+    radix0 = sum(c.get_state("radix_launches") for c in profiled) if args.full else 0
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step()
@@ -649,58 +711,52 @@ def main():
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    radix_per_frame = (sum(c.get_state("radix_launches") for c in profiled) - radix0) / float(args.steps)
-    prof = merged_prof()
-    # spread of the figure: the same K steps a few more times, outside the reported region
-    repeats = []
-    for _ in range(args.repeats):
-        torch.cuda.synchronize()
-        r0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        gather.finish()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, renderers[(turn[0] - 1) % len(renderers)], reflect, world)
+
+    split_stats, latency_ms = None, None
+    if args.full:
+        radix_per_frame = (sum(c.get_state("radix_launches") for c in profiled) - radix0) / float(args.steps)
+        prof = merged_prof()
+        # spread of the figure: the same K steps a few more times, outside the reported region
+        repeats = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            r0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            gather.finish()
+            for rr in renderers:
+                rr.synchronize()
+            torch.cuda.synchronize()
+            repeats.append((time.perf_counter() - r0) / args.steps * 1e3)
+        # The frame leaves processData's sort to whoever asks for its outputs (ugrt_sort_rays, deferred form with
+        # SHADOW_ALL_CHUNKS).  Beside the figure: the same K steps with that sort carried out in every frame ("ray_sort" 1).
+        ray_sort_kept = []
+        for _ in range(min(args.repeats, 2)):
+            for rr in renderers:
+                rr.ctx.set_option("ray_sort", 1)
+            torch.cuda.synchronize()
+            r0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            gather.finish()
+            for rr in renderers:
+                rr.synchronize()
+            torch.cuda.synchronize()
+            ray_sort_kept.append((time.perf_counter() - r0) / args.steps * 1e3)
         for rr in renderers:
-            rr.synchronize()
-        torch.cuda.synchronize()
-        repeats.append((time.perf_counter() - r0) / args.steps * 1e3)
-    # The frame leaves processData's sort to whoever asks for its outputs (ugrt_sort_rays, deferred form with
-    # SHADOW_ALL_CHUNKS).  Beside the figure: the same K steps with that sort carried out in every frame ("ray_sort" 1).
-    ray_sort_kept = []
-    for _ in range(min(args.repeats, 2)):
-        for rr in renderers:
-            rr.ctx.set_option("ray_sort", 1)
-        torch.cuda.synchronize()
-        r0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        gather.finish()
-        for rr in renderers:
-            rr.synchronize()
-        torch.cuda.synchronize()
-        ray_sort_kept.append((time.perf_counter() - r0) / args.steps * 1e3)
-    for rr in renderers:
-        rr.ctx.set_option("ray_sort", -1)
-    split_stats = None
-    # latency: the same K steps with ONE frame in flight (every frame is finished before the next one is started)
-    latency_ms = None
-    latency_repeats = []
-    if len(renderers) > 1:
-        user_waves = [kv for kv in opts if kv.startswith(("dda_blocks=", "shadow_waves=", "dda_rays_per_wave=", "dda_split="))]
-        if renderers[0].aux is not None and not user_waves:
-            renderers[0].aux.set_option("dda_blocks", DDA_WAVES_ONE_FRAME)
-            renderers[0].aux.set_option("dda_rays_per_wave", -1)
-            renderers[0].aux.set_option("dda_split", -1)
-            renderers[0].ctx.set_option("shadow_waves", -1)  # the default
-        torch.cuda.synchronize()
-        r0 = time.perf_counter()
-        for _ in range(args.steps):
-            renderers[0].display(setup, frame_cnt=1, shadows=True, reflect=reflect)
-            gather.gather(renderers[0].image)
-        gather.finish()
-        renderers[0].synchronize()
-        torch.cuda.synchronize()
-        latency_ms = (time.perf_counter() - r0) / args.steps * 1e3
-        for _ in range(min(args.repeats, 2)):  # (spread of the one-frame figure)
+            rr.ctx.set_option("ray_sort", -1)
+        # latency: the same K steps with ONE frame in flight (every frame is finished before the next one is started)
+        latency_repeats = []
+        if len(renderers) > 1:
+            user_waves = [kv for kv in opts if kv.startswith(("dda_blocks=", "shadow_waves=", "dda_rays_per_wave=", "dda_split="))]
+            if renderers[0].aux is not None and not user_waves:
+                renderers[0].aux.set_option("dda_blocks", DDA_WAVES_ONE_FRAME)
+                renderers[0].aux.set_option("dda_rays_per_wave", -1)
+                renderers[0].aux.set_option("dda_split", -1)
+                renderers[0].ctx.set_option("shadow_waves", -1)  # the default
+            torch.cuda.synchronize()
             r0 = time.perf_counter()
             for _ in range(args.steps):
                 renderers[0].display(setup, frame_cnt=1, shadows=True, reflect=reflect)
@@ -708,48 +764,57 @@ def main():
             gather.finish()
             renderers[0].synchronize()
             torch.cuda.synchronize()
-            latency_repeats.append((time.perf_counter() - r0) / args.steps * 1e3)
-        # what the bounce's split walks did in the last of those frames
-        if reflect:
-            c0 = renderers[0].aux if renderers[0].aux is not None else renderers[0].ctx
-            split_stats = c0.stats_dda_split()
-        if renderers[0].aux is not None and not user_waves:
-            renderers[0].aux.set_option("dda_blocks", DDA_WAVES_THROUGHPUT)
-            renderers[0].aux.set_option("dda_rays_per_wave", DDA_RPW_THROUGHPUT)
-            renderers[0].aux.set_option("dda_split", DDA_SPLIT_THROUGHPUT)
-            renderers[0].ctx.set_option("shadow_waves", SHADOW_WAVES_THROUGHPUT)
-    # untimed pass: the full stage table (with two streams the stages overlap: their sum exceeds the frame)
-    for c in profiled:
-        c.prof_enable(True)
-        c.prof_reset()
-    nfull = min(args.steps, 10)
-    for _ in range(nfull):
-        step()
-    gather.finish()
-    for rr in renderers:
-        rr.synchronize()
-    prof_full = merged_prof()
-    for c in profiled:
-        c.prof_enable(False)
-    # the same stage table with every kernel alone on the chip: one context, one stream, one frame at a time
-    # (what a stage costs, as opposed to how long it lasts beside the kernels of three other streams)
-    alone = None
-    if rank == 0 and not args.animate and shards is None:
-        actx = ugrt.Context(W, H, device=local, light_grid=lg, rows=rows, flags=flags, uniform_dims=udims)
-        ar = ugrt.Renderer(actx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
-        for kv in opts:
-            k, v = kv.split("=")
-            if k != "dda_blocks":
-                actx.set_option(k, int(v))
-        for i in range(3 + nfull):
-            if i == 3:
-                actx.synchronize()
-                actx.prof_enable(True)
-                actx.prof_reset()
-            ar.display(setup, frame_cnt=1, shadows=True, reflect=reflect)
-        actx.synchronize()
-        alone = {k: round(v[0] / nfull, 4) for k, v in sorted(actx.prof_get().items()) if v[1]}
-        del ar, actx
+            latency_ms = (time.perf_counter() - r0) / args.steps * 1e3
+            for _ in range(min(args.repeats, 2)):  # (spread of the one-frame figure)
+                r0 = time.perf_counter()
+                for _ in range(args.steps):
+                    renderers[0].display(setup, frame_cnt=1, shadows=True, reflect=reflect)
+                    gather.gather(renderers[0].image)
+                gather.finish()
+                renderers[0].synchronize()
+                torch.cuda.synchronize()
+                latency_repeats.append((time.perf_counter() - r0) / args.steps * 1e3)
+            # what the bounce's split walks did in the last of those frames
+            if reflect:
+                c0 = renderers[0].aux if renderers[0].aux is not None else renderers[0].ctx
+                split_stats = c0.stats_dda_split()
+            if renderers[0].aux is not None and not user_waves:
+                renderers[0].aux.set_option("dda_blocks", DDA_WAVES_THROUGHPUT)
+                renderers[0].aux.set_option("dda_rays_per_wave", DDA_RPW_THROUGHPUT)
+                renderers[0].aux.set_option("dda_split", DDA_SPLIT_THROUGHPUT)
+                renderers[0].ctx.set_option("shadow_waves", SHADOW_WAVES_THROUGHPUT)
+        # untimed pass: the full stage table (with two streams the stages overlap: their sum exceeds the frame)
+        for c in profiled:
+            c.prof_enable(True)
+            c.prof_reset()
+        nfull = min(args.steps, 10)
+        for _ in range(nfull):
+            step()
+        gather.finish()
+        for rr in renderers:
+            rr.synchronize()
+        prof_full = merged_prof()
+        for c in profiled:
+            c.prof_enable(False)
+        # the same stage table with every kernel alone on the chip: one context, one stream, one frame at a time
+        # (what a stage costs, as opposed to how long it lasts beside the kernels of three other streams)
+        alone = None
+        if rank == 0 and not args.animate and shards is None:
+            actx = ugrt.Context(W, H, device=local, light_grid=lg, rows=rows, flags=flags, uniform_dims=udims)
+            ar = ugrt.Renderer(actx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
+            for kv in opts:
+                k, v = kv.split("=")
+                if k != "dda_blocks":
+                    actx.set_option(k, int(v))
+            for i in range(3 + nfull):
+                if i == 3:
+                    actx.synchronize()
+                    actx.prof_enable(True)
+                    actx.prof_reset()
+                ar.display(setup, frame_cnt=1, shadows=True, reflect=reflect)
+            actx.synchronize()
+            alone = {k: round(v[0] / nfull, 4) for k, v in sorted(actx.prof_get().items()) if v[1]}
+            del ar, actx
 
     verified, verify_detail = None, None
     if args.verify:
@@ -815,155 +880,156 @@ def main():
             sys.exit(1)
         return
 
-    stages = {k: dict(ms_per_launch=v[0] / v[1], launches_per_step=v[1] / float(nfull),
-                      ms_per_step=v[0] / nfull) for k, v in prof_full.items() if v[1]}
-    for k in tracers:  # the tracers' numbers come from the timed loop itself
-        if prof.get(k, (0, 0))[1]:
-            v = prof[k]
-            stages[k] = dict(ms_per_launch=v[0] / v[1], launches_per_step=v[1] / float(args.steps),
-                             ms_per_step=v[0] / args.steps)
-    gpu_ms = sum(v["ms_per_step"] for v in stages.values())
-    # the roofline figure is quoted on the longest tracer whose algorithmic bytes are bytes the kernel's algorithm
-    # really addresses (every staged reference of the primary pass, every cell and triangle a bounce ray meets); the
-    # two shadow kernels only have a work count in units of the reference's algorithm (work_reduction below)
-    dom = max(("trace_primary", "trace_dda") if reflect else ("trace_primary",),
-              key=lambda k: stages.get(k, {}).get("ms_per_step", 0))
-    dom_ms = stages[dom]["ms_per_launch"]
-    achieved = abytes[dom] / (dom_ms * 1e-3) / 1e9
-    kname = {"trace_primary": "k_trace_primary", "trace_shadow": "k_trace_shadow", "shadow_cull": "k_shadow_cull",
-             "trace_dda": "k_trace_dda"}[dom]
-    traffic, tent, twhy = pmc_traffic(args.workload, W, H, args.scale, kname) if world == 1 else (None, None, "N > 1")
-    if twhy:
-        log("[bench] roofline.traffic = null: " + twhy)
-    roofline = dict(bound="hbm", kernel=kname, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic,
-                    algorithmic_bytes_per_launch=int(abytes[dom]), ms_per_launch=round(dom_ms, 4),
-                    traffic_source=(dict(profile=tent["profile"], kernel_source_hash=tent["kernel_source_hash"])
-                                    if tent else None),
-                    traffic_error=twhy,
-                    note="achieved = algorithmic bytes of THIS kernel (SURVEY 8(d): 48 B per ray + 8 B per cell visited + "
-                         "52 B per triangle tested, as the per-ray algorithm counts them) / its launch time from hipEvents "
-                         "on its own stream inside the timed loop; traffic = HBM bytes per launch from rocprofv3 PMC "
-                         "passes of the same build (2*FETCH_SIZE + WRITE_SIZE, KiB units).  The factor 2 on FETCH_SIZE is the "
-                         "guide's correction for wide coalesced streaming reads; this kernel gathers (4-48 B per lane), for "
-                         "which the factor is uncalibrated: read traffic as an UPPER bound (between FETCH_SIZE + WRITE_SIZE "
-                         "and the figure given)",
-                    traffic_is_upper_bound=True)
-    # (the other tracer with byte-exact algorithmic bytes, for the record: which of the two is the longer one changes
-    # with the workload and from round to round)
-    others = {}
-    for k in (("trace_primary", "trace_dda") if reflect else ("trace_primary",)):
-        if k != dom and k in stages and k in abytes:
-            ms = stages[k]["ms_per_launch"]
-            others[{"trace_primary": "k_trace_primary", "trace_dda": "k_trace_dda"}[k]] = dict(
-                achieved=round(abytes[k] / (ms * 1e-3) / 1e9, 2), frac=round(abytes[k] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                algorithmic_bytes_per_launch=int(abytes[k]), ms_per_launch=round(ms, 4))
-    roofline["other_kernels"] = others
-    # whole-frame HBM figure: all kernels' PMC bytes of one frame over the frame time
-    frame_hbm = None
-    if tent and tent.get("frame_bytes"):
-        fb = float(tent["frame_bytes"])
-        frame_hbm = dict(bytes=int(fb), GBps=round(fb / (elapsed / args.steps) / 1e9, 1),
-                         frac=round(fb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4), profile=tent["profile"])
-    # NOT a roofline: how much less data the restructured shadow stage moves than the reference's algorithm would
-    # (every 64-ray chunk re-stages its cell's whole list).  The "GB/s" of that formula exceed the HBM
-    # peak because most of those bytes are never moved; reported as a work-reduction factor.
-    a11_ms = sum(stages.get(k, {}).get("ms_per_step", 0.0) for k in ("shadow_prep", "shadow_cull", "trace_shadow"))
-    work_reduction = None
-    if a11_ms > 0:
-        ref_bytes = abytes["stage_shadow_A11"]
-        moved = None
-        if tent:
-            pl = tent.get("per_frame_bytes", {})
-            mv = [pl.get(k) for k in ("k_shadow_keys", "k_shadow_boxes", "k_shadow_cull", "k_trace_shadow")]
-            moved = int(sum(x for x in mv if x)) if any(mv) else None
-        work_reduction = dict(stage="shadow (SURVEY A11: regroup + cull + exact kernels)",
-                              reference_algorithm_bytes=int(ref_bytes), ms=round(a11_ms, 4),
-                              pmc_bytes_of_the_stage_kernels=moved,
-                              bytes_not_moved_factor=(round(ref_bytes / float(moved), 1) if moved else None),
-                              note="reference_algorithm_bytes / ms = %.0f GB/s would be %.2f x the HBM peak: it is a count of "
-                                   "work the restructured stage avoids, not a bandwidth"
-                                   % (ref_bytes / (a11_ms * 1e-3) / 1e9, ref_bytes / (a11_ms * 1e-3) / 1e9 / HBM_PEAK_GBS))
+    if args.full:
+        stages = {k: dict(ms_per_launch=v[0] / v[1], launches_per_step=v[1] / float(nfull),
+                          ms_per_step=v[0] / nfull) for k, v in prof_full.items() if v[1]}
+        for k in tracers:  # the tracers' numbers come from the timed loop itself
+            if prof.get(k, (0, 0))[1]:
+                v = prof[k]
+                stages[k] = dict(ms_per_launch=v[0] / v[1], launches_per_step=v[1] / float(args.steps),
+                                 ms_per_step=v[0] / args.steps)
+        gpu_ms = sum(v["ms_per_step"] for v in stages.values())
+        # the roofline figure is quoted on the longest tracer whose algorithmic bytes are bytes the kernel's algorithm
+        # really addresses (every staged reference of the primary pass, every cell and triangle a bounce ray meets); the
+        # two shadow kernels only have a work count in units of the reference's algorithm (work_reduction below)
+        dom = max(("trace_primary", "trace_dda") if reflect else ("trace_primary",),
+                  key=lambda k: stages.get(k, {}).get("ms_per_step", 0))
+        dom_ms = stages[dom]["ms_per_launch"]
+        achieved = abytes[dom] / (dom_ms * 1e-3) / 1e9
+        kname = {"trace_primary": "k_trace_primary", "trace_shadow": "k_trace_shadow", "shadow_cull": "k_shadow_cull",
+                 "trace_dda": "k_trace_dda"}[dom]
+        traffic, tent, twhy = pmc_traffic(args.workload, W, H, args.scale, kname) if world == 1 else (None, None, "N > 1")
+        if twhy:
+            log("[bench] roofline.traffic = null: " + twhy)
+        roofline = dict(bound="hbm", kernel=kname, achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(achieved / HBM_PEAK_GBS, 5), traffic=traffic,
+                        algorithmic_bytes_per_launch=int(abytes[dom]), ms_per_launch=round(dom_ms, 4),
+                        traffic_source=(dict(profile=tent["profile"], kernel_source_hash=tent["kernel_source_hash"])
+                                        if tent else None),
+                        traffic_error=twhy,
+                        note="achieved = algorithmic bytes of THIS kernel (SURVEY 8(d): 48 B per ray + 8 B per cell visited + "
+                             "52 B per triangle tested, as the per-ray algorithm counts them) / its launch time from hipEvents "
+                             "on its own stream inside the timed loop; traffic = HBM bytes per launch from rocprofv3 PMC "
+                             "passes of the same build (2*FETCH_SIZE + WRITE_SIZE, KiB units).  The factor 2 on FETCH_SIZE is the "
+                             "guide's correction for wide coalesced streaming reads; this kernel gathers (4-48 B per lane), for "
+                             "which the factor is uncalibrated: read traffic as an UPPER bound (between FETCH_SIZE + WRITE_SIZE "
+                             "and the figure given)",
+                        traffic_is_upper_bound=True)
+        # (the other tracer with byte-exact algorithmic bytes, for the record: which of the two is the longer one changes
+        # with the workload and from round to round)
+        others = {}
+        for k in (("trace_primary", "trace_dda") if reflect else ("trace_primary",)):
+            if k != dom and k in stages and k in abytes:
+                ms = stages[k]["ms_per_launch"]
+                others[{"trace_primary": "k_trace_primary", "trace_dda": "k_trace_dda"}[k]] = dict(
+                    achieved=round(abytes[k] / (ms * 1e-3) / 1e9, 2), frac=round(abytes[k] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                    algorithmic_bytes_per_launch=int(abytes[k]), ms_per_launch=round(ms, 4))
+        roofline["other_kernels"] = others
+        # whole-frame HBM figure: all kernels' PMC bytes of one frame over the frame time
+        frame_hbm = None
+        if tent and tent.get("frame_bytes"):
+            fb = float(tent["frame_bytes"])
+            frame_hbm = dict(bytes=int(fb), GBps=round(fb / (elapsed / args.steps) / 1e9, 1),
+                             frac=round(fb / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4), profile=tent["profile"])
+        # NOT a roofline: how much less data the restructured shadow stage moves than the reference's algorithm would
+        # (every 64-ray chunk re-stages its cell's whole list).  The "GB/s" of that formula exceed the HBM
+        # peak because most of those bytes are never moved; reported as a work-reduction factor.
+        a11_ms = sum(stages.get(k, {}).get("ms_per_step", 0.0) for k in ("shadow_prep", "shadow_cull", "trace_shadow"))
+        work_reduction = None
+        if a11_ms > 0:
+            ref_bytes = abytes["stage_shadow_A11"]
+            moved = None
+            if tent:
+                pl = tent.get("per_frame_bytes", {})
+                mv = [pl.get(k) for k in ("k_shadow_keys", "k_shadow_boxes", "k_shadow_cull", "k_trace_shadow")]
+                moved = int(sum(x for x in mv if x)) if any(mv) else None
+            work_reduction = dict(stage="shadow (SURVEY A11: regroup + cull + exact kernels)",
+                                  reference_algorithm_bytes=int(ref_bytes), ms=round(a11_ms, 4),
+                                  pmc_bytes_of_the_stage_kernels=moved,
+                                  bytes_not_moved_factor=(round(ref_bytes / float(moved), 1) if moved else None),
+                                  note="reference_algorithm_bytes / ms = %.0f GB/s would be %.2f x the HBM peak: it is a count of "
+                                       "work the restructured stage avoids, not a bandwidth"
+                                       % (ref_bytes / (a11_ms * 1e-3) / 1e9, ref_bytes / (a11_ms * 1e-3) / 1e9 / HBM_PEAK_GBS))
 
-    cpu = None
-    if world == 1 and args.cpu_seconds > 0:
-        try:
-            cpu = cpu_baseline(ugrt, s, setup, W, H, lg, udims, args.cpu_seconds)
-        except Exception as e:  # the baseline is a report, never a reason to lose the measurement
-            cpu = dict(value=None, unit="Mrays/s", cores=0, kind="port", sample="failed: %r" % (e,))
+        cpu = None
+        if world == 1 and args.cpu_seconds > 0:
+            try:
+                cpu = cpu_baseline(ugrt, s, setup, W, H, lg, udims, args.cpu_seconds)
+            except Exception as e:  # the baseline is a report, never a reason to lose the measurement
+                cpu = dict(value=None, unit="Mrays/s", cores=0, kind="port", sample="failed: %r" % (e,))
 
-    # one frame at a time, cut into bands of tile rows on streams of their own (renderer.BandedRenderer): the light grid,
-    # the uniform grid and the bounce whole on one side context.  Verified against the renderers' frame.
-    banded = None
-    if world == 1 and args.bands_in_frame and reflect and not args.animate and shards is None and not args.no_overlap:
-        banded = {}
-        try:
-            for nb in args.bands_in_frame:
-                br = ugrt.BandedRenderer(ugrt.Context, W, H, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"],
-                                         bands=nb, device=local, light_grid=lg, uniform_dims=udims, flags=flags)
-                for _ in range(6):
-                    br.display(setup, shadows=True, reflect=True)
-                br.synchronize()
-                torch.cuda.synchronize()
-                times = []
-                for _ in range(3):
-                    r0 = time.perf_counter()
-                    for _ in range(args.steps):
+        # one frame at a time, cut into bands of tile rows on streams of their own (renderer.BandedRenderer): the light grid,
+        # the uniform grid and the bounce whole on one side context.  Verified against the renderers' frame.
+        banded = None
+        if world == 1 and args.bands_in_frame and reflect and not args.animate and shards is None and not args.no_overlap:
+            banded = {}
+            try:
+                for nb in args.bands_in_frame:
+                    br = ugrt.BandedRenderer(ugrt.Context, W, H, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"],
+                                             bands=nb, device=local, light_grid=lg, uniform_dims=udims, flags=flags)
+                    for _ in range(6):
                         br.display(setup, shadows=True, reflect=True)
                     br.synchronize()
                     torch.cuda.synchronize()
-                    times.append((time.perf_counter() - r0) / args.steps * 1e3)
-                names = ["image", "is_shadowed", "intersect_id", "t", "normal", "dir", "hit_t", "hit_id", "active"]
-                same = all(bool(torch.equal(getattr(br, k).view(torch.uint8), getattr(renderers[0], k).view(torch.uint8)))
-                           for k in names) if not args.animate else None
-                banded["bands_%d" % nb] = {"ms_per_step": round(times[0], 4), "repeat_ms_per_step": [round(x, 4) for x in times[1:]],
-                                           "equal_to_the_timed_renderers_frame": same}
-                if same is False:
-                    failed = True
-                del br
-                gc.collect()
-        except Exception as e:
-            banded["error"] = repr(e)
-            failed = True
+                    times = []
+                    for _ in range(3):
+                        r0 = time.perf_counter()
+                        for _ in range(args.steps):
+                            br.display(setup, shadows=True, reflect=True)
+                        br.synchronize()
+                        torch.cuda.synchronize()
+                        times.append((time.perf_counter() - r0) / args.steps * 1e3)
+                    names = ["image", "is_shadowed", "intersect_id", "t", "normal", "dir", "hit_t", "hit_id", "active"]
+                    same = all(bool(torch.equal(getattr(br, k).view(torch.uint8), getattr(renderers[0], k).view(torch.uint8)))
+                               for k in names) if not args.animate else None
+                    banded["bands_%d" % nb] = {"ms_per_step": round(times[0], 4), "repeat_ms_per_step": [round(x, 4) for x in times[1:]],
+                                               "equal_to_the_timed_renderers_frame": same}
+                    if same is False:
+                        failed = True
+                    del br
+                    gc.collect()
+            except Exception as e:
+                banded["error"] = repr(e)
+                failed = True
 
-    # the same frame from the C++ host (child process), one frame at a time
-    cpp = None
-    if world == 1 and args.other_configs and reflect and not args.animate and args.scale == 1.0 and not (args.width or args.height):
-        try:
-            cpp = cpp_driver_leg(ugrt, torch, s, W, H, renderers[0].image)
-        except Exception as e:
-            cpp = {"error": repr(e)}
-        if cpp and cpp.get("ppm_equals_the_timed_renderers_image") is False:
-            failed = True
+        # the same frame from the C++ host (child process), one frame at a time
+        cpp = None
+        if world == 1 and args.other_configs and reflect and not args.animate and args.scale == 1.0 and not (args.width or args.height):
+            try:
+                cpp = cpp_driver_leg(ugrt, torch, s, W, H, renderers[0].image)
+            except Exception as e:
+                cpp = {"error": repr(e)}
+            if cpp and cpp.get("ppm_equals_the_timed_renderers_image") is False:
+                failed = True
 
-    # the other BASELINE configurations, in this same process, behind the headline measurement (each verified)
-    other = None
-    default_run = (world == 1 and args.workload == "crash" and args.scale == 1.0 and not (args.width or args.height) and reflect
-                   and not args.animate and not args.no_overlap and shards is None and not args.waiting_builds and not args.opt)
-    if args.other_configs and default_run:
-        for rr in renderers:
-            rr.close()
-        gc.collect()
-        other = {}
-        t_other = time.time()
-        try:
-            hall = load_scene(ugrt, "hall", 1.0, rank)
-            other["hall_1024"] = dict(measure_config(ugrt, torch, hall, 1024, 1024, local, False, False, 10, 3),
-                                      config="BASELINE configs[1] stand-in: procedural hall, primary + shadow (1 light, all chunks)")
-            del hall
-            other["crash_4k"] = dict(measure_config(ugrt, torch, s, 3840, 2160, local, True, False, 10, 3),
-                                     config="BASELINE configs[3]'s frame (3840x2160, primary + shadow + bounce) on ONE GPU: "
-                                            "the per-GPU ceiling of the 8-GPU configuration")
-            other["animated"] = dict(measure_config(ugrt, torch, s, W, H, local, True, True, 10, 3),
-                                     config="BASELINE configs[4]: animated sub-range transformed and all three grids rebuilt "
-                                            "every frame, 1920x1080, primary + shadow + bounce")
-        except Exception as e:  # the headline stands; what failed is said
-            other["error"] = repr(e)
-        other["wall_s"] = round(time.time() - t_other, 1)
-        bad_other = [k for k, v in other.items() if isinstance(v, dict) and v.get("verified") is False]
-        if bad_other or "error" in other:
-            failed = True
-            verify_detail = (verify_detail or []) + [{"other_configs": bad_other or other.get("error")}]
+        # the other BASELINE configurations, in this same process, behind the headline measurement (each verified)
+        other = None
+        default_run = (world == 1 and args.workload == "crash" and args.scale == 1.0 and not (args.width or args.height) and reflect
+                       and not args.animate and not args.no_overlap and shards is None and not args.waiting_builds and not args.opt)
+        if args.other_configs and default_run:
+            for rr in renderers:
+                rr.close()
+            gc.collect()
+            other = {}
+            t_other = time.time()
+            try:
+                hall = load_scene(ugrt, "hall", 1.0, rank)
+                other["hall_1024"] = dict(measure_config(ugrt, torch, hall, 1024, 1024, local, False, False, 10, 3),
+                                          config="BASELINE configs[1] stand-in: procedural hall, primary + shadow (1 light, all chunks)")
+                del hall
+                other["crash_4k"] = dict(measure_config(ugrt, torch, s, 3840, 2160, local, True, False, 10, 3),
+                                         config="BASELINE configs[3]'s frame (3840x2160, primary + shadow + bounce) on ONE GPU: "
+                                                "the per-GPU ceiling of the 8-GPU configuration")
+                other["animated"] = dict(measure_config(ugrt, torch, s, W, H, local, True, True, 10, 3),
+                                         config="BASELINE configs[4]: animated sub-range transformed and all three grids rebuilt "
+                                                "every frame, 1920x1080, primary + shadow + bounce")
+            except Exception as e:  # the headline stands; what failed is said
+                other["error"] = repr(e)
+            other["wall_s"] = round(time.time() - t_other, 1)
+            bad_other = [k for k, v in other.items() if isinstance(v, dict) and v.get("verified") is False]
+            if bad_other or "error" in other:
+                failed = True
+                verify_detail = (verify_detail or []) + [{"other_configs": bad_other or other.get("error")}]
 
     value = rays_total / elapsed * args.steps / 1e6
     line = {
@@ -1011,29 +1077,32 @@ def main():
                            if args.shard_builds else "replicated per rank",
             "parallelism": "image bands of tile rows, 1 process per GPU, RCCL gather of RGB" if world > 1 else "1 GPU",
         },
-        "roofline": roofline,
-        "frame_hbm": frame_hbm,
-        "work_reduction": work_reduction,
-        "cpu_baseline": cpu,
         "verified_against_single_context_frame": verified,
         "verify_mismatches_per_renderer": verify_detail,
-        "repeat_ms_per_step": [round(x, 4) for x in repeats],
-        "ms_per_step_with_the_ray_sort_in_every_frame": [round(x, 4) for x in ray_sort_kept],
-        "repeat_ms_per_step_one_frame_in_flight": [round(x, 4) for x in latency_repeats],
-        "ms_per_step_one_frame_in_flight": round(latency_ms, 4) if latency_ms else None,
-        "gpu_ms_per_step_in_kernels": round(gpu_ms, 4),
-        "radix_launches_per_step": round(radix_per_frame, 2),  # histogram + pass kernels of the built-in sort (ugrt_ctx_get_state)
-        "sort_rank_atomic": ctx.get_state("sort_rank_atomic"),
-        "stages_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(stages.items())},
-        "stages_ms_per_step_alone_on_one_stream": alone,
         "warmup_steps_run": warm,
         "band_bounds_tile_rows": list(bounds) if world > 1 else None,
         "band_balance_rounds": balance_log if world > 1 else None,
-        "algorithmic_bytes": {k: int(v) for k, v in abytes.items()},
-        "other_configs": other,
-        "one_frame_in_bands": banded,
-        "cpp_driver": cpp,
     }
+    if args.full:
+        line.update({
+            "roofline": roofline,
+            "frame_hbm": frame_hbm,
+            "work_reduction": work_reduction,
+            "cpu_baseline": cpu,
+            "repeat_ms_per_step": [round(x, 4) for x in repeats],
+            "ms_per_step_with_the_ray_sort_in_every_frame": [round(x, 4) for x in ray_sort_kept],
+            "repeat_ms_per_step_one_frame_in_flight": [round(x, 4) for x in latency_repeats],
+            "ms_per_step_one_frame_in_flight": round(latency_ms, 4) if latency_ms else None,
+            "gpu_ms_per_step_in_kernels": round(gpu_ms, 4),
+            "radix_launches_per_step": round(radix_per_frame, 2),  # histogram + pass kernels of the built-in sort (ugrt_ctx_get_state)
+            "sort_rank_atomic": ctx.get_state("sort_rank_atomic"),
+            "stages_ms_per_step": {k: round(v["ms_per_step"], 4) for k, v in sorted(stages.items())},
+            "stages_ms_per_step_alone_on_one_stream": alone,
+            "algorithmic_bytes": {k: int(v) for k, v in abytes.items()},
+            "other_configs": other,
+            "one_frame_in_bands": banded,
+            "cpp_driver": cpp,
+        })
     if failed:
         line["error"] = ("verification failed: the timed frames differ from the sequential waiting-build context in %r; "
                          "the measured %.3f Mrays/s are withheld" % (verify_detail, value))

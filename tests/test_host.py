@@ -1,20 +1,39 @@
 """Host layer of the product (loader, material file, camera, PPM) against the checkers:
-the REFERENCE's own obj_parser (oracle/_ref/ref_objdump, built from /root/reference) and
-the oracle's restatement of camera.h / per_app_funcs.h / scene.h."""
+the REFERENCE's own obj_parser (its output on the scene files below, recorded in tests/golden/ref_objdump_*.npz by
+tests/golden/make_ref_objdump.py; where oracle/_ref/ref_objdump is built, the parser is run as well and must still
+agree with the record) and the oracle's restatement of camera.h / per_app_funcs.h / scene.h."""
+import hashlib
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-def ref_dump(O, obj_path, tmp_path):
-    if not os.path.exists(O.REF_OBJDUMP):
-        pytest.skip("oracle/_ref/ref_objdump not built (reference checkout absent)")
-    out = str(tmp_path / "dump.bin")
-    subprocess.run([O.REF_OBJDUMP, os.path.basename(obj_path), out], cwd=os.path.dirname(obj_path), check=True,
-                   capture_output=True)
-    raw = open(out, "rb").read()
+QUIRKS_MTL = "newmtl red\nKd 1 0 0\nr 0.25\nnewmtl redder\nKd 0.5 0 0\nnewmtl blue\nKa 0 0 1\n"
+QUIRKS_OBJ = ("# comment\nmtllib q.mtl\nv 0 0 0\nv 1 0 0\nv 1 1 0\nv 0 1 0\nvn 0 0 1\nvt 0 0 0\n"
+              "usemtl blue\nf 1 2 3 4\nusemtl red\nf 1/1 2/1 3/1\nf 1//1 2//1 4//1\nusemtl redd\nf -4 -3 -2\n"
+              "usemtl nosuch\nf 1/1/1 3/1/1 4/1/1\ng grp\ns off\no obj\n")
+REF_SCENES = ("cornell", "hall", "crash", "quirks")
+
+
+def ref_scene(ugrt, name, d):
+    """Writes the files of scene `name` into directory d: (OBJ path, generator info or None)."""
+    if name == "quirks":
+        with open(os.path.join(d, "q.mtl"), "w") as f:
+            f.write(QUIRKS_MTL)
+        with open(os.path.join(d, "q.obj"), "w") as f:
+            f.write(QUIRKS_OBJ)
+        return os.path.join(d, "q.obj"), None
+    gen = {"cornell": lambda d: ugrt.scenes.cornell(d), "hall": lambda d: ugrt.scenes.hall(d, scale=0.05),
+           "crash": lambda d: ugrt.scenes.crash(d, scale=0.01)}[name]
+    s = gen(str(d))
+    return s["obj"], s
+
+
+def parse_ref_dump(raw):
+    """The binary oracle/ref_objdump.cpp writes: counts, vertices, faces, material indices, bbox, materials."""
     nv, nf, nm = np.frombuffer(raw, np.int32, 3)
     o = 12
     verts = np.frombuffer(raw, np.float32, nv * 3, o); o += nv * 12
@@ -25,15 +44,31 @@ def ref_dump(O, obj_path, tmp_path):
     return dict(verts=verts, faces=faces, matidx=matidx, bbox=bbox, mats=mats)
 
 
+def ref_dump(O, name, obj_path, tmp_path):
+    """The reference parser's reading of obj_path: the record of tests/golden (the file must be the one recorded),
+    checked against the parser itself where oracle/_ref/ref_objdump is built."""
+    with np.load(os.path.join(GOLDEN, "ref_objdump_%s.npz" % name)) as z:
+        rec = {k: z[k] for k in z.files}
+    sha = hashlib.sha256(open(obj_path, "rb").read()).hexdigest()
+    assert sha == str(rec.pop("obj_sha256")), \
+        "%s is not the file recorded in ref_objdump_%s.npz (tests/golden/make_ref_objdump.py)" % (obj_path, name)
+    if os.path.exists(O.REF_OBJDUMP):
+        out = str(tmp_path / "dump.bin")
+        subprocess.run([O.REF_OBJDUMP, os.path.basename(obj_path), out], cwd=os.path.dirname(obj_path), check=True,
+                       capture_output=True)
+        live = parse_ref_dump(open(out, "rb").read())
+        for k, v in rec.items():
+            np.testing.assert_array_equal(live[k], v, err_msg="the reference parser no longer gives the record: " + k)
+    return rec
+
+
 @pytest.mark.parametrize("which", ["cornell", "hall", "crash"])
 def test_loader_matches_reference_parser(ugrt, O, tmp_path, which):
-    gen = {"cornell": lambda d: ugrt.scenes.cornell(d), "hall": lambda d: ugrt.scenes.hall(d, scale=0.05),
-           "crash": lambda d: ugrt.scenes.crash(d, scale=0.01)}[which]
-    s = gen(str(tmp_path))
+    _, s = ref_scene(ugrt, which, tmp_path)
     m = ugrt.Model()
     m.some_material(s["mat"])
     m.load_model(s["obj"])
-    ref = ref_dump(O, s["obj"], tmp_path)
+    ref = ref_dump(O, which, s["obj"], tmp_path)
     assert m.num_faces == s["num_faces"] == len(ref["faces"]) // 3
     np.testing.assert_array_equal(m.h_vertexlist, ref["verts"])
     np.testing.assert_array_equal(m.h_facelist, ref["faces"])
@@ -49,14 +84,10 @@ def test_loader_matches_reference_parser(ugrt, O, tmp_path, which):
 
 def test_loader_obj_grammar_quirks(ugrt, O, tmp_path):
     """negative indices, v/vt/vn forms, quads cut to 3 indices, prefix material lookup, comments."""
-    (tmp_path / "q.mtl").write_text("newmtl red\nKd 1 0 0\nr 0.25\nnewmtl redder\nKd 0.5 0 0\nnewmtl blue\nKa 0 0 1\n")
-    (tmp_path / "q.obj").write_text(
-        "# comment\nmtllib q.mtl\nv 0 0 0\nv 1 0 0\nv 1 1 0\nv 0 1 0\nvn 0 0 1\nvt 0 0 0\n"
-        "usemtl blue\nf 1 2 3 4\nusemtl red\nf 1/1 2/1 3/1\nf 1//1 2//1 4//1\nusemtl redd\nf -4 -3 -2\n"
-        "usemtl nosuch\nf 1/1/1 3/1/1 4/1/1\ng grp\ns off\no obj\n")
+    obj, _ = ref_scene(ugrt, "quirks", tmp_path)
     m = ugrt.Model()
-    m.load_model(str(tmp_path / "q.obj"))
-    ref = ref_dump(O, str(tmp_path / "q.obj"), tmp_path)
+    m.load_model(obj)
+    ref = ref_dump(O, "quirks", obj, tmp_path)
     np.testing.assert_array_equal(m.h_facelist, ref["faces"])
     np.testing.assert_array_equal(m.h_materiallist_index, ref["matidx"])
     np.testing.assert_array_equal(m.h_vertexlist, ref["verts"])

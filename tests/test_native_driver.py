@@ -159,8 +159,8 @@ def test_bench_starts_its_own_ranks():
     env = dict(os.environ, UGRT_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--cpu-seconds", "0",
-           "--repeats", "0", "--scale", "0.05", "--width", "640", "--height", "360", "--balance-rounds", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4", "--warmup", "2",
+           "--cpu-seconds", "0", "--repeats", "0", "--scale", "0.05", "--width", "640", "--height", "360", "--balance-rounds", "1"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -178,8 +178,8 @@ def test_bench_fails_when_the_timed_frames_do_not_verify():
     import sys
 
     env = dict(os.environ, UGRT_BENCH_FORCE_MISMATCH="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-seconds", "0", "--repeats", "0",
-           "--scale", "0.05", "--width", "640", "--height", "360"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0",
+           "--repeats", "0", "--scale", "0.05", "--width", "640", "--height", "360"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode != 0, p.stdout[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -189,6 +189,40 @@ def test_bench_fails_when_the_timed_frames_do_not_verify():
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["verified_against_single_context_frame"] is True and line["value"] > 0 and "error" not in line
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_verified_frame(tmp_path):
+    """A plain run (no --full) prints the headline alone and, with --dump-outputs, writes the buffers of its last timed
+    frame as float .npy files of at most 64 MB in all; a --full run of the same arguments, whose frames are verified
+    against one sequential context, writes the same files bit for bit."""
+    import json
+    import sys
+
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--scale", "0.05", "--width",
+            "640", "--height", "360"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--cpu-seconds", "0", "--repeats", "0"])):
+        p = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / mode)], cwd=ROOT, capture_output=True,
+                           text=True, timeout=600)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
+        lines[mode] = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["higher_is_better"] is True
+    assert plain["verified_against_single_context_frame"] is None and "roofline" not in plain
+    assert full["verified_against_single_context_frame"] is True and "roofline" in full
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names == sorted(os.listdir(tmp_path / "full"))
+    assert {"image.npy", "t.npy", "intersect_id.npy", "is_shadowed.npy", "hit_id.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64), (n, a.dtype)
+        np.testing.assert_array_equal(a, b, err_msg=n)
+        total += a.nbytes
+    assert total <= 64 << 20
+    image = np.load(tmp_path / "plain" / "image.npy")
+    assert image.shape == (360, 640, 3) and image.max() > 0
 
 
 @pytest.mark.gpu
@@ -205,7 +239,7 @@ def test_bench_two_ranks_on_one_gpu_gather_the_right_image(extra):
     scale = ["--scale", "0.05"] if "--config3" not in extra else ["--scale", "0.02"]
     size = [] if "--config3" in extra else ["--width", "640", "--height", "360"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "4",
            "--warmup", "2", "--cpu-seconds", "0", "--repeats", "0", "--verify"] + scale + size + extra
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]

@@ -6,8 +6,8 @@
 #   gpurun_out/prof_TAG/sq      --pmc SQ_* (issue / wait / occupancy of every kernel)
 #   gpurun_out/prof_TAG/kernel_resources.txt   registers / spills / scratch / LDS of every kernel (tools/kernel_resources.py)
 # Fold them afterwards with tools/pmc_traffic.py into profiles/.
-# The first run is the default command (its line also carries the other BASELINE configs and the verification).  The
-# passes under rocprofv3 add --no-verify --no-other-configs: their per-kernel averages are then those of the timed
+# The first run is the default command with --full (its line also carries the other BASELINE configs and the verification).
+# The passes under rocprofv3 are plain runs and add --no-verify --no-other-configs: their per-kernel averages are then those of the timed
 # configuration alone (the verifying context runs one stream, other launch shapes and waiting builds; the other configs
 # other sizes), which is what roofline.traffic / frame_hbm are attributed to.
 set -e
@@ -16,7 +16,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof_$TAG
 mkdir -p $OUT
 python3 tools/kernel_resources.py -o $OUT/kernel_resources.txt > /dev/null
-python3 bench.py --steps 20 --warmup 5 --cpu-seconds 0 "$@" > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --steps 20 --warmup 5 --cpu-seconds 0 "$@" > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o s --output-format csv -- python3 bench.py --steps 20 --warmup 5 --cpu-seconds 0 --repeats 0 --no-verify --no-other-configs "$@" > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/fetch -o f --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --repeats 0 --no-verify --no-other-configs "$@" > /dev/null 2> $OUT/fetch.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/write -o w --output-format csv -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --repeats 0 --no-verify --no-other-configs "$@" > /dev/null 2> $OUT/write.err
