@@ -1,0 +1,41 @@
+"""Writes tests/golden/ref_kernels_<case>.npz and ref_kernels_animate.npz (copy_data_transform): what the reference's
+own CUDA kernels (oracle/_ref/ref_kernels, built by `make -C oracle ref` where the reference checkout is present)
+compute, stage by stage, on the inputs of the cases of tests/test_reference_kernels.py, recorded with the SHA-256 of
+each stage's inputs and what the run reported (shared-memory overrun, schedule dependence).  Arrays up to 16 KiB are
+stored whole, larger ones as a SHA-256 and a seeded sample.  tests/test_reference_kernels.py compares the oracle and the product with these records, and the
+live binary where it is built.
+Usage: python tests/golden/make_ref_kernels.py [case ...]"""
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import oracle_lib as O  # noqa: E402
+import test_reference_kernels as T  # noqa: E402
+
+if not os.path.exists(O.REF_KERNELS):
+    sys.exit("oracle/_ref/ref_kernels is not built (make -C oracle ref)")
+for name in (sys.argv[1:] or sorted(T.CASES)):
+    ins, outs = T.all_outputs(name, lambda st, i: T.run_reference(name, st, i))
+    rec = T.record_of(name, {st: {k: outs[st][k] for k in T.STAGE_OUTPUTS[st]} for st in T.STAGE_OUTPUTS})
+    for st, i in ins.items():
+        rec[st + "/input_sha"] = np.array(T.input_sha(i))
+    for st in T.REPORTED:
+        for k in T.REPORTS:
+            if k in outs[st]:
+                rec["%s/report/%s" % (st, k)] = np.int64(outs[st][k][0])
+    path = os.path.join(HERE, "ref_kernels_%s.npz" % name)
+    np.savez_compressed(path, **rec)
+    print("wrote", os.path.basename(path), os.path.getsize(path), "bytes",
+          {k.split("/")[0]: int(v) for k, v in rec.items() if "/report/" in k and "overrun_bytes" in k})
+rec = {}
+_, verts, orig, off, size = T.animate_inputs()
+for i, rot in enumerate(T.ANIMATE_ROTS):
+    ins = dict(verts=verts, orig=orig, offset=off, rot=float(np.float32(rot)))
+    rec["%d/input_sha" % i] = np.array(T.input_sha(ins))
+    rec["%d/verts/sha" % i] = np.array(T.array_sha(O.run_ref_kernels("animate", **ins)["verts"]))
+np.savez_compressed(os.path.join(HERE, "ref_kernels_animate.npz"), **rec)
+print("wrote ref_kernels_animate.npz")

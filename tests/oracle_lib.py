@@ -12,6 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 LIB = os.path.join(ORACLE_DIR, "libugrt_oracle.so")
 REF_OBJDUMP = os.path.join(ORACLE_DIR, "_ref", "ref_objdump")
+REF_KERNELS = os.path.join(ORACLE_DIR, "_ref", "ref_kernels")
 PI_F = float(np.float32(np.pi))
 
 
@@ -377,3 +378,80 @@ def frame(scene, setup, W, H, rows=None, light_grid=(128, 128), all_chunks=False
         add_shadows(img, is_shadowed, p0, n)
     r["image"], r["mat_ids"] = img, ids
     return r
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# oracle/_ref/ref_kernels (the reference's kernels as host C++, oracle/ref_kernels.cpp): its named-array file format
+
+_IO_TYPES = {"f": np.float32, "i": np.int32, "u": np.uint32, "b": np.uint8}
+_IO_CODES = {np.dtype(v): k for k, v in _IO_TYPES.items()}
+
+
+def write_ref_io(arrays):
+    """{name: array or scalar} -> bytes.  Python ints are int32, floats float32, str the stage name (u8)."""
+    out = [b"UGRK", np.uint32(len(arrays)).tobytes()]
+    for name, a in sorted(arrays.items()):
+        if isinstance(a, str):
+            a = np.frombuffer(a.encode(), np.uint8)
+        elif isinstance(a, (bool, int, np.integer)):
+            a = np.array([a], np.int32)
+        elif isinstance(a, (float, np.floating)):
+            a = np.array([a], np.float32)
+        a = np.ascontiguousarray(a).reshape(-1)
+        if a.dtype == np.int64:
+            a = a.astype(np.int32)
+        code = _IO_CODES[a.dtype]
+        nb = name.encode()
+        out += [np.uint32(len(nb)).tobytes(), nb, code.encode(), np.uint64(a.size).tobytes(), a.tobytes()]
+    return b"".join(out)
+
+
+def read_ref_io(blob):
+    assert blob[:4] == b"UGRK", "not a ref_kernels file"
+    count = int(np.frombuffer(blob, np.uint32, 1, 4)[0])
+    pos, out = 8, {}
+    for _ in range(count):
+        n = int(np.frombuffer(blob, np.uint32, 1, pos)[0])
+        name = blob[pos + 4:pos + 4 + n].decode()
+        pos += 4 + n
+        dt = _IO_TYPES[blob[pos:pos + 1].decode()]
+        cnt = int(np.frombuffer(blob, np.uint64, 1, pos + 1)[0])
+        pos += 9
+        out[name] = np.frombuffer(blob, dt, cnt, pos).copy()
+        pos += cnt * np.dtype(dt).itemsize
+    return out
+
+
+def run_ref_kernels(stage, **arrays):
+    """Runs one stage of the reference's kernels (oracle/_ref/ref_kernels) on the given inputs."""
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as d:
+        src, dst = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        with open(src, "wb") as f:
+            f.write(write_ref_io(dict(arrays, stage=stage)))
+        p = subprocess.run([REF_KERNELS, src, dst], capture_output=True, text=True)
+        assert p.returncode == 0, "ref_kernels %s: exit %d %s" % (stage, p.returncode, p.stderr[-2000:])
+        with open(dst, "rb") as f:
+            return read_ref_io(f.read())
+
+
+def fill_2d(rng, scan, nby):
+    """orc_fill_2d alone: the unsorted (key, value) lists of a 2D grid build."""
+    F = len(scan)
+    R = int(scan[-1]) if F else 0
+    keys = np.zeros(max(R, 1), np.uint32)
+    vals = np.zeros(max(R, 1), np.uint32)
+    _lib.orc_fill_2d(_p(_i32(rng)), _p(_u32(scan)), C.c_int(F), C.c_int(nby), _p(keys), _p(vals))
+    return keys[:R], vals[:R]
+
+
+def fill_slabs(rng, scan, zlist, nby, slabs):
+    """orc_fill_slabs alone: the unsorted (key, value) lists of a z-slab grid build."""
+    F = len(scan)
+    R = int(scan[-1]) if F else 0
+    keys = np.zeros(max(R, 1), np.uint32)
+    vals = np.zeros(max(R, 1), np.uint32)
+    _lib.orc_fill_slabs(_p(_i32(rng)), _p(_u32(scan)), _p(_u32(zlist)), C.c_int(F), C.c_int(nby), C.c_int(slabs),
+                        _p(keys), _p(vals))
+    return keys[:R], vals[:R]
