@@ -341,6 +341,34 @@ int ugrt_shade_reflect(ugrt_ctx *ctx, unsigned char *d_img, const float *d_norma
 		       const float *d_vertlist, const int *d_trilist, const float *d_rays, const int *d_active,
 		       const float *d_hit_t, const int *d_hit_id);
 
+/* ---- device: reflections of depth D ----------------
+ * Level 1 is ugrt_reflect_rays + ugrt_trace_dda.  Level j+1 (j >= 1) is ugrt_reflect_rays_next from level j's
+ * hits + ugrt_trace_dda.  The D levels of a frame lie one behind the other: level j's rays at (j-1)*W*H*6 floats,
+ * its active / hit_t / hit_id at (j-1)*W*H entries, each indexed by absolute pixel p = p0 + i as every per-pixel
+ * array of the frame; the caller sizes them for `depth` levels. */
+#define UGRT_MAX_REFLECT_DEPTH 8
+/* The next reflected rays from one level's hits, for the context's band: for a pixel with d_active[p],
+ * d_hit_t[p] > 0, d_hit_id[p] >= 0 and d_reflect[d_mat_idx[d_hit_id[p]]] > 0 (material in range), P = o + t*d,
+ * n = normalize(e1 x e2) turned so that d.n <= 0, ray {P + eps*n, d - 2(d.n)n} and d_active_next[p] = 1 (the
+ * arithmetic of ugrt_reflect_rays with the ray's own origin); every other pixel: six zeros and 0.  Stage
+ * UGRT_ST_REFLECT_GEN.  The ugrt_trace_dda that follows on the same context walks without the split-walk history
+ * (option "dda_split"), which stays that of the level-1 launches (ugrt_reflect_rays); results do not change. */
+int ugrt_reflect_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+			   const int *d_hit_id, const int *d_mat_idx, const float *d_reflect, int num_materials,
+			   const float *d_vertlist, const int *d_trilist, float eps, float *d_rays_next,
+			   int *d_active_next);
+/* Lambertian shading blended over `depth` (1..UGRT_MAX_REFLECT_DEPTH) reflection levels, d_rays / d_active /
+ * d_hit_t / d_hit_id holding levels 1..depth stacked as above.  Front to back from acc = 0, w = 1: a level L_j
+ * (clamped Lambert colour of its hit, 0 on a miss) whose pixel goes on to level j+1 adds (w*(1-k_j))*L_j and sets
+ * w = w*k_j (k_j: reflect of its material); the first level that does not go on (level depth at the latest) adds
+ * w*L_j.  depth 1 gives ugrt_shade_reflect's image byte for byte.  d_intersect_id is rewritten to material indices
+ * as ugrt_shade_reflect does.  Stage UGRT_ST_SHADE.  A depth outside 1..8 or a null argument: UGRT_EINVAL. */
+int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+			     const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+			     const int *d_mat_idx, const float *d_mat_list, const float *d_reflect,
+			     int num_materials, const float *d_vertlist, const int *d_trilist, int depth,
+			     const float *d_rays, const int *d_active, const float *d_hit_t, const int *d_hit_id);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

@@ -53,6 +53,7 @@ FLAG_STATIC_GEOMETRY = 4
 FLAG_STRICT_TEXTURE = 8
 CHUNKS_ON_DEVICE = 0xFFFFFFFF
 GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM = 0, 1, 2
+MAX_REFLECT_DEPTH = 8  # UGRT_MAX_REFLECT_DEPTH
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -149,6 +150,8 @@ PROTOTYPES = {
     "ugrt_reflect_rays": (C.c_int, [_P] * 7 + [C.c_int, _P, _P, C.c_float, _P, _P]),
     "ugrt_trace_dda": (C.c_int, [_P] * 10),
     "ugrt_shade_reflect": (C.c_int, [_P] * 10 + [C.c_int] + [_P] * 6),
+    "ugrt_reflect_rays_next": (C.c_int, [_P] * 7 + [C.c_int, _P, _P, C.c_float, _P, _P]),
+    "ugrt_shade_reflect_depth": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 4),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

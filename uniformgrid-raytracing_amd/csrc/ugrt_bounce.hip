@@ -1,0 +1,203 @@
+// ugrt_bounce.hip -- reflections of any depth through the uniform grid (not in the reference; DESIGN.md A13 and
+// section 6).  Level 1 is ugrt_reflect_rays + ugrt_trace_dda as they are; a level j >= 2 is ugrt_reflect_rays_next from
+// level j-1's hits + ugrt_trace_dda; ugrt_shade_reflect_depth blends the levels front to back.  The levels of a frame
+// lie one behind the other: level j's arrays at (j-1) * W*H pixels (rays: (j-1) * W*H * 6 floats), indexed by
+// absolute pixel like every per-pixel array of the frame.
+#include "ugrt_dev.h"
+
+#define PX_THREADS 256
+
+// level j -> j+1: the same arithmetic as k_reflect_rays (d_reflect_ray), from the ray's own origin.  Most pixels of a
+// deep level are inactive: their lane reads the one active word and writes the empty ray.
+__global__ __launch_bounds__(PX_THREADS) void k_reflect_rays_next(const float *__restrict__ rays,
+								   const int *__restrict__ active,
+								   const float *__restrict__ hit_t,
+								   const int *__restrict__ hit_id,
+								   const int *__restrict__ mat_idx,
+								   const float *__restrict__ reflect, int mat_count,
+								   const float *__restrict__ verts, const int *__restrict__ tris,
+								   float eps, float *__restrict__ rays_next,
+								   int *__restrict__ active_next, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int p = p0 + i;
+	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+	int act = 0;
+	if (active[p]) {
+		int id = hit_id[p];
+		float t = hit_t[p];
+		if (t > 0 && id >= 0) {
+			int m = mat_idx[id];
+			if (m >= 0 && m < mat_count && reflect[m] > 0) {
+				float tri[9], o[3], d[3];
+				d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
+#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					o[k] = rays[p * 6 + k];
+					d[k] = rays[p * 6 + 3 + k];
+				}
+				d_reflect_ray(o, d, t, tri, eps, out);
+				act = 1;
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 6; k++)
+		rays_next[p * 6 + k] = out[k];
+	active_next[p] = act;
+}
+
+extern "C" int ugrt_reflect_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+				      const int *d_hit_id, const int *d_mat_idx, const float *d_reflect, int num_materials,
+				      const float *d_vertlist, const int *d_trilist, float eps, float *d_rays_next,
+				      int *d_active_next)
+{
+	if (!ctx || !d_rays || !d_active || !d_hit_t || !d_hit_id || !d_mat_idx || !d_reflect || !d_vertlist ||
+	    !d_trilist || !d_rays_next || !d_active_next)
+		return ugrt_fail(UGRT_EINVAL, "reflect_rays_next: null argument");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
+	hipLaunchKernelGGL(k_reflect_rays_next, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+			   ctx->stream, d_rays, d_active, d_hit_t, d_hit_id, d_mat_idx, d_reflect, num_materials,
+			   d_vertlist, d_trilist, eps, d_rays_next, d_active_next, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
+	UGRT_HIP(hipGetLastError());
+	ctx->dda_deeper_level = true; // the next ugrt_trace_dda walks without the split-walk history (ugrt_dda.hip)
+	return UGRT_OK;
+}
+
+struct DepthIn {
+	const float *reflect;
+	const float *verts;
+	const int *tris;
+	const float *rays;  // level j at (j-1) * level * 6
+	const int *active;  // level j at (j-1) * level
+	const float *hit_t;
+	const int *hit_id;
+	size_t level;       // W*H
+	int depth;
+};
+
+// the clamped Lambert colour of level j's hit (as k_shade_reflect shades the first bounce's hit); 0 on a miss or a
+// material out of range.  *kr: the hit material's reflect (read only where the level goes on, i.e. it is in range).
+__device__ __forceinline__ void d_level_color(const CamBlock &cam, const DepthIn &in, const int *__restrict__ mat_idx,
+					      const float *__restrict__ mat_list, int mat_count, size_t q, float *rc,
+					      float *kr)
+{
+	rc[0] = rc[1] = rc[2] = 0.0f;
+	int hid = in.hit_id[q];
+	if (hid < 0)
+		return;
+	int hm = mat_idx[hid];
+	if (hm < 0 || hm >= mat_count)
+		return;
+	float t9[9], nn[3], hp[3], hmat[6];
+	float ht = in.hit_t[q];
+	*kr = in.reflect[hm];
+	d_stage_triangle(in.verts, in.tris, (u32)hid, 0.0f, 0.0f, 0.0f, t9);
+	float *e1 = &t9[3], *e2 = &t9[6];
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		hp[k] = in.rays[q * 6 + k] + ht * in.rays[q * 6 + 3 + k];
+		hmat[k] = mat_list[hm * 6 + 3 + k];
+		hmat[3 + k] = mat_list[hm * 6 + 3 + k];
+	}
+	D_NORMALIZE(e1);
+	D_NORMALIZE(e2);
+	D_CROSS(nn, e1, e2);
+	D_NORMALIZE(nn);
+	d_lambert<false>(cam, hp, nn, rc, hmat, 1.0f);
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		rc[k] = rc[k] > 1.0f ? 1.0f : rc[k];
+}
+
+// acc = 0, w = 1; level j that goes on (active_{j+1}): acc += (w*(1-k_j))*L_j, w *= k_j; the first level that does not
+// (level `depth` at the latest): acc += w*L_j.  At depth 1 this is k_shade_reflect operation for operation.  A pixel
+// reads the levels it reaches and no others.
+__global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_depth(CamBlock cam, unsigned char *__restrict__ d_img,
+								     const float *__restrict__ dd_normal,
+								     const float *__restrict__ dd_t_value,
+								     const float *__restrict__ dd_dir,
+								     int *__restrict__ dd_intersect_id,
+								     const float *__restrict__ d_cam_pos,
+								     const int *__restrict__ mat_idx,
+								     const float *__restrict__ mat_list, int mat_count,
+								     DepthIn in, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	float acc[3] = { 0.0f, 0.0f, 0.0f };
+	int tri = dd_intersect_id[pixelID];
+	int idx = tri >= 0 ? mat_idx[tri] : tri;
+	dd_intersect_id[pixelID] = idx;
+	if (idx >= 0 && idx < mat_count) {
+		float color[3] = { 0.0f, 0.0f, 0.0f };
+		float t_value = dd_t_value[pixelID];
+		float material[6];
+#pragma unroll
+		for (int k = 0; k < 3; k++) {
+			material[k] = mat_list[idx * 6 + 3 + k];
+			material[3 + k] = mat_list[idx * 6 + 3 + k];
+		}
+		if (t_value > 0) {
+			float point[3], nrm[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				point[k] = d_cam_pos[k] + t_value * dd_dir[pixelID * 3 + k];
+				nrm[k] = dd_normal[pixelID * 3 + k];
+			}
+			d_lambert<false>(cam, point, nrm, color, material, 1.0f);
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				color[k] = color[k] > 1.0f ? 1.0f : color[k];
+		}
+		float w = 1.0f, kr = in.reflect[idx];
+		// level j (0 = the primary hit) goes on when active_{j+1}, which lies at j * level
+		for (int j = 0;; j++) {
+			const size_t q = (size_t)j * in.level + (size_t)pixelID;
+			if (j >= in.depth || !in.active[q]) {
+#pragma unroll
+				for (int k = 0; k < 3; k++)
+					acc[k] = acc[k] + w * color[k];
+				break;
+			}
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				acc[k] = acc[k] + (w * (1.0f - kr)) * color[k];
+			w = w * kr;
+			d_level_color(cam, in, mat_idx, mat_list, mat_count, q, color, &kr);
+		}
+	}
+	d_img[pixelID * 3 + 0] = d_to_u8(acc[0]);
+	d_img[pixelID * 3 + 1] = d_to_u8(acc[1]);
+	d_img[pixelID * 3 + 2] = d_to_u8(acc[2]);
+}
+
+extern "C" int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
+					const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+					const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+					const float *d_reflect, int num_materials, const float *d_vertlist,
+					const int *d_trilist, int depth, const float *d_rays, const int *d_active,
+					const float *d_hit_t, const int *d_hit_id)
+{
+	if (!ctx || !d_img || !d_normal || !d_t_value || !d_ray_dir || !d_intersect_id || !d_cam_position || !d_mat_idx ||
+	    !d_mat_list || !d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth: null argument");
+	if (depth < 1 || depth > UGRT_MAX_REFLECT_DEPTH)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth: depth %d outside 1..%d", depth, UGRT_MAX_REFLECT_DEPTH);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	DepthIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id,
+		       (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, depth };
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_reflect_depth, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
+			   d_mat_idx, d_mat_list, num_materials, in, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}

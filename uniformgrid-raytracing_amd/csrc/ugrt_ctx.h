@@ -166,6 +166,9 @@ struct ugrt_ctx {
 	DevBuf dsplit;                // bounce, split walks: work items, the groups' job history, merge state (ugrt_dda_walk.hip)
 	u32 dda_turn = 0;             // which of the two ray counters the last bounce used
 	u32 dsplit_rpw = 0, dsplit_turn = 0; // rays per wave the history was laid out for; launches since
+	// ugrt_reflect_rays_next was the last bounce call: the ugrt_trace_dda that follows traces a level >= 2 and walks
+	// without the split-walk history (it neither reads nor replaces the history of the level-1 launches: DESIGN.md 6.1)
+	bool dda_deeper_level = false;
 	DevBuf best;                  // u64 per pixel: (t bits << 32 | ref) for split cells
 	DevBuf rmap[2];               // ray sort ping-pong (2n u32 each)
 	DevBuf rstart, cbase; // ray runs per light cell (sort_rays)

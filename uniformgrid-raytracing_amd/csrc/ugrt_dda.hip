@@ -339,6 +339,9 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_rays || !d_active ||
 	    !d_hit_t || !d_hit_id)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: null argument");
+	// (a level >= 2 of a deeper reflection: set by ugrt_reflect_rays_next, used up here)
+	const bool deeper_level = ctx->dda_deeper_level;
+	ctx->dda_deeper_level = false;
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
@@ -385,10 +388,13 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	if (DDA_RPW > 64u)
 		DDA_RPW = 64u;
 	// split walks of the window kernel (ugrt_dda_walk.hip): list positions go into 28 bits of their merge key, and the
-	// context's own grid tells how many there are
+	// context's own grid tells how many there are.  Not for the levels >= 2 of a deeper reflection: the history is the
+	// last launch's long ray groups, and a frame of D levels would hand each level the cuts of the level before (level 1
+	// those of level D: 0.23 -> 0.39-0.99 ms on the bench workload, profiles/reflect_depth.json); without them level 1
+	// keeps the history of the previous frame's level 1
 	WalkSplit sp = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, nullptr };
 	WalkSplitHost sph = {};
-	if (kernel == 0 && !counting && ctx->opt[UGRT_OPT_DDA_SORT] != 1 &&
+	if (kernel == 0 && !counting && !deeper_level && ctx->opt[UGRT_OPT_DDA_SORT] != 1 &&
 	    (rc = ugrt_dda_split_state(ctx, DDA_RPW, d_span == (const unsigned *)G.span.p && d_offset == (const unsigned *)G.offset.p ? G.R : 0xFFFFFFFFu,
 				       &sp, &sph)))
 		return rc;

@@ -334,6 +334,33 @@ __device__ __forceinline__ void d_lambert(const CamBlock &cam, const float *poin
 	}
 }
 
+// the reflection bounce's next ray: hit point P = o + t*d on the staged triangle tri
+// ({., e1, e2}: d_stage_triangle), n = normalize(e1 x e2) turned against d, out = {P + eps*n, d - 2(d.n)n}.
+// o is the camera for the first bounce (k_reflect_rays) and the ray's own origin after that (k_reflect_rays_next).
+__device__ __forceinline__ void d_reflect_ray(const float *o, const float *d, float t, const float *tri, float eps,
+					      float *out)
+{
+	const float *e1 = &tri[3], *e2 = &tri[6];
+	float nn[3], P[3];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		P[k] = o[k] + t * d[k];
+	D_CROSS(nn, e1, e2);
+	D_NORMALIZE(nn);
+	float dn = D_DOT(d, nn);
+	if (dn > 0) {
+		nn[0] = -nn[0];
+		nn[1] = -nn[1];
+		nn[2] = -nn[2];
+		dn = -dn;
+	}
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		out[k] = P[k] + eps * nn[k];
+		out[3 + k] = d[k] - (2.0f * dn) * nn[k];
+	}
+}
+
 __device__ __forceinline__ unsigned char d_to_u8(float c)
 {
 	return (unsigned char)(ugrt_f2u(c * 255) & 0xFFu);

@@ -478,28 +478,12 @@ __global__ __launch_bounds__(PX_THREADS) void k_reflect_rays(const float *__rest
 	if (t > 0 && id >= 0) {
 		int m = mat_idx[id];
 		if (m >= 0 && m < mat_count && reflect[m] > 0) {
-			float tri[9], nn[3], d[3], P[3];
+			float tri[9], d[3];
 			d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
-			const float *e1 = &tri[3], *e2 = &tri[6];
 #pragma unroll
-			for (int k = 0; k < 3; k++) {
+			for (int k = 0; k < 3; k++)
 				d[k] = dir_list[p * 3 + k];
-				P[k] = cam_pos[k] + t * d[k];
-			}
-			D_CROSS(nn, e1, e2);
-			D_NORMALIZE(nn);
-			float dn = D_DOT(d, nn);
-			if (dn > 0) {
-				nn[0] = -nn[0];
-				nn[1] = -nn[1];
-				nn[2] = -nn[2];
-				dn = -dn;
-			}
-#pragma unroll
-			for (int k = 0; k < 3; k++) {
-				out[k] = P[k] + eps * nn[k];
-				out[3 + k] = d[k] - (2.0f * dn) * nn[k];
-			}
+			d_reflect_ray(cam_pos, d, t, tri, eps, out);
 			act = 1;
 		}
 	}
@@ -524,6 +508,7 @@ extern "C" int ugrt_reflect_rays(ugrt_ctx *ctx, const float *d_cam_position, con
 			   num_materials, d_vertlist, d_trilist, eps, d_rays, d_active, ctx->p0, ctx->npix);
 	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
 	UGRT_HIP(hipGetLastError());
+	ctx->dda_deeper_level = false; // level 1: its ugrt_trace_dda uses the split-walk history (ugrt_bounce.hip)
 	return UGRT_OK;
 }
 

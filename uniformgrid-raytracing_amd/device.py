@@ -228,6 +228,22 @@ class Context:
                                      _ptr(verts), _ptr(faces), _ptr(rays), _ptr(active), _ptr(hit_t),
                                      _ptr(hit_id)))
 
+    def reflect_rays_next(self, rays, active, hit_t, hit_id, mat_idx, reflect, num_materials, verts, faces, eps,
+                          rays_next, active_next):
+        """Level j's hits -> level j+1's reflected rays (j >= 1; level 1 is reflect_rays)."""
+        check(lib.ugrt_reflect_rays_next(self._h, _ptr(rays), _ptr(active), _ptr(hit_t), _ptr(hit_id), _ptr(mat_idx),
+                                         _ptr(reflect), num_materials, _ptr(verts), _ptr(faces), eps,
+                                         _ptr(rays_next), _ptr(active_next)))
+
+    def shade_reflect_depth(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, reflect, num_materials,
+                            verts, faces, depth, rays, active, hit_t, hit_id):
+        """shade_reflect over `depth` levels; rays / active / hit_t / hit_id hold levels 1..depth one behind the
+        other (level j at (j-1) * W*H pixels)."""
+        check(lib.ugrt_shade_reflect_depth(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids),
+                                           _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list), _ptr(reflect),
+                                           num_materials, _ptr(verts), _ptr(faces), int(depth), _ptr(rays),
+                                           _ptr(active), _ptr(hit_t), _ptr(hit_id)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

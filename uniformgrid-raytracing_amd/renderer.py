@@ -12,14 +12,59 @@ sequences one frame exactly in the reference's order:
 (getRayGridMapping + the host max loop, main.cu:172-187, only produce values that
 are overwritten with M_PI, so they are dropped: xM = yM = (float)M_PI.)
 With ``reflect=True`` the shading step becomes: secondary rays -> uniform grid
-build -> 3D-DDA -> shade_reflect (not in the reference).
+build -> 3D-DDA -> shade_reflect (not in the reference).  With
+``bounces=D > 1`` the reflected rays are followed D levels deep: (next rays ->
+3D-DDA) x (D-1) behind the first bounce, then shade_reflect_depth (DESIGN.md
+section 6).
 """
 import numpy as np
 
-from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM
+from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
+
+
+def check_bounces(bounces):
+    """1..MAX_REFLECT_DEPTH levels of reflection, or ValueError (before anything is enqueued)."""
+    if isinstance(bounces, bool) or not isinstance(bounces, (int, np.integer)) or not 1 <= bounces <= MAX_REFLECT_DEPTH:
+        raise ValueError("bounces must be an integer in 1..%d, not %r" % (MAX_REFLECT_DEPTH, bounces))
+    return int(bounces)
+
+
+def level_buffers(owner, ctx, N, depth):
+    """owner.rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)] on ctx's device, allocated
+    once for the deepest `depth` asked for; owner.rays / active / hit_t / hit_id become level 1's views."""
+    if owner.rays_levels is None or owner.rays_levels.shape[0] < depth:
+        t = ctx.torch
+        owner.rays_levels = ctx.empty((depth, 6 * N), t.float32)
+        owner.active_levels = ctx.empty((depth, N), t.int32)
+        owner.hit_t_levels = ctx.empty((depth, N), t.float32)
+        owner.hit_id_levels = ctx.empty((depth, N), t.int32)
+    owner.rays, owner.active = owner.rays_levels[0], owner.active_levels[0]
+    owner.hit_t, owner.hit_id = owner.hit_t_levels[0], owner.hit_id_levels[0]
+
+
+def trace_deeper_levels(c, owner, bounces, eps, uvalue, uspan, uoffset):
+    """Levels 2..bounces on context c's stream, behind level 1's trace_dda: no host wait (a level without an active
+    ray costs the DDA's prepare kernel and an empty persistent launch)."""
+    R, A, T, I = owner.rays_levels, owner.active_levels, owner.hit_t_levels, owner.hit_id_levels
+    for j in range(1, bounces):
+        c.reflect_rays_next(R[j - 1], A[j - 1], T[j - 1], I[j - 1], owner.d_matidx, owner.d_reflect, owner.num_materials,
+                            owner.d_verts, owner.d_faces, eps, R[j], A[j])
+        c.trace_dda(uvalue, uspan, uoffset, owner.d_verts, owner.d_faces, R[j], A[j], T[j], I[j])
+
+
+def shade_reflections(c, owner, bounces, cam_pos):
+    if bounces == 1:
+        c.shade_reflect(owner.image, owner.normal, owner.t, owner.dir, owner.intersect_id, cam_pos, owner.d_matidx,
+                        owner.d_matlist, owner.d_reflect, owner.num_materials, owner.d_verts, owner.d_faces, owner.rays,
+                        owner.active, owner.hit_t, owner.hit_id)
+    else:
+        c.shade_reflect_depth(owner.image, owner.normal, owner.t, owner.dir, owner.intersect_id, cam_pos,
+                              owner.d_matidx, owner.d_matlist, owner.d_reflect, owner.num_materials, owner.d_verts,
+                              owner.d_faces, bounces, owner.rays_levels, owner.active_levels, owner.hit_t_levels,
+                              owner.hit_id_levels)
 
 
 class FrameSetup:
@@ -136,6 +181,8 @@ class Renderer:
         self._cam_pos_done = [None, None]  # event behind the copy out of each staging buffer
         self._cam_pos_turn = 0
         self.rays = self.active = self.hit_t = self.hit_id = None
+        # bounces > 1: levels 1..D one behind the other (level_buffers)
+        self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
         self.reflect_eps = float(reflect_eps)
         self._num_chunks = 0
         self.orig = None
@@ -192,19 +239,25 @@ class Renderer:
             self._worker.join()
             self._worker = None
 
-    def _ensure_reflect_buffers(self):
-        if self.rays is None:
+    def _ensure_reflect_buffers(self, bounces=1):
+        if bounces > 1:
+            level_buffers(self, self.ctx, self.N, bounces)
+        elif self.rays is None:
             t = self.ctx.torch
             self.rays = self.ctx.empty(6 * self.N, t.float32)
             self.active = self.ctx.empty(self.N, t.int32)
             self.hit_t = self.ctx.empty(self.N, t.float32)
             self.hit_id = self.ctx.empty(self.N, t.int32)
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1):
+        """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  With bounces > 1,
+        rays_levels / active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t /
+        hit_id are level 1's views."""
+        bounces = check_bounces(bounces)
         if self.aux is not None and shade:
             if getattr(self, "_inline", False):
-                return self._display_two_streams_inline(setup, frame_cnt, shadows, reflect)
-            return self._display_overlapped(setup, frame_cnt, shadows, reflect)
+                return self._display_two_streams_inline(setup, frame_cnt, shadows, reflect, bounces)
+            return self._display_overlapped(setup, frame_cnt, shadows, reflect, bounces)
         ctx = self.ctx
         t = ctx.torch
         # updateLightPosition, per_frame_funcs.h:6
@@ -236,7 +289,7 @@ class Renderer:
         if not shade:
             return
         if reflect:
-            self._ensure_reflect_buffers()
+            self._ensure_reflect_buffers(bounces)
             ctx.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect,
                              self.num_materials, self.d_verts, self.d_faces, self.reflect_eps, self.rays,
                              self.active)
@@ -248,9 +301,8 @@ class Renderer:
             uvalue, uspan, uoffset, _ = ctx.grid_ptrs(GRID_UNIFORM)
             ctx.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t,
                           self.hit_id)
-            ctx.shade_reflect(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                              self.d_matidx, self.d_matlist, self.d_reflect, self.num_materials, self.d_verts,
-                              self.d_faces, self.rays, self.active, self.hit_t, self.hit_id)
+            trace_deeper_levels(ctx, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
+            shade_reflections(ctx, self, bounces, self.cam_pos)
         elif frame_cnt < 2:
             ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
                              self.d_matidx, self.d_matlist, self.num_materials)
@@ -260,7 +312,7 @@ class Renderer:
         if shadows:
             ctx.shade_add_shadows(self.image, self.is_shadowed)
 
-    def _display_overlapped(self, setup, frame_cnt, shadows, reflect):
+    def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces=1):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
         uniform grid, then - once the primary hits exist - secondary rays and the 3D-DDA.  Main stream: screen
         grid, primary rays, ray mapping and sort, shadow rays (after the light grid), shading (after the DDA).
@@ -271,7 +323,7 @@ class Renderer:
         main, side = self.main_stream, self.aux_stream
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         if reflect:
-            self._ensure_reflect_buffers()
+            self._ensure_reflect_buffers(bounces)
         ev_primary, ev_light_grid = t.cuda.Event(), t.cuda.Event()
         primary_recorded, light_grid_recorded = threading.Event(), threading.Event()
         # side stream: starts once the geometry of this frame is final on the main stream
@@ -302,6 +354,7 @@ class Renderer:
                 uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
                 aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active,
                               self.hit_t, self.hit_id)
+                trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
 
         self._jobs.put(side_job)
         failed = None
@@ -345,9 +398,7 @@ class Renderer:
         if err is not None:
             raise err
         if reflect:
-            ctx.shade_reflect(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                              self.d_matidx, self.d_matlist, self.d_reflect, self.num_materials, self.d_verts,
-                              self.d_faces, self.rays, self.active, self.hit_t, self.hit_id)
+            shade_reflections(ctx, self, bounces, self.cam_pos)
         elif frame_cnt < 2:
             ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
                              self.d_matidx, self.d_matlist, self.num_materials)
@@ -357,7 +408,7 @@ class Renderer:
         if shadows:
             ctx.shade_add_shadows(self.image, self.is_shadowed)
 
-    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect):
+    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect, bounces=1):
         """The two-stream frame from ONE host thread: with option async_build no call waits for the device, so the
         side stream's work is simply enqueued first (light grid, uniform grid), then the camera pass on the main
         stream, then what depends on the primary hits on either stream; events join them as in _display_overlapped."""
@@ -365,7 +416,7 @@ class Renderer:
         main, side = self.main_stream, self.aux_stream
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         if reflect:
-            self._ensure_reflect_buffers()
+            self._ensure_reflect_buffers(bounces)
         ev_primary, ev_light_grid = t.cuda.Event(), t.cuda.Event()
         side.wait_stream(main)  # the geometry of this frame is final on the main stream
         # the light grid and the uniform grid depend on the geometry only: their reference lists are sorted in shared
@@ -399,6 +450,7 @@ class Renderer:
             uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
             aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t,
                           self.hit_id)
+            trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
         ctx.upload_camera(lcam.camcoords)  # dd_camcoords is the light's from here on (main.cu:170)
         if shadows:
             ctx.map_rays_to_light(self.t, self.dir, self._d_map, self.cam_pos, PI_F, PI_F)
@@ -409,9 +461,7 @@ class Renderer:
                              self._d_map, self._prefix, self.cam_pos, self._num_chunks)
         main.wait_stream(side)
         if reflect:
-            ctx.shade_reflect(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                              self.d_matidx, self.d_matlist, self.d_reflect, self.num_materials, self.d_verts,
-                              self.d_faces, self.rays, self.active, self.hit_t, self.hit_id)
+            shade_reflections(ctx, self, bounces, self.cam_pos)
         elif frame_cnt < 2:
             ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
                              self.d_matidx, self.d_matlist, self.num_materials)
@@ -510,6 +560,9 @@ class BandedRenderer:
         for name in shared:
             setattr(self, name, getattr(r0, name))
         self.F, self.num_materials, self.bbmin, self.bbmax, self.aspect = r0.F, r0.num_materials, r0.bbmin, r0.bbmax, r0.aspect
+        self.N, self.reflect_eps = r0.N, r0.reflect_eps
+        # bounces > 1: the levels of the frame (level_buffers), shared by the bands like the level-1 arrays
+        self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
         for c in [self.aux] + [r.ctx for r in self.rs]:
             c.set_option("async_build", 1)
         # (as in the two-stream frame: the bounce's persistent waves leave room for the bands' short kernels)
@@ -518,8 +571,11 @@ class BandedRenderer:
     def contexts(self):
         return [self.aux] + [r.ctx for r in self.rs]
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=True):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1):
+        bounces = check_bounces(bounces)
         t, aux, main, side = self.torch, self.aux, self.main_stream, self.side_stream
+        if reflect and bounces > 1:
+            level_buffers(self, aux, self.N, bounces)
         r0 = self.rs[0]
         cam = make_camera(setup.camera, setup.fovy, self.aspect)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
@@ -553,6 +609,7 @@ class BandedRenderer:
                                  self.num_materials, self.d_verts, self.d_faces, r0.reflect_eps, self.rays, self.active)
                 uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
                 aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t, self.hit_id)
+                trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
                 ev_dda.record(side)
         for r, st in zip(self.rs, self.streams):
             with t.cuda.stream(st):
@@ -570,9 +627,7 @@ class BandedRenderer:
                 ctx = r.ctx
                 if reflect:
                     st.wait_event(ev_dda)
-                    ctx.shade_reflect(self.image, self.normal, self.t, self.dir, self.intersect_id, r.cam_pos, self.d_matidx,
-                                      self.d_matlist, self.d_reflect, self.num_materials, self.d_verts, self.d_faces, self.rays,
-                                      self.active, self.hit_t, self.hit_id)
+                    shade_reflections(ctx, self, bounces, r.cam_pos)
                 elif frame_cnt < 2:
                     ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, r.cam_pos, self.d_matidx,
                                      self.d_matlist, self.num_materials)

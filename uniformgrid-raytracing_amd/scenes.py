@@ -13,6 +13,9 @@ parse the same text, so the float32 vertex arrays are identical.
   crash()    -- "crashing"-class stand-in: the room + table + 20 chairs
                 (200 000 tris) + icosphere level 7 (327 680) + debris shards
                 = 1 000 000 tris; sphere + shards are the animated sub-range
+  mirrors()  -- a corridor between two facing mirror walls over a reflective
+                floor, boxes and an icosphere between them: reflections of
+                many levels (Renderer.display(..., bounces=D))
 """
 import os
 
@@ -301,3 +304,40 @@ def crash(outdir=None, scale=1.0):
                    dict(cameras={"ref": REF_CAMERA}, light_camera=REF_LIGHT_CAMERA,
                         shading_light=REF_SHADING_LIGHT, animated_offset=n_static_verts,
                         animated_size=mesh.nv - n_static_verts, static_faces=n_static_faces))
+
+
+MATERIALS_MIRRORS = [
+    # name, Ka, Kd, reflect
+    ("r0_floor", (0.2, 0.2, 0.2), (0.55, 0.55, 0.60), 0.5),
+    ("r1_mirror", (0.2, 0.2, 0.2), (0.70, 0.80, 0.90), 0.85),
+    ("r2_end_wall", (0.2, 0.2, 0.2), (0.80, 0.78, 0.70), 0.0),
+    ("r3_box", (0.2, 0.2, 0.2), (0.80, 0.25, 0.20), 0.0),
+    ("r4_glossy_box", (0.2, 0.2, 0.2), (0.20, 0.45, 0.80), 0.3),
+    ("r5_sphere", (0.2, 0.2, 0.2), (0.85, 0.75, 0.30), 0.6),
+]
+
+
+def mirrors(outdir=None, scale=1.0):
+    """Corridor [0,30]x[0,4]x[0,4]: the long walls y = 0 and y = 4 are mirrors (reflect 0.85) facing each other, the
+    floor reflects 0.5, the wall at x = 30 is matt; no ceiling and no wall at x = 0 (behind the camera: see add_room),
+    so rays that climb leave the grid.  Between the mirrors: four boxes and an icosphere.  The camera looks obliquely
+    down the corridor, so rays bounce from mirror to mirror many times.  ~40 000 triangles at scale 1."""
+    mesh = Mesh()
+    s = max(0.05, scale) ** 0.5
+    n = max(2, int(48 * s))
+    L, Wd, Hh = 30.0, 4.0, 4.0
+    mesh.add(*grid_quad((0, 0, 0), (L, 0, 0), (0, Wd, 0), 2 * n, n // 2 + 1), 0)   # floor
+    mesh.add(*grid_quad((0, 0, 0), (L, 0, 0), (0, 0, Hh), 2 * n, n // 2 + 1), 1)   # mirror y = 0
+    mesh.add(*grid_quad((0, Wd, 0), (L, 0, 0), (0, 0, Hh), 2 * n, n // 2 + 1), 1)  # mirror y = Wd
+    mesh.add(*grid_quad((L, 0, 0), (0, Wd, 0), (0, 0, Hh), n // 2 + 1, n // 2 + 1), 2)  # end wall
+    nb = max(1, int(6 * s))
+    for (x0, y0, sx, sy, h, m) in ((8.0, 0.8, 0.9, 0.9, 1.2, 3), (13.0, 2.4, 1.0, 0.8, 0.7, 4),
+                                   (19.0, 1.2, 0.7, 1.2, 1.6, 3), (24.0, 2.6, 0.9, 0.9, 1.0, 4)):
+        add_box(mesh, (x0, y0, 0.0), (x0 + sx, y0 + sy, h), nb, m, faces="xXyYZ")
+    level = 4 if scale >= 1.0 else max(1, int(round(4 + np.log(max(scale, 1e-3)) / np.log(4))))
+    sv, sf = icosphere(level)
+    mesh.add(sv * 0.8 + np.array([16.0, 1.6, 1.6]), sf, 5)
+    cams = {"ref": dict(eye=(1.0, 1.0, 1.7), look=(8.0, 3.6, 1.2), up=(0, 0, 1), near=0.1, far=100.0)}
+    light_cam = dict(eye=(15.0, 2.0, 9.0), look=(15.0, 2.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
+    return _finish(outdir, "mirrors%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_MIRRORS,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(15.0, 2.0, 3.5)))
