@@ -20,8 +20,9 @@
 // Image size: main.cu.h fixes SCREEN_WIDTH/HEIGHT at 1024 and NUM_BLOCKS_X/Y at 128 = the image's 8x8 tiles, which
 // are also the light grid's cells (mapSort_Effective_kernel uses one constant for both).  Here they are runtime
 // globals: W x H, NUM_BLOCKS = (W/8, H/8) for the perspective stages and the light grid's dimensions for the
-// spherical ones; NUM_SLABS is 1 except in the z-slab build ("slab" stage).  MAX_TRIANGLES and the 8x8 thread shape
-// stay as the reference has them.
+// spherical ones; NUM_SLABS is 1 unless the input names it ("slabs": the z-slab build, "slab" stage, its bounds, and
+// the traces over it, "primary" and "shadow"); every stage that sets it restores 1.  MAX_TRIANGLES and the 8x8
+// thread shape stay as the reference has them.
 //
 // Platform maths: see ref_shim.h.  A float -> int cast written as a cast in the kernel text, (int)((angle / max) *
 // (NUM_BLOCKS_X / 2)) in getEffective_x/y (grid_kernel.cu) and the colour stores of lambertian_shade, is x86's here
@@ -29,14 +30,16 @@
 // operands finite and in range (no vertex and no hit point on the light's position).
 //
 // Reference behaviours that read out of bounds are given defined values, as the oracle defines them:
-// the light grid's sentinel cell (Q11) gets span = offset = 0 (one extra entry), and the material index of a miss,
+// the light grid's sentinel cell (Q11) gets span = offset = 0 (NUM_SLABS extra entries: the kernel reads
+// blockcnt[C * NUM_SLABS + p] for every p), and the material index of a miss,
 // mat_idx[-2] (Q17, shader_kernel.cu:170), is -2 (two entries in front of the list).
 //
 // I/O: one binary input file (named arrays; "stage" names the stage) -> one binary output file in the same format
 // (tests/oracle_lib.py: write_ref_io / read_ref_io):
 //   "UGRK", u32 count, then per array: u32 name length, name, u8 type ('f' f32, 'i' i32, 'u' u32, 'b' u8),
 //   u64 element count, data.
-// Usage: ref_kernels in.bin out.bin
+// Usage: ref_kernels in.bin out.bin; ref_kernels --stamp prints the hash of this file and ref_shim.h it was built
+// from (oracle/Makefile), so that a binary left from other sources is recognised as such.
 #include <stdint.h>
 #include <ucontext.h>
 
@@ -483,13 +486,16 @@ static void stage_bounds()
 		acc += span[i];
 	}
 	out_int("used", used);
+	g_slabs = 1;
 }
 
 // rckernel_alpha (frustum_tracer.h:40-52).  Inputs: cc, tex, W, H, vals, span, offset, verts, faces; blocks
-// (optional).  Outputs: normal, t, dir, shadowed, id (untouched pixels keep 0 / the "init" value).
+// (optional); slabs (optional, NUM_SLABS: span/offset hold (W/8)*(H/8)*slabs cells).  Outputs: normal, t, dir,
+// shadowed, id (untouched pixels keep 0 / the "init" value).
 static void stage_primary()
 {
 	set_camcoords("cc");
+	g_slabs = g_in.count("slabs") ? in_int("slabs") : 1;
 	g_tex = in("tex").p<float>();
 	g_strict_texture = g_in.count("strict_texture") ? in_int("strict_texture") : 0;
 	g_W = in_int("W");
@@ -515,6 +521,7 @@ static void stage_primary()
 		       [&] { rckernel_alpha(vals, span, offs, normal, t, dir, sh, id, verts, faces); });
 	});
 	out_int("shm_bytes", shm);
+	g_slabs = 1;
 }
 
 // mapSort_Effective_kernel (per_frame_funcs.h:95-111).  The kernel's NUM_BLOCKS_X/Y are both the image's tiles and
@@ -562,10 +569,12 @@ static void stage_chunks()
 
 // mod_light_rckernel (per_frame_funcs.h:138-151), launched on (W/8) x (H/8) blocks with size = nchunks.  Inputs:
 // cc (light camera), vals, span, offset (light grid, C cells), verts, faces, t, dir, is_shadowed, d_map (sorted),
-// prefix, cam_pos, nchunks, W, H; blocks (optional).  Output: is_shadowed.
+// prefix, cam_pos, nchunks, W, H; blocks (optional); slabs (optional, NUM_SLABS: C * slabs cells).  Output:
+// is_shadowed.
 static void stage_shadow()
 {
 	set_camcoords("cc");
+	g_slabs = g_in.count("slabs") ? in_int("slabs") : 1;
 	g_W = in_int("W");
 	g_H = in_int("H");
 	g_nbx = g_W / NUM_THREADS_X;
@@ -574,8 +583,8 @@ static void stage_shadow()
 	int nchunks = in_int("nchunks");
 	Arr &sp = in("span"), &of = in("offset");
 	std::vector<unsigned> span(sp.p<unsigned>(), sp.p<unsigned>() + sp.n()), offs(of.p<unsigned>(), of.p<unsigned>() + of.n());
-	span.push_back(0); // Q11: the sentinel cell
-	offs.push_back(0);
+	span.resize(span.size() + g_slabs, 0); // Q11: the sentinel cell, blockcnt[C * NUM_SLABS + p] for p < NUM_SLABS
+	offs.resize(offs.size() + g_slabs, 0);
 	Arr &pf = in("prefix");
 	std::vector<unsigned> prefix(pf.p<unsigned>(), pf.p<unsigned>() + pf.n());
 	prefix.resize(std::max<size_t>(prefix.size(), (size_t)g_nbx * g_nby + 1), 0);
@@ -595,6 +604,7 @@ static void stage_shadow()
 		});
 	});
 	out_int("shm_bytes", shm);
+	g_slabs = 1;
 }
 
 // lambertian_shade then shadow_kernel (shader.h:56-84).  Inputs: cc (the matrices in dd_camcoords at that point: the
@@ -712,6 +722,10 @@ static void stage_animate()
 
 int main(int argc, char **argv)
 {
+	if (argc == 2 && !strcmp(argv[1], "--stamp")) {
+		puts(REF_DRIVER_STAMP);
+		return 0;
+	}
 	if (argc < 3) {
 		fprintf(stderr, "usage: %s in.bin out.bin\n", argv[0]);
 		return 2;

@@ -16,8 +16,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import oracle_lib as O  # noqa: E402
 import test_reference_kernels as T  # noqa: E402
 
-if not os.path.exists(O.REF_KERNELS):
-    sys.exit("oracle/_ref/ref_kernels is not built (make -C oracle ref)")
+if not O.ref_kernels_live():
+    sys.exit("oracle/_ref/ref_kernels is not built from the driver in the tree (make -C oracle ref)")
 for name in (sys.argv[1:] or sorted(T.CASES)):
     ins, outs = T.all_outputs(name, lambda st, i: T.run_reference(name, st, i))
     rec = T.record_of(name, {st: {k: outs[st][k] for k in T.STAGE_OUTPUTS[st]} for st in T.STAGE_OUTPUTS})

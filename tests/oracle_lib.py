@@ -422,6 +422,27 @@ def read_ref_io(blob):
     return out
 
 
+def ref_kernels_stamp():
+    """The stamp of the driver sources in the tree (oracle/Makefile: the hash of ref_kernels.cpp + ref_shim.h)."""
+    import hashlib
+
+    h = hashlib.sha256()
+    for name in ("ref_kernels.cpp", "ref_shim.h"):
+        with open(os.path.join(ORACLE_DIR, name), "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
+
+
+def ref_kernels_live():
+    """oracle/_ref/ref_kernels is built and was built from the driver sources in the tree.  A binary kept from
+    other sources (the Makefile keeps a prebuilt one where the reference checkout cannot be read) is not run: it
+    may not know the inputs the tests now pass."""
+    if not os.path.exists(REF_KERNELS):
+        return False
+    p = subprocess.run([REF_KERNELS, "--stamp"], capture_output=True, text=True)
+    return p.returncode == 0 and p.stdout.strip() == ref_kernels_stamp()
+
+
 def run_ref_kernels(stage, **arrays):
     """Runs one stage of the reference's kernels (oracle/_ref/ref_kernels) on the given inputs."""
     import tempfile

@@ -1237,43 +1237,124 @@ def test_overlapped_display_equals_sequential(ugrt, O, torch, helper_thread):
     r2.close()
 
 
+def _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, lg, slabs, all_chunks, rows=None, patch=None):
+    """One frame at NUM_SLABS = slabs against the oracle's: both slab builds (keys, values, span, offset, zMin/zMax,
+    projCoordZ), primary t (bits), normals, is_shadowed, the ids and the image; with rows, the band's pixels and
+    its perspective grid's size.  patch(ctx, r) may replace the context's tracers before the frame."""
+    flags = ugrt.FLAG_SHADOW_ALL_CHUNKS if all_chunks else 0
+    ctx = ugrt.Context(W, H, light_grid=lg, rows=rows, flags=flags, uniform_dims=(32, 32, 16), slabs=slabs)
+    r = ugrt.Renderer(ctx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
+    if patch is not None:
+        patch(ctx, r)
+    r.display(setup, frame_cnt=1, shadows=True)
+    ctx.synchronize()
+    want = O.frame(s, setup, W, H, rows=rows, light_grid=lg, all_chunks=all_chunks, slabs=slabs)
+    for which, key in ((ugrt.GRID_PERSPECTIVE, "grid"), (ugrt.GRID_SPHERICAL, "lgrid")):
+        value, keys, span, offset, gi = ctx.grid_arrays(which)
+        g = want[key]
+        assert gi.num_cells == len(g["span"]) and gi.total_refs == g["R"]
+        if rows is not None and which == ugrt.GRID_PERSPECTIVE:
+            continue  # a band's grid: its size is checked, the band's pixels below
+        np.testing.assert_array_equal(u32(keys), g["keys"])
+        np.testing.assert_array_equal(u32(value), g["vals"])
+        np.testing.assert_array_equal(u32(span), g["span"])
+        np.testing.assert_array_equal(u32(offset), g["offset"])
+        si = ctx.grid_slabs(which)
+        assert si.slabs == slabs
+        assert_bits_equal(np.array([si.z_min, si.z_max], np.float32), np.array(g["zrange"], np.float32), "zMin/zMax")
+        pz = ctx.wrap_u32(si.d_proj_coord_z, len(g["zmin"]))
+        np.testing.assert_array_equal(u32(pz), bits(g["zmin"]))
+    a, b = ctx.p0, ctx.p0 + ctx.npix
+    pr = want["primary"]
+    np.testing.assert_array_equal(r.t.cpu().numpy().view(np.uint32)[a:b], bits(pr["t"])[a:b])
+    assert_bits_equal(r.normal.cpu().numpy()[3 * a:3 * b], pr["normal"][3 * a:3 * b], "normal")
+    np.testing.assert_array_equal(r.is_shadowed.cpu().numpy()[a:b], want["is_shadowed"][a:b])
+    np.testing.assert_array_equal(r.intersect_id.cpu().numpy()[a:b], want["mat_ids"][a:b])
+    np.testing.assert_array_equal(r.image.cpu().numpy()[3 * a:3 * b], want["image"][3 * a:3 * b])
+    assert (pr["id"][a:b] >= 0).sum() > 0
+    r.close()
+    return want
+
+
 @pytest.mark.parametrize("name,cam,W,H,lg", [("hall", "ref", 256, 256, (64, 64)), ("crash", "ref", 256, 144, (128, 128)),
                                              ("cornell", "B", 256, 256, (32, 32))])
 @pytest.mark.parametrize("slabs", [2, 4])
 def test_z_slabs(ugrt, O, torch, name, cam, W, H, lg, slabs):
     """NUM_SLABS > 1 (main.cu.h:18): projCoordZ, the zMin/zMax loop (frustum_grid.h:221-241), SlabKernel
     (grid_kernel.cu:334), slab keys in both grids, the slab walk of rckernel_alpha (trace_kernel.cu:132-229) with
-    its state machine as written, the light kernel over all slabs of a cell (light_kernel.cu:105)."""
+    its state machine as written, the light kernel over all slabs of a cell (light_kernel.cu:105).  The stock
+    cameras put every hit in the last slab; test_z_slabs_depth_spread reaches the rest of the walk."""
     s = scene(ugrt, name)
     setup = setup_for(ugrt, s, cam)
     for all_chunks in (False, True):
-        flags = ugrt.FLAG_SHADOW_ALL_CHUNKS if all_chunks else 0
-        ctx = ugrt.Context(W, H, light_grid=lg, flags=flags, uniform_dims=(32, 32, 16), slabs=slabs)
-        r = ugrt.Renderer(ctx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
-        r.display(setup, frame_cnt=1, shadows=True)
-        ctx.synchronize()
-        want = O.frame(s, setup, W, H, light_grid=lg, all_chunks=all_chunks, slabs=slabs)
-        for which, key in ((ugrt.GRID_PERSPECTIVE, "grid"), (ugrt.GRID_SPHERICAL, "lgrid")):
-            # the renderer rebuilt the perspective grid last with the light camera?  no: one build each per frame
-            value, keys, span, offset, gi = ctx.grid_arrays(which)
-            g = want[key]
-            assert gi.num_cells == len(g["span"]) and gi.total_refs == g["R"]
-            np.testing.assert_array_equal(u32(keys), g["keys"])
-            np.testing.assert_array_equal(u32(value), g["vals"])
-            np.testing.assert_array_equal(u32(span), g["span"])
-            np.testing.assert_array_equal(u32(offset), g["offset"])
-            si = ctx.grid_slabs(which)
-            assert si.slabs == slabs
-            assert_bits_equal(np.array([si.z_min, si.z_max], np.float32), np.array(g["zrange"], np.float32), "zMin/zMax")
-            pz = ctx.wrap_u32(si.d_proj_coord_z, len(g["zmin"]))
-            np.testing.assert_array_equal(u32(pz), bits(g["zmin"]))
-        pr = want["primary"]
-        np.testing.assert_array_equal(r.t.cpu().numpy().view(np.uint32), bits(pr["t"]))
-        assert_bits_equal(r.normal.cpu().numpy(), pr["normal"], "normal")
-        np.testing.assert_array_equal(r.is_shadowed.cpu().numpy(), want["is_shadowed"])
-        np.testing.assert_array_equal(r.intersect_id.cpu().numpy(), want["mat_ids"])
-        np.testing.assert_array_equal(r.image.cpu().numpy(), want["image"])
-        assert (pr["id"] >= 0).sum() > 0
+        _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, lg, slabs, all_chunks)
+
+
+def depth_spread(ugrt, base):
+    """(scene, setup, W, H) of a depth-spread case of tests/test_reference_kernels.py: hits in every z-slab."""
+    import test_reference_kernels as RK
+
+    build, W, H = RK.DEPTH_SPREAD[base]
+    s, setup = build(ugrt)
+    return s, setup, W, H
+
+
+DEPTH_SPREAD = ["cornellBz_128", "soup1z_128x96"]
+
+
+@pytest.mark.parametrize("base", DEPTH_SPREAD)
+@pytest.mark.parametrize("slabs", [2, 3, 4, 8])
+def test_z_slabs_depth_spread(ugrt, O, torch, base, slabs):
+    """The slab walk where it matters: cameras whose hits lie in every slab, so that rays are accepted early, an
+    accepted ray is reset to "no hit" when its tile goes on (trace_kernel.cu:59-62) and tiles leave the walk before
+    their last slab (the beam-done exit, :217-228); both chunk modes of the shadow pass over the slab union."""
+    s, setup, W, H = depth_spread(ugrt, base)
+    for all_chunks in (False, True):
+        want = _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, (32, 32), slabs, all_chunks)
+    one = O.frame(s, setup, W, H, light_grid=(32, 32))
+    lost = (one["primary"]["id"] >= 0) & (want["primary"]["id"] < 0)
+    assert lost.sum() > 0, (base, slabs)  # the reset path ran
+
+
+def test_z_slabs_at_the_abi_limit(ugrt, O, torch):
+    """slabs = 64, the most the C-ABI accepts: 64 slab lists per cell in both grids.  Random soup 2 (the camera
+    inside the cloud): its surviving hits are accepted in slabs 54..59, so tiles leave the walk in its middle, and
+    most hits of NUM_SLABS = 1 are lost.  (At 64 slabs the depth-spread Cornell camera keeps no hit at all.)"""
+    import test_reference_kernels as RK
+
+    build, W, H = RK.CASES["soup2_160x128"]
+    s, setup = build(ugrt)
+    for all_chunks in (False, True):
+        _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, (16, 16), 64, all_chunks)
+
+
+def test_z_slabs_band_split(ugrt, O, torch):
+    """Image-tile bands (rows=) with slabs: k_trace_primary_slabs from a first tile row other than 0, on a band's
+    slab build; each band equals the oracle's band frame."""
+    s, setup, W, H = depth_spread(ugrt, "cornellBz_128")
+    nby = H // 8
+    for rows in ((0, 7), (7, nby)):
+        _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, (32, 32), 3, True, rows=rows)
+
+
+def test_z_slabs_gather_path_without_records(ugrt, O, torch):
+    """k_trace_primary_slabs<false> and the shadow pass without the triangle records (the caller's vertex/face
+    arrays are not the ones the grids were built from, as in test_gather_path_without_records), at slabs."""
+    s, setup, W, H = depth_spread(ugrt, "soup1z_128x96")
+
+    def patch(ctx, r):
+        verts2, faces2 = r.d_verts.clone(), r.d_faces.clone()
+        for name in ("trace_primary", "trace_shadow"):
+            orig = getattr(ctx, name)
+
+            def patched(*a, _orig=orig):
+                a = [verts2 if x is r.d_verts else faces2 if x is r.d_faces else x for x in a]
+                return _orig(*a)
+
+            setattr(ctx, name, patched)
+
+    for slabs in (3, 4):
+        _slab_frame_equals_oracle(ugrt, O, s, setup, W, H, (32, 32), slabs, False, patch=patch)
 
 
 @pytest.mark.parametrize("name,nparts", [("hall", 2), ("crash", 3)])

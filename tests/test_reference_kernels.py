@@ -5,6 +5,12 @@ oracle/ref_shim.h) runs each stage on the oracle's inputs for that stage; its ou
 Integers equal, floats bit-equal, RGB8 equal.  The scans, sorts and compactions between the stages (CUDPP) are
 integer primitives pinned by definition, so every stage starts from the oracle's inputs.
 
+The z-slab frame (NUM_SLABS = S > 1) is pinned the same way: the builds (SlabKernel and the fills), their bounds and
+the traces over them (rckernel_alpha and mod_light_rckernel at NUM_SLABS = S), fed the oracle's slab frame.  The
+stock cameras put every primary hit in the last slab (near << far), where no accepted hit is ever lost; the
+depth-spread cases move near/far in so that hits fall in every slab and reach the early accept, the reset of an
+accepted ray when its tile goes on, and the beam-done exit (test_depth_spread_cases_reach_every_slab).
+
 tests/golden/ref_kernels_<case>.npz (tests/golden/make_ref_kernels.py) records the reference kernels' outputs per
 stage with the SHA-256 of the stage's inputs, so the pin holds where the reference checkout is absent:
 * the CPU tests here compare the oracle with the record always, and the live binary with it where it is built;
@@ -24,7 +30,7 @@ import oracle_lib as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
-LIVE = os.path.exists(O.REF_KERNELS)
+LIVE = O.ref_kernels_live()  # built, and from the driver sources in the tree
 WHOLE_BYTES = 16384  # arrays up to this size are recorded whole; larger ones by SHA-256 and a seeded sample
 SAMPLE = 256
 
@@ -110,6 +116,15 @@ def _soup(u, seed, ntri):
     return s, u.FrameSetup(cam, light, tuple(rng.uniform(100.0, 450.0, 3)))
 
 
+def _near_far(build, near, far):
+    """A case's scene and setup with the camera's near/far planes moved: the GL depth of its hits spreads over
+    [0, 1) and so over every z-slab."""
+    def b(u):
+        s, setup = build(u)
+        return s, u.FrameSetup(dict(setup.camera, near=near, far=far), setup.light_camera, setup.shading_light)
+    return b
+
+
 def _named(u, name, cam):
     s = {"cornell": lambda: u.scenes.cornell(), "hall": lambda: u.scenes.hall(scale=0.1),
          "crash": lambda: u.scenes.crash(scale=0.02)}[name]()
@@ -131,10 +146,25 @@ CASES = {
     # the reference's own constants: 1024 x 1024, NUM_BLOCKS 128, a 128 x 128 light grid
     "hall_1024": (lambda u: _named(u, "hall", "ref"), 1024, 1024),
 }
+# depth-spread scenes (hits in every z-slab), each a case at every slab count of DEPTH_SPREAD_SLABS
+DEPTH_SPREAD = {
+    "cornellBz_128": (_near_far(lambda u: _named(u, "cornell", "B"), 600.0, 1600.0), 128, 128),
+    "soup1z_128x96": (_near_far(lambda u: _soup(u, 1, 600), 10.0, 300.0), 128, 96),
+}
+DEPTH_SPREAD_SLABS = (2, 3, 4)
+CASE_SLABS = {}
+for _base, _case in DEPTH_SPREAD.items():
+    for _S in DEPTH_SPREAD_SLABS:
+        CASES["%s_s%d" % (_base, _S)] = _case
+        CASE_SLABS["%s_s%d" % (_base, _S)] = _S
 # cases whose barrier kernels run on a seeded sample of the blocks (each block is independent)
 SAMPLED_BLOCKS = {"hall_1024": 2000}
-SLABS = 4  # the z-slab builds (SlabKernel + the fills with NUM_SLABS = 4)
+SLABS = 4  # the z-slab frame of every other case (SlabKernel, the fills and the traces with NUM_SLABS = 4)
 _FRAMES = {}
+
+
+def slabs_of(name):
+    return CASE_SLABS.get(name, SLABS)
 
 
 def case_frame(name):
@@ -151,9 +181,18 @@ def slab_grids(name):
     s, setup, W, H, r = case_frame(name)
     if "slab_grids" not in r:
         faces, verts = s["faces"], s["verts"]
-        r["slab_grids"] = (O.grid_perspective(r["cam"].cc, faces, verts, W // 8, H // 8, slabs=SLABS),
-                           O.grid_spherical(r["lcam"].cc, faces, verts, W // 8, H // 8, slabs=SLABS))
+        S = slabs_of(name)
+        r["slab_grids"] = (O.grid_perspective(r["cam"].cc, faces, verts, W // 8, H // 8, slabs=S),
+                           O.grid_spherical(r["lcam"].cc, faces, verts, W // 8, H // 8, slabs=S))
     return r["slab_grids"]
+
+
+def slab_frame(name):
+    """The oracle's frame of a case at NUM_SLABS = slabs_of(name), strict shadow chunks, cached with the frame."""
+    s, setup, W, H, r = case_frame(name)
+    if "slab_frame" not in r:
+        r["slab_frame"] = O.frame(s, setup, W, H, light_grid=(W // 8, H // 8), slabs=slabs_of(name))
+    return r["slab_frame"]
 
 
 def sampled_blocks(name):
@@ -169,18 +208,18 @@ def restrict(name, stage, ins, out):
     """In a sampled case, the outputs of the barrier kernels at the pixels their sampled blocks own: the 8x8 tiles
     (rckernel_alpha) and the rays of the chunks (mod_light_rckernel: block b traces chunk b - 1, Q13)."""
     blocks = sampled_blocks(name)
-    if blocks is None or stage not in ("primary", "shadow"):
+    if blocks is None or stage not in PRIMARY_STAGES + SHADOW_STAGES:
         return out
     W, H = CASES[name][1], CASES[name][2]
     nbx = W // 8
-    if stage == "primary":
+    if stage in PRIMARY_STAGES:
         bx, by = (blocks % nbx).astype(np.int64), (blocks // nbx).astype(np.int64)
         t = np.arange(64)
         px = ((by[:, None] * 8 + t // 8) * W + bx[:, None] * 8 + t % 8).reshape(-1)
         px3 = (3 * px[:, None] + np.arange(3)).reshape(-1)
         return dict(out, **{k: np.ascontiguousarray(out[k])[px3 if k in ("normal", "dir") else px]
                             for k in STAGE_OUTPUTS["primary"]})
-    a = ins["shadow"]
+    a = ins[stage]
     pre, n = a["prefix"].astype(np.int64), int(a["nchunks"])
     rays = []
     for b in blocks.astype(np.int64):
@@ -206,6 +245,9 @@ def stage_inputs(name):
     cam_pos = cam.worldori[:3].copy()
     n = r["nchunks"]
     gs, lgs = slab_grids(name)
+    S = slabs_of(name)
+    rs = slab_frame(name)
+    prs, ns = rs["primary"], rs["nchunks"]
     blocks = {} if sampled_blocks(name) is None else dict(blocks=sampled_blocks(name))
     shade = dict(cc=lcam.cc, light_pos=np.asarray(setup.shading_light, np.float32), normal=pr["normal"], t=pr["t"],
                  dir=pr["dir"], id=pr["id"], cam_pos=cam_pos, mat_idx=np.asarray(s["matidx"], np.int32),
@@ -226,11 +268,18 @@ def stage_inputs(name):
         "spot": shade,
         "perlin": dict(id=pr["id"], W=W, H=H),
         "pslab": dict(cc=cam.cc, faces=faces, verts=verts, nbx=nbx, nby=nby, scan=gs["scan"], zmin=gs["zmin"],
-                      zMin=gs["zrange"][0], zMax=gs["zrange"][1], slabs=SLABS, spherical=0),
+                      zMin=gs["zrange"][0], zMax=gs["zrange"][1], slabs=S, spherical=0),
         "lslab": dict(cc=lcam.cc, faces=faces, verts=verts, nbx=nbx, nby=nby, scan=lgs["scan"], zmin=lgs["zmin"],
-                      zMin=lgs["zrange"][0], zMax=lgs["zrange"][1], slabs=SLABS, spherical=1, xM=O.PI_F, yM=O.PI_F),
-        "pslab_bounds": dict(keys=gs["keys"], nbx=nbx, nby=nby, slabs=SLABS),
-        "lslab_bounds": dict(keys=lgs["keys"], nbx=nbx, nby=nby, slabs=SLABS),
+                      zMin=lgs["zrange"][0], zMax=lgs["zrange"][1], slabs=S, spherical=1, xM=O.PI_F, yM=O.PI_F),
+        "pslab_bounds": dict(keys=gs["keys"], nbx=nbx, nby=nby, slabs=S),
+        "lslab_bounds": dict(keys=lgs["keys"], nbx=nbx, nby=nby, slabs=S),
+        # the traces over the slab builds, on the slab frame's own primary hits, ray map and chunks
+        "pslab_primary": dict(cc=cam.cc, tex=cam.tex, W=W, H=H, vals=rs["grid"]["vals"], span=rs["grid"]["span"],
+                              offset=rs["grid"]["offset"], verts=verts, faces=faces, slabs=S, **blocks),
+        "lslab_shadow": dict(cc=lcam.cc, vals=rs["lgrid"]["vals"], span=rs["lgrid"]["span"],
+                             offset=rs["lgrid"]["offset"], verts=verts, faces=faces, t=prs["t"], dir=prs["dir"],
+                             is_shadowed=prs["shadowed"], d_map=rs["map"], prefix=rs["prefix"][:ns], cam_pos=cam_pos,
+                             nchunks=ns, W=W, H=H, slabs=S, **blocks),
     }
 
 
@@ -241,8 +290,10 @@ def oracle_outputs(name):
     k, v = O.fill_2d(g["rng"], g["scan"], H // 8)
     lk, lv = O.fill_2d(lg["rng"], lg["scan"], H // 8)
     gs, lgs = slab_grids(name)
-    sk, sv = O.fill_slabs(gs["rng"], gs["scan"], gs["zlist"], H // 8, SLABS)
-    lsk, lsv = O.fill_slabs(lgs["rng"], lgs["scan"], lgs["zlist"], H // 8, SLABS)
+    sk, sv = O.fill_slabs(gs["rng"], gs["scan"], gs["zlist"], H // 8, slabs_of(name))
+    lsk, lsv = O.fill_slabs(lgs["rng"], lgs["scan"], lgs["zlist"], H // 8, slabs_of(name))
+    rs = slab_frame(name)
+    prs = rs["primary"]
     N = W * H
     spot_img, spot_ids, dump = np.zeros(3 * N, np.uint8), pr["id"].copy(), np.zeros(2 * N, np.float32)
     O.shade(r["lcam"].cc, setup.shading_light, spot_img, pr["normal"], pr["t"], pr["dir"], spot_ids,
@@ -265,10 +316,15 @@ def oracle_outputs(name):
         "lslab": dict(zlist=lgs["zlist"], keys=lsk, vals=lsv),
         "pslab_bounds": dict(span=gs["span"], offset=gs["offset"], used=np.int32([gs["used"]])),
         "lslab_bounds": dict(span=lgs["span"], offset=lgs["offset"], used=np.int32([lgs["used"]])),
+        "pslab_primary": dict(id=prs["id"], t=prs["t"], normal=prs["normal"], dir=prs["dir"],
+                              shadowed=prs["shadowed"]),
+        "lslab_shadow": dict(is_shadowed=rs["is_shadowed"]),
     }
 
 
-REPORTED = ("sph", "lslab", "map", "primary", "shadow")
+PRIMARY_STAGES = ("primary", "pslab_primary")  # rckernel_alpha at NUM_SLABS = 1 and = slabs_of(case)
+SHADOW_STAGES = ("shadow", "lslab_shadow")  # mod_light_rckernel, likewise
+REPORTED = ("sph", "lslab", "map", "primary", "shadow", "pslab_primary", "lslab_shadow")
 REPORTS = ("acos_nan", "overrun_blocks", "overrun_bytes", "overrun_min_bytes", "divergent_barriers",
            "tex_coord_mismatch", "schedule_differs", "used", "nchunks")
 STAGE_OUTPUTS = {st: tuple(v) for st, v in dict(
@@ -278,13 +334,14 @@ STAGE_OUTPUTS = {st: tuple(v) for st, v in dict(
     chunks=("prefix", "nchunks"), shadow=("is_shadowed",), shade=("image_unshadowed", "mat_ids", "image"),
     spot=("image", "mat_ids", "dump"), perlin=("image",), pslab=("zlist", "keys", "vals"),
     lslab=("zlist", "keys", "vals"), pslab_bounds=("span", "offset", "used"), lslab_bounds=("span", "offset", "used"),
-    pslab_sorted=("keys", "vals"), lslab_sorted=("keys", "vals")).items()}
+    pslab_sorted=("keys", "vals"), lslab_sorted=("keys", "vals"), pslab_primary=("id", "t", "normal", "dir", "shadowed"),
+    lslab_shadow=("is_shadowed",)).items()}
 
 
 DERIVED = {"persp_sorted": "persp", "sph_sorted": "sph", "map_sorted": "map", "pslab_sorted": "pslab",
            "lslab_sorted": "lslab"}
 DRIVER_STAGE = {"lbounds": "bounds", "pslab_bounds": "bounds", "lslab_bounds": "bounds", "pslab": "slab",
-                "lslab": "slab"}
+                "lslab": "slab", "pslab_primary": "primary", "lslab_shadow": "shadow"}
 
 
 def sorted_outputs(stage, out):
@@ -395,6 +452,11 @@ def test_oracle_equals_reference_kernels(name):
     np.testing.assert_array_equal(want["persp_sorted"]["keys"], r["grid"]["keys"])
     np.testing.assert_array_equal(want["sph_sorted"]["vals"], r["lgrid"]["vals"])
     np.testing.assert_array_equal(want["map_sorted"]["d_map"], r["map"])
+    # the slab traces run on the pinned slab builds
+    rs = slab_frame(name)
+    for built, traced in zip(slab_grids(name), (rs["grid"], rs["lgrid"])):
+        for k in ("vals", "span", "offset"):
+            np.testing.assert_array_equal(built[k], traced[k])
     if LIVE:
         _, got = all_outputs(name, lambda st, i: run_reference(name, st, i))
         for stage in STAGE_OUTPUTS:
@@ -407,7 +469,8 @@ def test_oracle_equals_reference_kernels(name):
 
 def test_reports_of_the_reference_run():
     """What running the reference's kernels showed, as recorded: no barrier-interval race (forward and reverse
-    thread order agree) in rckernel_alpha or mod_light_rckernel, every thread reaches every barrier, the ray
+    thread order agree) in rckernel_alpha or mod_light_rckernel, at NUM_SLABS = 1 and over the slab builds, every
+    thread reaches every barrier (also where a tile's slab walk ends early, the beam-done exit), the ray
     coordinate of every pixel is the one the texture fetch is defined on, rckernel_alpha stays inside its shared
     memory, and mod_light_rckernel writes past its launched shared memory (light_kernel.cu:66: rayDoneMap lies
     behind the 7 + 576 words the launch sizes, per_frame_funcs.h:139-141) in every block that runs, by 256 bytes
@@ -417,11 +480,11 @@ def test_reports_of_the_reference_run():
         for stage in ("sph", "lslab", "map"):
             # no NaN angle reaches getEffective_x/y's integer cast (x86: INT_MIN, CUDA: 0): inputs stay in range
             assert int(rec["%s/report/acos_nan" % stage]) == 0, (name, stage)
-        for stage in ("primary", "shadow"):
+        for stage in PRIMARY_STAGES + SHADOW_STAGES:
             r = {k: int(rec["%s/report/%s" % (stage, k)]) for k in REPORTS if "%s/report/%s" % (stage, k) in rec}
             assert r["schedule_differs"] == 0 and r["divergent_barriers"] == 0, (name, stage, r)
             assert r["tex_coord_mismatch"] == 0, (name, stage, r)
-            if stage == "primary":
+            if stage in PRIMARY_STAGES:
                 assert r["overrun_blocks"] == 0, (name, r)
             else:
                 W, H = CASES[name][1], CASES[name][2]
@@ -430,6 +493,40 @@ def test_reports_of_the_reference_run():
                 # rayDoneMap[i * 64 + t] for i < count / 64 + 1: 64 words past the launch when the block's chunk has
                 # fewer than 64 rays, 128 words when it has 64
                 assert r["overrun_min_bytes"] in (256, 512) and r["overrun_bytes"] in (256, 512), (name, r)
+
+
+def ndc_slab(cc, t, dirs, slabs):
+    """floor(ndc_z * slabs) of the hit at t along each ray, isWithin's slab index (trace_kernel.cu:56-82)."""
+    t, d = np.asarray(t, np.float32), np.asarray(dirs, np.float32).reshape(-1, 3)
+    p = cc[0:3][None, :] + t[:, None] * d
+    m = cc[48:64]
+    z = ((m[2] * p[:, 0] + m[6] * p[:, 1]) + m[10] * p[:, 2]) + m[14]
+    w = ((m[3] * p[:, 0] + m[7] * p[:, 1]) + m[11] * p[:, 2]) + m[15]
+    return np.floor((z / w) * np.float32(slabs)).astype(np.int64)
+
+
+def slab_census(name):
+    """(hits per slab, of them accepted at slabs_of(name), hits lost): every pixel that hits at NUM_SLABS = 1 is
+    classified by the ndc-z slab of that hit; accepted = it hits in the slab frame too, lost = it misses there."""
+    S = slabs_of(name)
+    r, rs = case_frame(name)[4], slab_frame(name)
+    pr = r["primary"]
+    hit, hit_s = pr["id"] >= 0, rs["primary"]["id"] >= 0
+    k = ndc_slab(r["cam"].cc, pr["t"], pr["dir"], S)
+    return ([int((hit & (k == j)).sum()) for j in range(S)], [int((hit & hit_s & (k == j)).sum()) for j in range(S)],
+            int((hit & ~hit_s).sum()))
+
+
+@pytest.mark.parametrize("name", sorted(CASE_SLABS))
+def test_depth_spread_cases_reach_every_slab(name):
+    """The depth-spread cases are not vacuous, with no reference binary needed: the oracle accepts hits in the
+    first slab and in the last (the early accept ends a tile's walk before its last slab, or an accepted ray is
+    reset because its tile goes on), and loses hits that NUM_SLABS = 1 keeps (isWithin's reset of an accepted ray).
+    The stock cameras fail this: all their hits lie in the last slab."""
+    per_slab, accepted, lost = slab_census(name)
+    S = slabs_of(name)
+    assert accepted[0] > 0 and accepted[S - 1] > 0, (name, per_slab, accepted)
+    assert lost > 0, (name, per_slab, accepted, lost)
 
 
 ANIMATE_ROTS = (1.81, 1.81 + 0.05 * 3, -2.5)
@@ -471,7 +568,7 @@ def test_product_equals_reference_record(ugrt, name):
     """libugrt.so (strict shadow chunks) against the reference kernels' recorded outputs, no oracle in between:
     the three grids (perspective, spherical, and both again as z-slab builds) value/span/offset, primary
     id/t/normal/dir, the sorted d_map and chunk starts, is_shadowed, the material ids and the RGB8 image of the
-    Lambert, spotlight and Perlin shaders.  A sampled case checks the barrier kernels' outputs at the pixels its
+    Lambert, spotlight and Perlin shaders; in the z-slab frame, primary id/t/normal/dir and is_shadowed too.  A sampled case checks the barrier kernels' outputs at the pixels its
     sampled blocks own."""
     import torch
 
@@ -535,9 +632,24 @@ def test_product_equals_reference_record(ugrt, name):
     ctx.synchronize()
     assert_matches_record(rec, name, "spot", dict(image=img.cpu().numpy(), mat_ids=r.intersect_id.cpu().numpy(),
                                                   dump=dump.cpu().numpy()), "product")
-    # the z-slab builds of both grids
-    sctx = ugrt.Context(W, H, light_grid=(W // 8, H // 8), flags=0, slabs=SLABS)
+    # the z-slab frame: both builds, then the traces over them (k_trace_primary_slabs, the shadow pass over the slab
+    # union), on the product's own slab grids, ray map and chunks
+    sctx = ugrt.Context(W, H, light_grid=(W // 8, H // 8), flags=0, slabs=slabs_of(name))
     sr = ugrt.Renderer(sctx, s["verts"], s["faces"], s["matidx"], s["mat_list"], s["reflect"])
     sr.display(setup, frame_cnt=1, shadows=True)
     sctx.synchronize()
     grids(sctx, (("pslab", "pslab_bounds"), ("lslab", "lslab_bounds")))
+    sins = {"lslab_shadow": dict(d_map=u32(sr.d_map), prefix=u32(sr.prefix)[:sr.num_chunks], nchunks=sr.num_chunks)}
+    assert_matches_record(rec, name, "lslab_shadow",
+                          restrict(name, "lslab_shadow", sins, dict(is_shadowed=sr.is_shadowed.cpu().numpy())),
+                          "product")
+    prim = dict(t=sr.t.cpu().numpy(), normal=sr.normal.cpu().numpy(), dir=sr.dir.cpu().numpy())
+    sctx.upload_camera(c.camcoords)
+    value, key, span, offset, gi = sctx.grid_arrays(ugrt.GRID_PERSPECTIVE)
+    sctx.trace_primary(value, span, offset, sr.normal, sr.t, sr.dir, sr.is_shadowed, sr.intersect_id, sr.d_verts,
+                       sr.d_faces)
+    sctx.synchronize()
+    prim.update(id=sr.intersect_id.cpu().numpy(), shadowed=sr.is_shadowed.cpu().numpy())
+    for k in ("t", "normal", "dir"):
+        assert array_sha(prim[k]) == array_sha(getattr(sr, k).cpu().numpy()), "%s: the second slab trace differs" % k
+    assert_matches_record(rec, name, "pslab_primary", restrict(name, "pslab_primary", sins, prim), "product")
