@@ -16,7 +16,13 @@ build -> 3D-DDA -> shade_reflect (not in the reference).  With
 ``bounces=D > 1`` the reflected rays are followed D levels deep: (next rays ->
 3D-DDA) x (D-1) behind the first bounce, then shade_reflect_depth (DESIGN.md
 section 6).
+
+Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
+streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
+and in the events that join the streams.
 """
+import contextlib
+
 import numpy as np
 
 from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_REFLECT_DEPTH
@@ -32,39 +38,108 @@ def check_bounces(bounces):
     return int(bounces)
 
 
-def level_buffers(owner, ctx, N, depth):
-    """owner.rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)] on ctx's device, allocated
-    once for the deepest `depth` asked for; owner.rays / active / hit_t / hit_id become level 1's views."""
-    if owner.rays_levels is None or owner.rays_levels.shape[0] < depth:
-        t = ctx.torch
-        owner.rays_levels = ctx.empty((depth, 6 * N), t.float32)
-        owner.active_levels = ctx.empty((depth, N), t.int32)
-        owner.hit_t_levels = ctx.empty((depth, N), t.float32)
-        owner.hit_id_levels = ctx.empty((depth, N), t.int32)
-    owner.rays, owner.active = owner.rays_levels[0], owner.active_levels[0]
-    owner.hit_t, owner.hit_id = owner.hit_t_levels[0], owner.hit_id_levels[0]
+# -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
+# BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
 
-def trace_deeper_levels(c, owner, bounces, eps, uvalue, uspan, uoffset):
-    """Levels 2..bounces on context c's stream, behind level 1's trace_dda: no host wait (a level without an active
-    ray costs the DDA's prepare kernel and an empty persistent launch)."""
-    R, A, T, I = owner.rays_levels, owner.active_levels, owner.hit_t_levels, owner.hit_id_levels
-    for j in range(1, bounces):
-        c.reflect_rays_next(R[j - 1], A[j - 1], T[j - 1], I[j - 1], owner.d_matidx, owner.d_reflect, owner.num_materials,
-                            owner.d_verts, owner.d_faces, eps, R[j], A[j])
-        c.trace_dda(uvalue, uspan, uoffset, owner.d_verts, owner.d_faces, R[j], A[j], T[j], I[j])
+def camera_pass(c, f, b, setup, cam):
+    """updateLightPosition (per_frame_funcs.h:6), d_cam_position <- worldori (main.cu:128), fillCoordinatesData,
+    build_frustum_grid, FrustumTracer::trace."""
+    c.set_light_position(setup.shading_light)
+    b._upload_cam_pos(cam.worldori)
+    c.upload_camera(cam.camcoords)
+    c.grid_build_perspective(f.d_faces, f.d_verts, f.F)
+    value, span, offset, _ = c.grid_ptrs(GRID_PERSPECTIVE)
+    c.trace_primary(value, span, offset, f.normal, f.t, f.dir, f.is_shadowed, f.intersect_id, f.d_verts, f.d_faces)
 
 
-def shade_reflections(c, owner, bounces, cam_pos):
-    if bounces == 1:
-        c.shade_reflect(owner.image, owner.normal, owner.t, owner.dir, owner.intersect_id, cam_pos, owner.d_matidx,
-                        owner.d_matlist, owner.d_reflect, owner.num_materials, owner.d_verts, owner.d_faces, owner.rays,
-                        owner.active, owner.hit_t, owner.hit_id)
+def use_light_camera(c, lcam):
+    """dd_camcoords is the light's from here on, shadows or not: the light grid build and the shading kernels read it
+    (main.cu:158-170)."""
+    c.upload_camera(lcam.camcoords)
+
+
+def build_grid(c, f, which, shards=None):
+    """build_secondary_frustum_grid (GRID_SPHERICAL) or the uniform grid (GRID_UNIFORM) over f's triangles.
+    shards (parallel.GridShards; one-stream frames only): this rank bins its window of the triangle list, the shards
+    are exchanged and merged."""
+    if shards is None:
+        if which == GRID_SPHERICAL:
+            c.grid_build_spherical(f.d_faces, f.d_verts, f.F, PI_F, PI_F)
+        else:
+            c.grid_build_uniform(f.d_faces, f.d_verts, f.F, f.bbmin, f.bbmax)
+        return
+    from .parallel import face_window
+
+    c.set_face_window(*face_window(shards.rank, shards.world, f.F))
+    try:
+        build_grid(c, f, which)
+        value, key, span, offset, gi = c.grid_arrays(which)
+        ks, vs, sps, counts = shards.exchange(key, value, span, gi.total_refs)
+        if shards.world == 1:  # the parts must not be the context's own arrays
+            ks, vs, sps = [ks[0].clone()], [vs[0].clone()], [sps[0].clone()]
+        c.grid_merge_shards(which, ks, vs, sps, counts)
+        f._shard_parts = (ks, vs, sps)  # alive until the merge has run
+    finally:
+        c.set_face_window(0, -1)  # whatever happened: later builds bin every triangle again
+
+
+# The one-stream frame builds the light grid between the ray mapping and the sort (the reference's order), the
+# two-stream frames on the side stream: so these are two stages, and the shadow trace is given the grid's pointers.
+def map_rays(c, f, b):
+    """getEffectiveRayGridMapping."""
+    c.map_rays_to_light(f.t, f.dir, b._d_map, b.cam_pos, PI_F, PI_F)
+
+
+def sort_rays(c, b):
+    """processData, deferred: the chunk count stays on the device until num_chunks is read."""
+    b._num_chunks = c.sort_rays(b._d_map, b._prefix, deferred=True)
+
+
+def trace_shadows(c, f, b, light_grid):
+    """check_for_shadows through the light grid; light_grid: its grid_ptrs()."""
+    lvalue, lspan, loffset, _ = light_grid
+    c.trace_shadow(lvalue, f.d_verts, f.d_faces, lspan, loffset, f.t, f.dir, f.is_shadowed, b._d_map, b._prefix,
+                   b.cam_pos, b._num_chunks)
+
+
+def reflect_rays(c, f, cam_pos):
+    """Level 1's secondary rays from the primary hits."""
+    c.reflect_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
+                   f.d_faces, f.reflect_eps, f.rays, f.active)
+
+
+def trace_reflections(c, f, bounces):
+    """3D-DDA of level 1 through c's uniform grid, then levels 2..bounces (next rays -> 3D-DDA) behind it with no
+    host wait (a level without an active ray costs the DDA's prepare kernel and an empty persistent launch)."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    rays, active, hit_t, hit_id = f.rays, f.active, f.hit_t, f.hit_id
+    for j in range(bounces):
+        if j:
+            nrays, nactive = f.rays_levels[j], f.active_levels[j]
+            c.reflect_rays_next(rays, active, hit_t, hit_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
+                                f.d_faces, f.reflect_eps, nrays, nactive)
+            rays, active, hit_t, hit_id = nrays, nactive, f.hit_t_levels[j], f.hit_id_levels[j]
+        c.trace_dda(uvalue, uspan, uoffset, f.d_verts, f.d_faces, rays, active, hit_t, hit_id)
+
+
+def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces):
+    """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1), then add_shadows."""
+    if reflect and bounces == 1:
+        c.shade_reflect(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.d_reflect,
+                        f.num_materials, f.d_verts, f.d_faces, f.rays, f.active, f.hit_t, f.hit_id)
+    elif reflect:
+        c.shade_reflect_depth(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                              f.d_reflect, f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
+                              f.active_levels, f.hit_t_levels, f.hit_id_levels)
+    elif frame_cnt < 2:
+        c.shade_simple(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                       f.num_materials)
     else:
-        c.shade_reflect_depth(owner.image, owner.normal, owner.t, owner.dir, owner.intersect_id, cam_pos,
-                              owner.d_matidx, owner.d_matlist, owner.d_reflect, owner.num_materials, owner.d_verts,
-                              owner.d_faces, bounces, owner.rays_levels, owner.active_levels, owner.hit_t_levels,
-                              owner.hit_id_levels)
+        c.shade_spotlight(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                          f.num_materials)
+    if shadows:
+        c.shade_add_shadows(f.image, f.is_shadowed)
 
 
 class FrameSetup:
@@ -87,70 +162,11 @@ def make_camera(params, fovy, aspect):
     return c.adjustCameraAndPosition()
 
 
-class Renderer:
-    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, reflect_eps=1e-3, overlap=False,
-                 shards=None, helper_thread=True, aux_stream=None, batch_builds=False):
-        """overlap=True: the light grid and the uniform grid (which do not depend on the camera pass) are built
-        by a second context on a second HIP stream while the main stream builds the perspective grid and
-        traces the primary rays; streams are joined with events before the grids are consumed.  Same results.
-        A grid build blocks its caller once (the read-back of total_refs), so the second context is driven by
-        a helper thread: both streams then really run side by side."""
-        t = ctx.torch
-        self.ctx = ctx
-        self.aux = None
-        self._worker = None
-        # parallel.GridShards: the light grid and the uniform grid are built in shards of the triangle list, one
-        # per rank, exchanged and merged (SURVEY.md 8f.1); one-stream frames only
-        self.shards = shards
-        assert not (overlap and shards is not None), "sharded builds run in the one-stream frame"
-        # (two-stream frame from one host thread: the light and the uniform build may share their sorts' launches --
-        # three launches less per frame, measured 2 % SLOWER with four frames in flight and equal with one:
-        # profiles/r04_batched_builds.txt -- so it is off unless asked for)
-        self.batch_builds = batch_builds
-        if overlap:
-            from .device import Context
+class _Frame:
+    """The scene on the device and the arrays of a whole frame, which every context that renders rows of it writes
+    (pixel ids are global)."""
 
-            self.main_stream = t.cuda.current_stream(ctx.device)
-            # (aux_stream: a stream the caller made; which streams end up on the same hardware queue depends on
-            # the order in which they were created)
-            self.aux_stream = aux_stream if aux_stream is not None else t.cuda.Stream(ctx.device)
-            with t.cuda.stream(self.aux_stream):
-                self.aux = Context(ctx.width, ctx.height, device=ctx.device_index, light_grid=ctx.light_grid,
-                                   rows=ctx.rows, flags=int(ctx.cfg.flags),
-                                   uniform_dims=tuple(ctx.cfg.uniform_dims[k] for k in range(3)),
-                                   slabs=int(ctx.cfg.slabs))
-            self._inline = not helper_thread
-            if self._inline:
-                # builds that never wait for the device (option async_build): one host thread keeps both streams fed
-                ctx.set_option("async_build", 1)
-                self.aux.set_option("async_build", 1)
-            # the bounce runs beside the ray sort and the shadow pass and has slack: four persistent waves per CU leave
-            # the registers and LDS of every CU to the main stream's workgroups (with the whole chip taken by
-            # the bounce's waves, a sort pass of the main stream waited 0.2 ms for room)
-            self.aux.set_option("dda_blocks", 1024)
-            import queue
-            import threading
-
-            if self._inline:
-                return self._finish_init(ctx, verts, faces, matidx, mat_list, reflect, reflect_eps)
-            self._jobs, self._done = queue.Queue(), queue.Queue()
-
-            def loop():
-                while True:
-                    job = self._jobs.get()
-                    if job is None:
-                        return
-                    try:
-                        job()
-                        self._done.put(None)
-                    except BaseException as e:  # handed to the frame loop
-                        self._done.put(e)
-
-            self._worker = threading.Thread(target=loop, name="ugrt-aux", daemon=True)
-            self._worker.start()
-        self._finish_init(ctx, verts, faces, matidx, mat_list, reflect, reflect_eps)
-
-    def _finish_init(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps):
+    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps):
         t = ctx.torch
         self.F = int(len(faces))
         self.num_materials = int(len(mat_list) // 6 if np.ndim(mat_list) == 1 else len(mat_list))
@@ -170,9 +186,35 @@ class Renderer:
         self.dir = ctx.empty(3 * N, t.float32)
         self.is_shadowed = ctx.empty(N, t.int32)
         self.intersect_id = ctx.empty(N, t.int32)
-        self._d_map = ctx.empty(2 * ctx.npix, t.int32)
-        self._prefix = ctx.empty(ctx.prefix_capacity(), t.int32)
         self.image = t.zeros(3 * N, dtype=t.uint8, device=ctx.device)
+        self.torch = t
+        # the reflection levels 1..D one behind the other (_ensure_reflect_buffers)
+        self.rays = self.active = self.hit_t = self.hit_id = None
+        self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
+        self.reflect_eps = float(reflect_eps)
+        self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
+
+    def _ensure_reflect_buffers(self, bounces=1):
+        """rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)], allocated once for the
+        deepest frame asked for; rays / active / hit_t / hit_id are level 1's views."""
+        if self.rays_levels is not None and self.rays_levels.shape[0] >= bounces:
+            return
+        t, N, dev = self.torch, self.N, self.image.device
+        self.rays_levels = t.empty((bounces, 6 * N), dtype=t.float32, device=dev)
+        self.active_levels = t.empty((bounces, N), dtype=t.int32, device=dev)
+        self.hit_t_levels = t.empty((bounces, N), dtype=t.float32, device=dev)
+        self.hit_id_levels = t.empty((bounces, N), dtype=t.int32, device=dev)
+        self.rays, self.active = self.rays_levels[0], self.active_levels[0]
+        self.hit_t, self.hit_id = self.hit_t_levels[0], self.hit_id_levels[0]
+
+
+class _Band:
+    """What each context that renders rows of a frame owns besides the frame's arrays: d_cam_position with the pinned
+    staging that feeds it, and the ray map, chunk starts and chunk count of its shadow pass."""
+
+    def __init__(self, ctx):
+        t = ctx.torch
+        self.ctx = ctx
         self.cam_pos = ctx.empty(3, t.float32)
         # pinned staging for d_cam_position: a pageable-memory copy would make the host wait for the whole
         # previous frame before it may enqueue the next one.  Two buffers alternate and an event behind each copy
@@ -180,13 +222,9 @@ class Renderer:
         self._cam_pos_host = [t.empty(3, dtype=t.float32).pin_memory() for _ in range(2)]
         self._cam_pos_done = [None, None]  # event behind the copy out of each staging buffer
         self._cam_pos_turn = 0
-        self.rays = self.active = self.hit_t = self.hit_id = None
-        # bounces > 1: levels 1..D one behind the other (level_buffers)
-        self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
-        self.reflect_eps = float(reflect_eps)
+        self._d_map = ctx.empty(2 * ctx.npix, t.int32)
+        self._prefix = ctx.empty(ctx.prefix_capacity(), t.int32)
         self._num_chunks = 0
-        self.orig = None
-        self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
     def _upload_cam_pos(self, worldori):
         """main.cu:128 d_cam_position <- worldori, without a host wait in the steady state."""
@@ -221,6 +259,74 @@ class Renderer:
         self.num_chunks
         return self._prefix
 
+
+class Renderer(_Frame, _Band):
+    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, reflect_eps=1e-3, overlap=False,
+                 shards=None, helper_thread=True, aux_stream=None, batch_builds=False):
+        """overlap=True: the light grid and the uniform grid (which do not depend on the camera pass) are built
+        by a second context on a second HIP stream while the main stream builds the perspective grid and
+        traces the primary rays; streams are joined with events before the grids are consumed.  Same results.
+        A grid build blocks its caller once (the read-back of total_refs), so the second context is driven by
+        a helper thread: both streams then really run side by side."""
+        self.aux = None
+        self._worker = None
+        # parallel.GridShards: the light grid and the uniform grid are built in shards of the triangle list, one
+        # per rank, exchanged and merged (SURVEY.md 8f.1); one-stream frames only
+        self.shards = shards
+        assert not (overlap and shards is not None), "sharded builds run in the one-stream frame"
+        # (two-stream frame from one host thread: the light and the uniform build may share their sorts' launches --
+        # three launches less per frame, measured 2 % SLOWER with four frames in flight and equal with one:
+        # profiles/r04_batched_builds.txt -- so it is off unless asked for)
+        self.batch_builds = batch_builds
+        self._inline = overlap and not helper_thread
+        if overlap:
+            self._make_side_context(ctx, aux_stream, helper_thread)
+        _Frame.__init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps)
+        _Band.__init__(self, ctx)
+        self.orig = None
+
+    def _make_side_context(self, ctx, aux_stream, helper_thread):
+        from .device import Context
+
+        t = ctx.torch
+        self.main_stream = t.cuda.current_stream(ctx.device)
+        # (aux_stream: a stream the caller made; which streams end up on the same hardware queue depends on
+        # the order in which they were created)
+        self.aux_stream = aux_stream if aux_stream is not None else t.cuda.Stream(ctx.device)
+        with t.cuda.stream(self.aux_stream):
+            self.aux = Context(ctx.width, ctx.height, device=ctx.device_index, light_grid=ctx.light_grid,
+                               rows=ctx.rows, flags=int(ctx.cfg.flags),
+                               uniform_dims=tuple(ctx.cfg.uniform_dims[k] for k in range(3)),
+                               slabs=int(ctx.cfg.slabs))
+        if not helper_thread:
+            # builds that never wait for the device (option async_build): one host thread keeps both streams fed
+            ctx.set_option("async_build", 1)
+            self.aux.set_option("async_build", 1)
+        # the bounce runs beside the ray sort and the shadow pass and has slack: four persistent waves per CU leave
+        # the registers and LDS of every CU to the main stream's workgroups (with the whole chip taken by
+        # the bounce's waves, a sort pass of the main stream waited 0.2 ms for room)
+        self.aux.set_option("dda_blocks", 1024)
+        if not helper_thread:
+            return
+        import queue
+        import threading
+
+        self._jobs, self._done = queue.Queue(), queue.Queue()
+
+        def loop():
+            while True:
+                job = self._jobs.get()
+                if job is None:
+                    return
+                try:
+                    job()
+                    self._done.put(None)
+                except BaseException as e:  # handed to the frame loop
+                    self._done.put(e)
+
+        self._worker = threading.Thread(target=loop, name="ugrt-aux", daemon=True)
+        self._worker.start()
+
     # Model::init_orig_list, scene.h:336
     def init_orig_list(self, size, offset):
         self.orig = self.d_verts[3 * offset:3 * (offset + size)].clone()
@@ -239,80 +345,34 @@ class Renderer:
             self._worker.join()
             self._worker = None
 
-    def _ensure_reflect_buffers(self, bounces=1):
-        if bounces > 1:
-            level_buffers(self, self.ctx, self.N, bounces)
-        elif self.rays is None:
-            t = self.ctx.torch
-            self.rays = self.ctx.empty(6 * self.N, t.float32)
-            self.active = self.ctx.empty(self.N, t.int32)
-            self.hit_t = self.ctx.empty(self.N, t.float32)
-            self.hit_id = self.ctx.empty(self.N, t.int32)
-
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1):
-        """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  With bounces > 1,
-        rays_levels / active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t /
-        hit_id are level 1's views."""
+        """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
+        active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
+        1's views."""
         bounces = check_bounces(bounces)
+        if reflect and shade:
+            self._ensure_reflect_buffers(bounces)
         if self.aux is not None and shade:
-            if getattr(self, "_inline", False):
-                return self._display_two_streams_inline(setup, frame_cnt, shadows, reflect, bounces)
-            return self._display_overlapped(setup, frame_cnt, shadows, reflect, bounces)
+            two_streams = self._display_two_streams_inline if self._inline else self._display_overlapped
+            return two_streams(setup, frame_cnt, shadows, reflect, bounces)
         ctx = self.ctx
-        t = ctx.torch
-        # updateLightPosition, per_frame_funcs.h:6
-        ctx.set_light_position(setup.shading_light)
-        cam = make_camera(setup.camera, setup.fovy, self.aspect)
-        # main.cu:128 d_cam_position <- worldori ; fillCoordinatesData
-        self._upload_cam_pos(cam.worldori)
-        ctx.upload_camera(cam.camcoords)
-        # build_frustum_grid
-        ctx.grid_build_perspective(self.d_faces, self.d_verts, self.F)
-        value, span, offset, _ = ctx.grid_ptrs(GRID_PERSPECTIVE)
-        # FrustumTracer::trace
-        ctx.trace_primary(value, span, offset, self.normal, self.t, self.dir, self.is_shadowed, self.intersect_id,
-                          self.d_verts, self.d_faces)
-        # dd_camcoords is the light's from here on, shadows or not (main.cu:158-170: the shading kernels read it)
-        lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
-        ctx.upload_camera(lcam.camcoords)
+        camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
+        use_light_camera(ctx, make_camera(setup.light_camera, setup.fovy, self.aspect))
         if shadows:
-            ctx.map_rays_to_light(self.t, self.dir, self._d_map, self.cam_pos, PI_F, PI_F)
-            if self.shards is not None:
-                self._sharded(GRID_SPHERICAL,
-                              lambda: ctx.grid_build_spherical(self.d_faces, self.d_verts, self.F, PI_F, PI_F))
-            else:
-                ctx.grid_build_spherical(self.d_faces, self.d_verts, self.F, PI_F, PI_F)
-            lvalue, lspan, loffset, _ = ctx.grid_ptrs(GRID_SPHERICAL)
-            self._num_chunks = ctx.sort_rays(self._d_map, self._prefix, deferred=True)
-            ctx.trace_shadow(lvalue, self.d_verts, self.d_faces, lspan, loffset, self.t, self.dir, self.is_shadowed,
-                             self._d_map, self._prefix, self.cam_pos, self._num_chunks)
+            map_rays(ctx, self, self)
+            build_grid(ctx, self, GRID_SPHERICAL, self.shards)
+            light_grid = ctx.grid_ptrs(GRID_SPHERICAL)
+            sort_rays(ctx, self)
+            trace_shadows(ctx, self, self, light_grid)
         if not shade:
             return
         if reflect:
-            self._ensure_reflect_buffers(bounces)
-            ctx.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect,
-                             self.num_materials, self.d_verts, self.d_faces, self.reflect_eps, self.rays,
-                             self.active)
-            if self.shards is not None:
-                self._sharded(GRID_UNIFORM, lambda: ctx.grid_build_uniform(self.d_faces, self.d_verts, self.F,
-                                                                            self.bbmin, self.bbmax))
-            else:
-                ctx.grid_build_uniform(self.d_faces, self.d_verts, self.F, self.bbmin, self.bbmax)
-            uvalue, uspan, uoffset, _ = ctx.grid_ptrs(GRID_UNIFORM)
-            ctx.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t,
-                          self.hit_id)
-            trace_deeper_levels(ctx, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
-            shade_reflections(ctx, self, bounces, self.cam_pos)
-        elif frame_cnt < 2:
-            ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                             self.d_matidx, self.d_matlist, self.num_materials)
-        else:
-            ctx.shade_spotlight(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                                self.d_matidx, self.d_matlist, self.num_materials)
-        if shadows:
-            ctx.shade_add_shadows(self.image, self.is_shadowed)
+            reflect_rays(ctx, self, self.cam_pos)
+            build_grid(ctx, self, GRID_UNIFORM, self.shards)
+            trace_reflections(ctx, self, bounces)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
 
-    def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces=1):
+    def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
         uniform grid, then - once the primary hits exist - secondary rays and the 3D-DDA.  Main stream: screen
         grid, primary rays, ray mapping and sort, shadow rays (after the light grid), shading (after the DDA).
@@ -322,8 +382,6 @@ class Renderer:
         ctx, aux, t = self.ctx, self.aux, self.ctx.torch
         main, side = self.main_stream, self.aux_stream
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
-        if reflect:
-            self._ensure_reflect_buffers(bounces)
         ev_primary, ev_light_grid = t.cuda.Event(), t.cuda.Event()
         primary_recorded, light_grid_recorded = threading.Event(), threading.Event()
         # side stream: starts once the geometry of this frame is final on the main stream
@@ -334,8 +392,8 @@ class Renderer:
         def side_job():
             try:
                 if shadows:
-                    aux.upload_camera(lcam.camcoords)
-                    aux.grid_build_spherical(self.d_faces, self.d_verts, self.F, PI_F, PI_F)
+                    use_light_camera(aux, lcam)
+                    build_grid(aux, self, GRID_SPHERICAL)
                     ev_light_grid.record(side)
             except BaseException:
                 status["light_grid_failed"] = True  # the main thread must not wait for an event never recorded
@@ -343,49 +401,34 @@ class Renderer:
             finally:
                 light_grid_recorded.set()
             if reflect:
-                aux.grid_build_uniform(self.d_faces, self.d_verts, self.F, self.bbmin, self.bbmax)
+                build_grid(aux, self, GRID_UNIFORM)
                 primary_recorded.wait()
                 if status["primary_failed"]:
                     return
                 side.wait_event(ev_primary)
-                aux.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect,
-                                 self.num_materials, self.d_verts, self.d_faces, self.reflect_eps, self.rays,
-                                 self.active)
-                uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
-                aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active,
-                              self.hit_t, self.hit_id)
-                trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
+                reflect_rays(aux, self, self.cam_pos)
+                trace_reflections(aux, self, bounces)
 
         self._jobs.put(side_job)
         failed = None
         try:
             try:
-                # main stream: the camera pass
-                ctx.set_light_position(setup.shading_light)
-                cam = make_camera(setup.camera, setup.fovy, self.aspect)
-                self._upload_cam_pos(cam.worldori)
-                ctx.upload_camera(cam.camcoords)
-                ctx.grid_build_perspective(self.d_faces, self.d_verts, self.F)
-                value, span, offset, _ = ctx.grid_ptrs(GRID_PERSPECTIVE)
-                ctx.trace_primary(value, span, offset, self.normal, self.t, self.dir, self.is_shadowed,
-                                  self.intersect_id, self.d_verts, self.d_faces)
+                camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
                 ev_primary.record(main)
             except BaseException as e:
                 status["primary_failed"] = True  # the side job skips what depends on the primary hits
                 raise e
             finally:
                 primary_recorded.set()
-            ctx.upload_camera(lcam.camcoords)  # dd_camcoords is the light's from here on (main.cu:170)
+            use_light_camera(ctx, lcam)
             if shadows:
-                ctx.map_rays_to_light(self.t, self.dir, self._d_map, self.cam_pos, PI_F, PI_F)
-                self._num_chunks = ctx.sort_rays(self._d_map, self._prefix, deferred=True)
+                map_rays(ctx, self, self)
+                sort_rays(ctx, self)
                 light_grid_recorded.wait()
                 if status["light_grid_failed"]:
                     raise RuntimeError("the light grid build on the side stream failed")
                 main.wait_event(ev_light_grid)
-                lvalue, lspan, loffset, _ = aux.grid_ptrs(GRID_SPHERICAL)
-                ctx.trace_shadow(lvalue, self.d_verts, self.d_faces, lspan, loffset, self.t, self.dir,
-                                 self.is_shadowed, self._d_map, self._prefix, self.cam_pos, self._num_chunks)
+                trace_shadows(ctx, self, self, aux.grid_ptrs(GRID_SPHERICAL))
         except BaseException as e:
             failed = e
         finally:
@@ -397,26 +440,15 @@ class Renderer:
             raise failed
         if err is not None:
             raise err
-        if reflect:
-            shade_reflections(ctx, self, bounces, self.cam_pos)
-        elif frame_cnt < 2:
-            ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                             self.d_matidx, self.d_matlist, self.num_materials)
-        else:
-            ctx.shade_spotlight(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                                self.d_matidx, self.d_matlist, self.num_materials)
-        if shadows:
-            ctx.shade_add_shadows(self.image, self.is_shadowed)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
 
-    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect, bounces=1):
+    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect, bounces):
         """The two-stream frame from ONE host thread: with option async_build no call waits for the device, so the
         side stream's work is simply enqueued first (light grid, uniform grid), then the camera pass on the main
         stream, then what depends on the primary hits on either stream; events join them as in _display_overlapped."""
         ctx, aux, t = self.ctx, self.aux, self.ctx.torch
         main, side = self.main_stream, self.aux_stream
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
-        if reflect:
-            self._ensure_reflect_buffers(bounces)
         ev_primary, ev_light_grid = t.cuda.Event(), t.cuda.Event()
         side.wait_stream(main)  # the geometry of this frame is final on the main stream
         # the light grid and the uniform grid depend on the geometry only: their reference lists are sorted in shared
@@ -424,69 +456,36 @@ class Renderer:
         batch = shadows and reflect and self.batch_builds
         if batch:
             aux.grid_build_batch_begin()
-        if shadows:
-            aux.upload_camera(lcam.camcoords)
-            aux.grid_build_spherical(self.d_faces, self.d_verts, self.F, PI_F, PI_F)
-            if not batch:
-                ev_light_grid.record(side)
-        if reflect:
-            aux.grid_build_uniform(self.d_faces, self.d_verts, self.F, self.bbmin, self.bbmax)
+        try:
+            if shadows:
+                use_light_camera(aux, lcam)
+                build_grid(aux, self, GRID_SPHERICAL)
+                if not batch:
+                    ev_light_grid.record(side)
+            if reflect:
+                build_grid(aux, self, GRID_UNIFORM)
+        except BaseException:
+            if batch:  # an open batch would refuse every later frame's; the build's own failure is the one raised
+                with contextlib.suppress(Exception):
+                    aux.grid_build_batch_end()
+            raise
         if batch:
             aux.grid_build_batch_end()
             ev_light_grid.record(side)
-        ctx.set_light_position(setup.shading_light)
-        cam = make_camera(setup.camera, setup.fovy, self.aspect)
-        self._upload_cam_pos(cam.worldori)
-        ctx.upload_camera(cam.camcoords)
-        ctx.grid_build_perspective(self.d_faces, self.d_verts, self.F)
-        value, span, offset, _ = ctx.grid_ptrs(GRID_PERSPECTIVE)
-        ctx.trace_primary(value, span, offset, self.normal, self.t, self.dir, self.is_shadowed, self.intersect_id,
-                          self.d_verts, self.d_faces)
+        camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
         ev_primary.record(main)
         if reflect:
             side.wait_event(ev_primary)
-            aux.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect,
-                             self.num_materials, self.d_verts, self.d_faces, self.reflect_eps, self.rays, self.active)
-            uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
-            aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t,
-                          self.hit_id)
-            trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
-        ctx.upload_camera(lcam.camcoords)  # dd_camcoords is the light's from here on (main.cu:170)
+            reflect_rays(aux, self, self.cam_pos)
+            trace_reflections(aux, self, bounces)
+        use_light_camera(ctx, lcam)
         if shadows:
-            ctx.map_rays_to_light(self.t, self.dir, self._d_map, self.cam_pos, PI_F, PI_F)
-            self._num_chunks = ctx.sort_rays(self._d_map, self._prefix, deferred=True)
+            map_rays(ctx, self, self)
+            sort_rays(ctx, self)
             main.wait_event(ev_light_grid)
-            lvalue, lspan, loffset, _ = aux.grid_ptrs(GRID_SPHERICAL)
-            ctx.trace_shadow(lvalue, self.d_verts, self.d_faces, lspan, loffset, self.t, self.dir, self.is_shadowed,
-                             self._d_map, self._prefix, self.cam_pos, self._num_chunks)
+            trace_shadows(ctx, self, self, aux.grid_ptrs(GRID_SPHERICAL))
         main.wait_stream(side)
-        if reflect:
-            shade_reflections(ctx, self, bounces, self.cam_pos)
-        elif frame_cnt < 2:
-            ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                             self.d_matidx, self.d_matlist, self.num_materials)
-        else:
-            ctx.shade_spotlight(self.image, self.normal, self.t, self.dir, self.intersect_id, self.cam_pos,
-                                self.d_matidx, self.d_matlist, self.num_materials)
-        if shadows:
-            ctx.shade_add_shadows(self.image, self.is_shadowed)
-
-    def _sharded(self, which, build):
-        """Runs `build` on this rank's window of the triangle list, exchanges the shards, merges them."""
-        from .parallel import face_window
-
-        ctx, sh = self.ctx, self.shards
-        ctx.set_face_window(*face_window(sh.rank, sh.world, self.F))
-        try:
-            build()
-            value, key, span, offset, gi = ctx.grid_arrays(which)
-            ks, vs, sps, counts = sh.exchange(key, value, span, gi.total_refs)
-            if sh.world == 1:  # the parts must not be the context's own arrays
-                ks, vs, sps = [ks[0].clone()], [vs[0].clone()], [sps[0].clone()]
-            ctx.grid_merge_shards(which, ks, vs, sps, counts)
-            self._shard_parts = (ks, vs, sps)  # alive until the merge has run
-        finally:
-            ctx.set_face_window(0, -1)  # whatever happened: later builds bin every triangle again
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
 
     def synchronize(self):
         """Both contexts are synchronised before anything is raised: an overflow reported by one must not leave the
@@ -508,7 +507,7 @@ class Renderer:
         return self.image[3 * ctx.p0:3 * (ctx.p0 + ctx.npix)].view(-1, ctx.width, 3)
 
 
-class BandedRenderer:
+class BandedRenderer(_Frame):
     """ONE frame at a time, cut into bands of tile rows that run on HIP streams of their own (SURVEY 8(e)'s sharding,
     applied to the streams of one GPU instead of to GPUs).
 
@@ -534,108 +533,72 @@ class BandedRenderer:
         nby = H // 8
         import torch as t
 
-        self.torch = t
         dev = t.device("cuda", device)
         self.main_stream = t.cuda.current_stream(dev)
         self.side_stream = t.cuda.Stream(dev)
         with t.cuda.stream(self.side_stream):
             self.aux = Context(W, H, device=device, light_grid=light_grid, flags=flags, uniform_dims=uniform_dims)
-        self.streams, self.rs = [], []
+        self.streams, self._per_band = [], []
         bounds = parallel.equal_bounds(bands, nby)
         for b in range(bands):
             st = self.main_stream if b == 0 else t.cuda.Stream(self.aux.device)
             with t.cuda.stream(st):
                 cx = Context(W, H, device=device, light_grid=light_grid, rows=(bounds[b], bounds[b + 1]), flags=flags,
                              uniform_dims=uniform_dims)
-                r = Renderer(cx, verts, faces, matidx, mat_list, reflect)
+                self._per_band.append(_Band(cx))
             self.streams.append(st)
-            self.rs.append(r)
-        r0 = self.rs[0]
-        r0._ensure_reflect_buffers()
-        shared = ("normal", "t", "dir", "is_shadowed", "intersect_id", "image", "rays", "active", "hit_t", "hit_id", "d_verts",
-                  "d_faces", "d_matidx", "d_matlist", "d_reflect")
-        for r in self.rs[1:]:
-            for name in shared:
-                setattr(r, name, getattr(r0, name))
-        for name in shared:
-            setattr(self, name, getattr(r0, name))
-        self.F, self.num_materials, self.bbmin, self.bbmax, self.aspect = r0.F, r0.num_materials, r0.bbmin, r0.bbmax, r0.aspect
-        self.N, self.reflect_eps = r0.N, r0.reflect_eps
-        # bounces > 1: the levels of the frame (level_buffers), shared by the bands like the level-1 arrays
-        self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
-        for c in [self.aux] + [r.ctx for r in self.rs]:
+        # the scene and the frame's arrays once, on the main stream (band 0's)
+        _Frame.__init__(self, self._per_band[0].ctx, verts, faces, matidx, mat_list, reflect, 1e-3)
+        for c in self.contexts():
             c.set_option("async_build", 1)
         # (as in the two-stream frame: the bounce's persistent waves leave room for the bands' short kernels)
         self.aux.set_option("dda_blocks", 1024)
 
     def contexts(self):
-        return [self.aux] + [r.ctx for r in self.rs]
+        return [self.aux] + [b.ctx for b in self._per_band]
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1):
         bounces = check_bounces(bounces)
         t, aux, main, side = self.torch, self.aux, self.main_stream, self.side_stream
-        if reflect and bounces > 1:
-            level_buffers(self, aux, self.N, bounces)
-        r0 = self.rs[0]
+        if reflect:
+            self._ensure_reflect_buffers(bounces)
         cam = make_camera(setup.camera, setup.fovy, self.aspect)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         ev_grids, ev_dda = t.cuda.Event(), t.cuda.Event()
-        ev_prim = [t.cuda.Event() for _ in self.rs]
+        ev_prim = [t.cuda.Event() for _ in self._per_band]
         for st in self.streams[1:] + [side]:
             st.wait_stream(main)  # the geometry of this frame (and the last frame's readers) are behind the main stream
         with t.cuda.stream(side):
             if shadows:
-                aux.upload_camera(lcam.camcoords)
-                aux.grid_build_spherical(self.d_faces, self.d_verts, self.F, PI_F, PI_F)
+                use_light_camera(aux, lcam)
+                build_grid(aux, self, GRID_SPHERICAL)
             if reflect:
-                aux.grid_build_uniform(self.d_faces, self.d_verts, self.F, self.bbmin, self.bbmax)
+                build_grid(aux, self, GRID_UNIFORM)
             ev_grids.record(side)
-        for r, st, ev in zip(self.rs, self.streams, ev_prim):
+        for b, st, ev in zip(self._per_band, self.streams, ev_prim):
             with t.cuda.stream(st):
-                ctx = r.ctx
-                ctx.set_light_position(setup.shading_light)
-                r._upload_cam_pos(cam.worldori)
-                ctx.upload_camera(cam.camcoords)
-                ctx.grid_build_perspective(self.d_faces, self.d_verts, self.F)
-                value, span, offset, _ = ctx.grid_ptrs(GRID_PERSPECTIVE)
-                ctx.trace_primary(value, span, offset, self.normal, self.t, self.dir, self.is_shadowed, self.intersect_id,
-                                  self.d_verts, self.d_faces)
+                camera_pass(b.ctx, self, b, setup, cam)
                 ev.record(st)
         if reflect:
             with t.cuda.stream(side):
                 for ev in ev_prim:
                     side.wait_event(ev)
-                aux.reflect_rays(r0.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect,
-                                 self.num_materials, self.d_verts, self.d_faces, r0.reflect_eps, self.rays, self.active)
-                uvalue, uspan, uoffset, _ = aux.grid_ptrs(GRID_UNIFORM)
-                aux.trace_dda(uvalue, uspan, uoffset, self.d_verts, self.d_faces, self.rays, self.active, self.hit_t, self.hit_id)
-                trace_deeper_levels(aux, self, bounces, self.reflect_eps, uvalue, uspan, uoffset)
+                reflect_rays(aux, self, self._per_band[0].cam_pos)
+                trace_reflections(aux, self, bounces)
                 ev_dda.record(side)
-        for r, st in zip(self.rs, self.streams):
+        for b, st in zip(self._per_band, self.streams):
             with t.cuda.stream(st):
-                ctx = r.ctx
-                ctx.upload_camera(lcam.camcoords)  # dd_camcoords is the light's from here on (main.cu:170)
+                use_light_camera(b.ctx, lcam)
                 if shadows:
-                    ctx.map_rays_to_light(self.t, self.dir, r._d_map, r.cam_pos, PI_F, PI_F)
-                    r._num_chunks = ctx.sort_rays(r._d_map, r._prefix, deferred=True)
+                    map_rays(b.ctx, self, b)
+                    sort_rays(b.ctx, b)
                     st.wait_event(ev_grids)
-                    lvalue, lspan, loffset, _ = aux.grid_ptrs(GRID_SPHERICAL)
-                    ctx.trace_shadow(lvalue, self.d_verts, self.d_faces, lspan, loffset, self.t, self.dir, self.is_shadowed,
-                                     r._d_map, r._prefix, r.cam_pos, r._num_chunks)
-        for r, st in zip(self.rs, self.streams):
+                    trace_shadows(b.ctx, self, b, aux.grid_ptrs(GRID_SPHERICAL))
+        for b, st in zip(self._per_band, self.streams):
             with t.cuda.stream(st):
-                ctx = r.ctx
                 if reflect:
                     st.wait_event(ev_dda)
-                    shade_reflections(ctx, self, bounces, r.cam_pos)
-                elif frame_cnt < 2:
-                    ctx.shade_simple(self.image, self.normal, self.t, self.dir, self.intersect_id, r.cam_pos, self.d_matidx,
-                                     self.d_matlist, self.num_materials)
-                else:
-                    ctx.shade_spotlight(self.image, self.normal, self.t, self.dir, self.intersect_id, r.cam_pos, self.d_matidx,
-                                        self.d_matlist, self.num_materials)
-                if shadows:
-                    ctx.shade_add_shadows(self.image, self.is_shadowed)
+                shade_frame(b.ctx, self, b.cam_pos, frame_cnt, shadows, reflect, bounces)
         for st in self.streams[1:] + [side]:
             main.wait_stream(st)
 
