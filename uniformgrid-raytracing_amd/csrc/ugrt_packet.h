@@ -1,4 +1,4 @@
-// ugrt_packet.h -- device helpers shared by the tracers (ugrt_trace.hip, ugrt_dda.hip): XCD-aware work
+// ugrt_packet.h -- device helpers shared by the tracers (ugrt_trace_primary.hip, ugrt_trace_shadow.hip, ugrt_dda.hip): XCD-aware work
 // placement, triangle records, conservative packet culls, cross-lane primitives.
 #ifndef UGRT_PACKET_H
 #define UGRT_PACKET_H
