@@ -4,11 +4,12 @@
 //   DSKernel -> [D2H + host z loop] -> cudppScan -> [D2H R] -> 4x cudaMalloc ->
 //   SlabKernel -> DSFillkernel -> cudppPlan + cudppSort(32 bit) -> do_scan_dump ->
 //   cudppPlan + cudppCompact -> [D2H] -> set_as_zero -> create_histogram -> cudppScan
-// Here: count (stores the cell range) -> rocPRIM inclusive scan -> [D2H R, 4 B]
-//   -> fill (one thread per REF, coalesced, no recomputation of the bbox) ->
-//   rocPRIM radix sort on ceil(log2 C) bits -> one boundary kernel -> one
-//   per-cell kernel -> rocPRIM exclusive scan.  Outputs are identical arrays:
-//   value[R], key[R], span[C], offset[C].
+// Here: count (stores the cell range) -> inclusive scan -> [D2H {R, wide triangles}, 8 B; an asynchronous build
+//   leaves them on the device] -> fill (one thread per REF, coalesced, no recomputation of the bbox) ->
+//   radix sort on ceil(log2 C) bits -> one boundary kernel -> one scan that forms the spans and their
+//   offsets.  Outputs are identical arrays: value[R], key[R], span[C], offset[C].
+// The host side behind the count kernels is one sequence for the waiting and the asynchronous form:
+//   build_common = scan, plan_waiting or plan_async (a BuildPlan, ugrt_ctx.h), build_fill, build_sort, build_finish.
 // Triangles whose cell range is the WHOLE grid (the reference clamps the screen box of a triangle that
 //   straddles the eye plane to the full screen, SURVEY.md Q9: 325 of 1 M triangles make 10.3 M of the
 //   12.2 M references of the bench scene) are not pushed through fill + sort: they are kept as a short
@@ -664,33 +665,72 @@ static int bits_for(u32 C)
 }
 
 // ---------------------------------------------------------------------------
-// Asynchronous build (option "async_build"): no read-back, the host never waits.  The counts the reference reads
-// back (total_triangles, frustum_grid.h:254) stay on the device; launches and buffers are sized by what the same
-// grid needed in the previous build plus a margin, and every kernel takes the real counts from device memory.
-// k_fill_parts compares them with the capacities first: when they do not fit, the build is emptied (nothing is
-// written out of bounds) and a status bit is raised, which the host sees at its next synchronisation
-// (UGRT_EOVERFLOW; the following build of the grid runs synchronously and sizes the buffers exactly).
+// The shared tail of the three builders, one pipeline in two forms:
+//   inclusive scan of the sizes -> k_fill_parts -> k_fill -> pair sort -> k_wide_rank -> k_bounds -> spans + offsets
+//   (one scan: SpanLoad, SpanTail) -> k_merge_narrow -> k_merge_wide.
+// A waiting build reads the counts the reference reads back (total_triangles, frustum_grid.h:254) and sizes buffers and
+// launches exactly.  An asynchronous build (option "async_build") has no read-back, the host never waits: the counts stay
+// on the device; launches and buffers are sized by what the same grid needed in the previous build plus a margin, and
+// every kernel takes the real counts from device memory.  k_fill_parts compares them with the capacities first: when
+// they do not fit, the build is emptied (nothing is written out of bounds) and a status bit is raised, which the host
+// sees at its next synchronisation (UGRT_EOVERFLOW; the following build of the grid waits and sizes the buffers exactly).
+// Each form fills a BuildPlan (plan_waiting, plan_async); the stages are written once and take from the plan what
+// differs.  (Three stages: everything before the sort, the sort, everything behind it -- so that the builds of a batch,
+// ugrt_grid_build_batch_begin / _end, can share the launches of their sorts.)
 // ---------------------------------------------------------------------------
-// (three parts: everything before the sort, the sort, everything behind it -- so that the builds of a batch,
-// ugrt_grid_build_batch_begin / _end, can share the launches of their sorts)
-static int build_async_begin(ugrt_ctx *ctx, AsyncBuild &b)
+// the reserves of both forms: the sort goes key[0] -> key[1]; with wide triangles the merged lists are written back
+// into key[0]
+static int build_reserve(ugrt_ctx *ctx, Grid &G, size_t bytes0, size_t bytes1, size_t Rn)
 {
-	Grid &G = *b.G;
-	const int F = b.F, ny = b.ny, nz = b.nz, ylo = b.ylo, yhi = b.yhi;
-	const u32 C = b.C;
-	hipStream_t st = ctx->stream;
+	const struct {
+		DevBuf &b;
+		size_t bytes;
+	} want[] = {
+		{ G.key[0], bytes0 }, { G.val[0], bytes0 }, { G.key[1], bytes1 }, { G.val[1], bytes1 },
+		{ G.parts, (Rn / BUILD_THREADS + 2) * 4 }, // first triangle per fill workgroup
+		{ G.span, (size_t)G.C * 8 + 16 },          // span[C], run starts[C], cells_used
+		{ G.offset, (size_t)G.C * 4 },
+	};
+	for (const auto &w : want)
+		if (int rc = ugrt_buf_reserve(ctx, w.b, w.bytes))
+			return rc;
+	return UGRT_OK;
+}
+
+static int plan_waiting(ugrt_ctx *ctx, BuildPlan &p)
+{
+	Grid &G = *p.G;
+	const int gi = (int)(&G - ctx->grid);
+	// total_triangles, frustum_grid.h:254 (the one unavoidable read-back: it sizes the lists), here
+	// as narrow references + number of wide triangles
+	UGRT_HIP(hipMemcpyAsync(ctx->h_pinned + UGRT_PIN_RW, (u32 *)G.scan.p + (p.F - 1), 8, hipMemcpyDeviceToHost, ctx->stream));
+	UGRT_HIP(hipStreamSynchronize(ctx->stream));
+	const u32 Rn = ctx->h_pinned[UGRT_PIN_RW], W = ctx->h_pinned[UGRT_PIN_RW + 1];
+	const unsigned long long Rtot = (unsigned long long)Rn + p.active * W;
+	if (Rtot > 0xFFFFFFF0ull)
+		return ugrt_fail(UGRT_ENOMEM, "grid build: %llu references exceed the 32-bit lists", Rtot);
+	p.Rn = Rn, p.W = W, p.R = (u32)Rtot;
+	p.no_wide = W == 0u;
+	p.own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1 && Rn <= (1u << 30);
+	p.prehist = p.own_sort;
+	G.R = p.R;
+	G.r_exact = true;
+	G.est_rn = Rn;
+	G.est_w = W;
+	G.have_est = true;
+	// (the slots an asynchronous build reports into: never older than this build)
+	ctx->h_pinned[UGRT_PIN_REPORT + 4 * gi] = Rn;
+	ctx->h_pinned[UGRT_PIN_REPORT + 4 * gi + 1] = W;
+	const size_t rb1 = (size_t)(Rn ? Rn : 1) * 4, rb0 = W ? (size_t)(p.R ? p.R : 1) * 4 : rb1;
+	return build_reserve(ctx, G, rb0, rb1, Rn);
+}
+
+static int plan_async(ugrt_ctx *ctx, BuildPlan &p)
+{
+	Grid &G = *p.G;
 	const int gi = (int)(&G - ctx->grid);
 	int rc;
-	G.valid = false;
-	G.C = C;
-	G.F = F;
-	ugrt_prof_begin(ctx, UGRT_ST_BUILD_SCAN);
-	rc = ugrt_prim_inclusive_scan(ctx, (const u32 *)G.sizes.p, (u32 *)G.scan.p, (size_t)F);
-	ugrt_prof_end(ctx, UGRT_ST_BUILD_SCAN);
-	if (rc)
-		return rc;
 	// capacities: the last known need of this grid + a quarter; the wide list goes through the rank kernel
-	const unsigned long long active = (unsigned long long)(C / ((u32)ny * (u32)nz)) * (u32)(yhi - ylo + 1) * (u32)nz;
 	const u32 estRn = G.est_rn, estW = G.est_w;
 	// A grid that had no wide triangle in its last build (the light grid and the uniform grid of the bench scene) is
 	// built for none: the sorted references are the final lists, so the rank kernel and the two merge kernels (for
@@ -700,7 +740,7 @@ static int build_async_begin(ugrt_ctx *ctx, AsyncBuild &b)
 	u32 capRn = estRn + estRn / 4u + 65536u, capW = no_wide ? 0u : estW + estW / 4u + 16u;
 	if (capW > 4096u)
 		capW = 4096u;
-	unsigned long long capR = (unsigned long long)capRn + active * capW;
+	unsigned long long capR = (unsigned long long)capRn + p.active * capW;
 	if (capR > 0xFFFFFFF0ull)
 		capR = 0xFFFFFFF0ull;
 	// never shrink below what the buffers already hold: a grow-only arena
@@ -708,10 +748,7 @@ static int build_async_begin(ugrt_ctx *ctx, AsyncBuild &b)
 		capRn = (u32)(G.key[1].cap / 4);
 	if (capR * 4 < G.key[0].cap)
 		capR = G.key[0].cap / 4 < 0xFFFFFFF0ull ? G.key[0].cap / 4 : 0xFFFFFFF0ull;
-	if ((rc = ugrt_buf_reserve(ctx, G.key[0], (size_t)capR * 4)) || (rc = ugrt_buf_reserve(ctx, G.val[0], (size_t)capR * 4)) ||
-	    (rc = ugrt_buf_reserve(ctx, G.key[1], (size_t)capRn * 4)) || (rc = ugrt_buf_reserve(ctx, G.val[1], (size_t)capRn * 4)) ||
-	    (rc = ugrt_buf_reserve(ctx, G.parts, ((size_t)capRn / BUILD_THREADS + 2) * 4)) ||
-	    (rc = ugrt_buf_reserve(ctx, G.span, (size_t)C * 8 + 16)) || (rc = ugrt_buf_reserve(ctx, G.offset, (size_t)C * 4)))
+	if ((rc = build_reserve(ctx, G, (size_t)capR * 4, (size_t)capRn * 4, capRn)))
 		return rc;
 	// the capacities actually available (buffers may be larger than asked for)
 	capRn = (u32)((G.key[1].cap < G.val[1].cap ? G.key[1].cap : G.val[1].cap) / 4 < 0xFFFFFFF0ull
@@ -721,140 +758,150 @@ static int build_async_begin(ugrt_ctx *ctx, AsyncBuild &b)
 	capR = (G.key[0].cap < G.val[0].cap ? G.key[0].cap : G.val[0].cap) / 4;
 	if (capR > 0xFFFFFFF0ull)
 		capR = 0xFFFFFFF0ull;
-	u32 *k0 = (u32 *)G.key[0].p, *v0 = (u32 *)G.val[0].p;
-	u32 *rw = ctx->d_small + UGRT_DSMALL_RW + 2 * gi, *status = ctx->d_small + UGRT_DSMALL_STATUS;
-	// (written by the build's kernels straight into the pinned host words: no copy behind the build)
-	u32 *report = ctx->h_pinned + UGRT_PIN_REPORT + 4 * gi;
-	// launch sizes: the estimate plus the margin (every kernel stops at the real count).  The check below is made
+	// launch sizes: the estimate plus the margin (every kernel stops at the real count).  k_fill_parts checks the counts
 	// against THIS size, not against the (larger, grow-only) buffers: fill, sort, bounds and merge run one thread per
 	// reference of the launch, so a count between the two would leave references unfilled and unsorted.
-	const u32 launchRn = estRn + estRn / 4u + 65536u < capRn ? estRn + estRn / 4u + 65536u : capRn;
-	BuildCheck chk = { (const u32 *)G.scan.p + (F - 1), launchRn, capW, capR, active, rw, status, report };
-	const u32 nparts = (launchRn + BUILD_THREADS - 1) / BUILD_THREADS;
-	ugrt_prof_begin(ctx, UGRT_ST_BUILD_FILL);
-	hipLaunchKernelGGL(k_fill_parts, dim3((nparts + BUILD_THREADS) / BUILD_THREADS), dim3(BUILD_THREADS), 0, st,
-			   (const u32 *)G.scan.p, F, 0u, 0u, (u32 *)G.parts.p, chk);
+	p.Rn = estRn + estRn / 4u + 65536u < capRn ? estRn + estRn / 4u + 65536u : capRn;
+	p.W = capW, p.R = (u32)capR;
+	p.rw = ctx->d_small + UGRT_DSMALL_RW + 2 * gi;
+	// (written by the build's kernels straight into the pinned host words: no copy behind the build)
+	p.report = ctx->h_pinned + UGRT_PIN_REPORT + 4 * gi;
+	p.status = ctx->d_small + UGRT_DSMALL_STATUS;
+	p.no_wide = no_wide;
+	p.own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1;
 	// the fill counts the first digit of its keys for the build's own sort, unless that sort shares its launches with
 	// another build's (ugrt_grid_build_batch_begin: the lists of a batch are counted by one histogram kernel)
-	RsFirst hs = { nullptr };
-	if (ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1 && !ctx->batch_open && (rc = ugrt_sort_first_digit(ctx, &hs)))
-		return rc;
-	b.prehist = hs.hist != nullptr;
-	const u32 fill_blocks = hs.hist ? FILL_MAX_BLOCKS_COUNTING : FILL_MAX_BLOCKS;
-	hipLaunchKernelGGL(k_fill, dim3(nparts < fill_blocks ? nparts : fill_blocks), dim3(BUILD_THREADS), 0, st,
-			   (const u32 *)G.scan.p, (const Rng *)G.rng.p, (const u32 *)G.parts.p, 0u, ny, nz, k0, v0, (u32 *)G.span.p,
-			   2u * C + 1u, (const u32 *)rw, hs);
-	ugrt_prof_end(ctx, UGRT_ST_BUILD_FILL);
-	UGRT_HIP(hipGetLastError());
-	b.launchRn = launchRn, b.capW = capW, b.capR = capR, b.active = active, b.no_wide = no_wide, b.nparts = nparts;
+	p.prehist = p.own_sort && !ctx->batch_open;
 	return UGRT_OK;
 }
 
-// the sort of one or two begun builds, in shared launches
-static int build_async_sort(ugrt_ctx *ctx, AsyncBuild *b, int n)
+static inline u32 build_parts(const BuildPlan &p) { return (p.Rn + BUILD_THREADS - 1) / BUILD_THREADS; }
+
+// (the launches for the narrow references are skipped when there are none: only a waiting build can know that, the launch
+// size of an asynchronous one is never zero)
+static int build_fill(ugrt_ctx *ctx, const BuildPlan &p)
 {
-	int rc = UGRT_OK;
-	const bool own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1;
-	ugrt_prof_begin(ctx, UGRT_ST_BUILD_SORT);
-	RsJob jobs[2];
-	for (int i = 0; i < n; i++) {
-		Grid &G = *b[i].G;
-		const int gi = (int)(&G - ctx->grid);
-		jobs[i] = RsJob{ (const u32 *)G.key[0].p, (const u32 *)G.val[0].p, (u32 *)G.key[1].p, (u32 *)G.val[1].p, b[i].launchRn,
-				 bits_for(b[i].C), (const u32 *)(ctx->d_small + UGRT_DSMALL_RW + 2 * gi) };
-	}
-	if (own_sort) {
-		rc = ugrt_sort_pairs_batch(ctx, jobs, n, n == 1 && b[0].prehist);
-	} else {
-		for (int i = 0; i < n && !rc; i++)
-			rc = ugrt_prim_sort_pairs(ctx, jobs[i].kin, jobs[i].kout, jobs[i].vin, jobs[i].vout, jobs[i].n, jobs[i].end_bit, jobs[i].n_dev);
-	}
-	if (rc)
+	if (!p.Rn)
+		return UGRT_OK;
+	Grid &G = *p.G;
+	hipStream_t st = ctx->stream;
+	int rc;
+	const u32 nparts = build_parts(p);
+	const BuildCheck chk = { p.rw ? (const u32 *)G.scan.p + (p.F - 1) : nullptr, p.Rn, p.W, p.R, p.active, p.rw, p.status, p.report };
+	ugrt_prof_begin(ctx, UGRT_ST_BUILD_FILL);
+	hipLaunchKernelGGL(k_fill_parts, dim3((nparts + BUILD_THREADS) / BUILD_THREADS), dim3(BUILD_THREADS), 0, st,
+			   (const u32 *)G.scan.p, p.F, p.Rn, nparts, (u32 *)G.parts.p, chk);
+	RsFirst hs = { nullptr };
+	if (p.prehist && (rc = ugrt_sort_first_digit(ctx, &hs)))
 		return rc;
+	const u32 fill_blocks = hs.hist ? FILL_MAX_BLOCKS_COUNTING : FILL_MAX_BLOCKS;
+	hipLaunchKernelGGL(k_fill, dim3(nparts < fill_blocks ? nparts : fill_blocks), dim3(BUILD_THREADS), 0, st,
+			   (const u32 *)G.scan.p, (const Rng *)G.rng.p, (const u32 *)G.parts.p, p.Rn, p.ny, p.nz, (u32 *)G.key[0].p,
+			   (u32 *)G.val[0].p, (u32 *)G.span.p, 2u * p.C + 1u, (const u32 *)p.rw, hs);
+	ugrt_prof_end(ctx, UGRT_ST_BUILD_FILL);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+// the sorts of one build, or of the builds of a batch in shared launches; then the order of their wide triangles
+static int build_sort(ugrt_ctx *ctx, const BuildPlan *b, int n)
+{
+	int rc;
+	const bool narrow = b[0].Rn != 0u; // (the builds of a batch are asynchronous: their launch sizes are never zero)
+	if (!narrow && b[0].no_wide)
+		return UGRT_OK;
+	ugrt_prof_begin(ctx, UGRT_ST_BUILD_SORT);
+	if (narrow) {
+		RsJob jobs[2];
+		for (int i = 0; i < n; i++) {
+			Grid &G = *b[i].G;
+			jobs[i] = RsJob{ (const u32 *)G.key[0].p, (const u32 *)G.val[0].p, (u32 *)G.key[1].p, (u32 *)G.val[1].p, b[i].Rn,
+					 bits_for(b[i].C), (const u32 *)b[i].rw };
+		}
+		if (b[0].own_sort) {
+			rc = ugrt_sort_pairs_batch(ctx, jobs, n, n == 1 && b[0].prehist);
+		} else {
+			rc = UGRT_OK;
+			for (int i = 0; i < n && !rc; i++)
+				rc = ugrt_prim_sort_pairs(ctx, jobs[i].kin, jobs[i].kout, jobs[i].vin, jobs[i].vout, jobs[i].n, jobs[i].end_bit, jobs[i].n_dev);
+		}
+		if (rc)
+			return rc;
+	}
 	for (int i = 0; i < n; i++) {
-		Grid &G = *b[i].G;
-		const int gi = (int)(&G - ctx->grid);
-		if (!b[i].no_wide)
-			hipLaunchKernelGGL(k_wide_rank, dim3((b[i].capW + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS), 0, ctx->stream,
-					   (const u32 *)G.wide.p, 0u, (u32 *)G.wide.p + b[i].F, (const u32 *)(ctx->d_small + UGRT_DSMALL_RW + 2 * gi));
+		const BuildPlan &p = b[i];
+		u32 *wl = (u32 *)p.G->wide.p, *wsorted = wl + p.F;
+		if (p.no_wide)
+			continue;
+		if (p.W > 4096u) {
+			// many wide triangles (a tiny grid, and a waiting build): radix sort of the ids, the values are not used
+			if ((rc = ugrt_prim_sort_pairs(ctx, wl, wsorted, wl, (u32 *)p.G->sizes.p, p.W, bits_for((u32)p.F))))
+				return rc;
+			continue;
+		}
+		hipLaunchKernelGGL(k_wide_rank, dim3((p.W + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS), 0, ctx->stream,
+				   (const u32 *)wl, p.W, wsorted, (const u32 *)p.rw);
 	}
 	ugrt_prof_end(ctx, UGRT_ST_BUILD_SORT);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
 }
 
-static int build_async_end(ugrt_ctx *ctx, AsyncBuild &b)
+static int build_finish(ugrt_ctx *ctx, const BuildPlan &p)
 {
-	Grid &G = *b.G;
-	const int F = b.F;
-	const u32 C = b.C;
+	Grid &G = *p.G;
+	const u32 C = p.C;
 	hipStream_t st = ctx->stream;
-	const int gi = (int)(&G - ctx->grid);
 	int rc;
 	u32 *k0 = (u32 *)G.key[0].p, *k1 = (u32 *)G.key[1].p, *v0 = (u32 *)G.val[0].p, *v1 = (u32 *)G.val[1].p;
-	u32 *wsorted = (u32 *)G.wide.p + F;
-	u32 *rw = ctx->d_small + UGRT_DSMALL_RW + 2 * gi, *status = ctx->d_small + UGRT_DSMALL_STATUS;
-	u32 *report = ctx->h_pinned + UGRT_PIN_REPORT + 4 * gi;
-	const bool no_wide = b.no_wide;
-	WideBox wb;
-	wb.W = 0;
-	wb.ny = (u32)b.ny;
-	wb.nz = (u32)b.nz;
-	wb.ylo = (u32)b.ylo;
-	wb.yhi = (u32)b.yhi;
-	wb.rw = rw;
-	const u32 nparts = b.nparts;
-	ugrt_prof_begin(ctx, UGRT_ST_BUILD_BOUNDS);
+	u32 *wsorted = (u32 *)G.wide.p + p.F;
 	u32 *cstart = (u32 *)G.span.p + C, *used = cstart + C;
-	hipLaunchKernelGGL(k_bounds, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, 0u, cstart, (u32 *)G.span.p,
-			   (const u32 *)rw);
-	// spans + offsets in one kernel; a grid without wide triangles ends its report there (with them: k_merge_wide)
+	u32 *report_tail = p.report ? p.report + 2 : nullptr;
+	const WideBox wb = { p.W, (u32)p.ny, (u32)p.nz, (u32)p.ylo, (u32)p.yhi, p.rw };
+	const u32 nparts = build_parts(p);
+	ugrt_prof_begin(ctx, UGRT_ST_BUILD_BOUNDS);
+	if (p.Rn)
+		hipLaunchKernelGGL(k_bounds, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, p.Rn, cstart, (u32 *)G.span.p,
+				   (const u32 *)p.rw);
+	else
+		UGRT_HIP(hipMemsetAsync(G.span.p, 0, (size_t)C * 8 + 4, st)); // (otherwise cleared by k_fill)
+	// spans + offsets in one kernel (an empty build: the cleared words are the spans); an asynchronous build without
+	// wide triangles ends its report there (with them: k_merge_wide)
 	{
 		SpanLoad sl = { (const u32 *)cstart, (u32 *)G.span.p, used, wb };
-		SpanTail tl = { no_wide ? report + 2 : (u32 *)nullptr, (const u32 *)used, (const u32 *)status, wide_counter(G, F) };
+		SpanTail tl = { p.no_wide ? report_tail : (u32 *)nullptr, (const u32 *)used, (const u32 *)p.status, wide_counter(G, p.F) };
 		if ((rc = ugrt_scan_launch<false>(ctx, sl, (u32 *)G.offset.p, (size_t)C, tl)))
 			return rc;
-		G.wide_zeroed = wide_counter(G, F);
+		G.wide_zeroed = wide_counter(G, p.F);
 	}
-	if (no_wide) {
+	if (p.no_wide) {
 		G.keys = k1;
 		G.vals = v1;
 	} else {
 		// the merged lists go to key[0]/val[0]
-		hipLaunchKernelGGL(k_merge_narrow, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, (const u32 *)v1, 0u,
-				   (const u32 *)cstart, (const u32 *)G.offset.p, (const u32 *)wsorted, wb, k0, v0);
+		if (p.Rn)
+			hipLaunchKernelGGL(k_merge_narrow, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, (const u32 *)v1, p.Rn,
+					   (const u32 *)cstart, (const u32 *)G.offset.p, (const u32 *)wsorted, wb, k0, v0);
 		u32 blocks = C < 256u * 32u ? C : 256u * 32u;
 		hipLaunchKernelGGL(k_merge_wide, dim3(blocks), dim3(64), 0, st, (const u32 *)v1, (const u32 *)cstart,
-				   (const u32 *)G.span.p, (const u32 *)G.offset.p, (const u32 *)wsorted, C, wb, k0, v0, report + 2,
-				   (const u32 *)used, (const u32 *)status);
+				   (const u32 *)G.span.p, (const u32 *)G.offset.p, (const u32 *)wsorted, C, wb, k0, v0, report_tail,
+				   (const u32 *)used, (const u32 *)p.status);
 		G.keys = k0;
 		G.vals = v0;
 	}
 	UGRT_HIP(hipGetLastError());
 	ugrt_prof_end(ctx, UGRT_ST_BUILD_BOUNDS);
-	G.R = no_wide ? b.launchRn : (u32)b.capR; // an upper bound; the exact count is in the pinned report words once the stream has got here
-	G.r_exact = false;
-	G.active_cells = b.active;
-	G.async_pending = true;
+	if (p.rw) {
+		G.R = p.no_wide ? p.Rn : p.R; // an upper bound; the exact count is in the pinned report words once the stream has got here
+		G.r_exact = false;
+		G.active_cells = p.active;
+		G.async_pending = true;
+	} else {
+		// "Number of actual cells" (frustum_grid.h:337): fetched lazily by ugrt_grid_get_info
+		UGRT_HIP(hipMemcpyAsync(ctx->h_pinned + UGRT_PIN_CELLS_USED + (&G - ctx->grid), used, 4, hipMemcpyDeviceToHost, st));
+	}
 	G.valid = true;
 	return UGRT_OK;
-}
-
-static int build_common_async(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, int ylo, int yhi)
-{
-	AsyncBuild b = {};
-	b.G = &G, b.F = F, b.C = C, b.ny = ny, b.nz = nz, b.ylo = ylo, b.yhi = yhi;
-	int rc = build_async_begin(ctx, b);
-	if (rc)
-		return rc;
-	// inside ugrt_grid_build_batch_begin / _end the build stops here: its sort shares its launches with the next build's
-	if (ctx->batch_open && ctx->nbatch < 2) {
-		ctx->batch[ctx->nbatch++] = b;
-		return UGRT_OK;
-	}
-	if ((rc = build_async_sort(ctx, &b, 1)))
-		return rc;
-	return build_async_end(ctx, b);
 }
 
 // Two grid builds that depend on the geometry only (the light grid and the uniform grid of a frame) between
@@ -885,31 +932,30 @@ extern "C" int ugrt_grid_build_batch_end(ugrt_ctx *ctx)
 	if (n == 0)
 		return UGRT_OK;
 	UGRT_HIP(hipSetDevice(ctx->device));
-	int rc = build_async_sort(ctx, ctx->batch, n);
+	int rc = build_sort(ctx, ctx->batch, n);
 	for (int i = 0; i < n && !rc; i++)
-		rc = build_async_end(ctx, ctx->batch[i]);
+		rc = build_finish(ctx, ctx->batch[i]);
 	return rc;
 }
 
-// shared tail of the three builders: sizes/rng/wide list are filled, ny/nz give the key layout,
-// [ylo, yhi] the y range of the cells a wide triangle covers
+// sizes/rng/wide list are filled, ny/nz give the key layout, [ylo, yhi] the y range of the cells a wide triangle covers
 static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, int ylo, int yhi)
 {
-	hipStream_t st = ctx->stream;
 	int rc;
-	const int gidx = (int)(&G - ctx->grid);
+	const int gi = (int)(&G - ctx->grid);
 	if (G.async_pending) { // what the previous asynchronous build of this grid reported (possibly a frame old)
-		G.est_rn = ctx->h_pinned[UGRT_PIN_REPORT + 4 * gidx];
-		G.est_w = ctx->h_pinned[UGRT_PIN_REPORT + 4 * gidx + 1];
+		G.est_rn = ctx->h_pinned[UGRT_PIN_REPORT + 4 * gi];
+		G.est_w = ctx->h_pinned[UGRT_PIN_REPORT + 4 * gi + 1];
 	}
 	// asynchronous when asked for, when this grid has been built before (an estimate exists), when no overflow is
 	// pending, and when the wide list fits the rank kernel
-	if (ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && G.have_est && G.est_w <= 3000u && ctx->cfg.slabs == 1 &&
-	    ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen)
-		return build_common_async(ctx, G, F, C, ny, nz, ylo, yhi);
-	if (ugrt_reported_status(ctx) != 0u)
-		ctx->overflow_seen = true; // reported by ugrt_ctx_synchronize; until then every call waits and sizes exactly
-	G.async_pending = false;
+	const bool async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && G.have_est && G.est_w <= 3000u && ctx->cfg.slabs == 1 &&
+			   ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen;
+	if (!async) {
+		if (ugrt_reported_status(ctx) != 0u)
+			ctx->overflow_seen = true; // reported by ugrt_ctx_synchronize; until then every call waits and sizes exactly
+		G.async_pending = false;
+	}
 	G.valid = false;
 	G.C = C;
 	G.F = F;
@@ -918,121 +964,20 @@ static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, in
 	ugrt_prof_end(ctx, UGRT_ST_BUILD_SCAN);
 	if (rc)
 		return rc;
-	// total_triangles, frustum_grid.h:254 (the one unavoidable read-back: it sizes the lists), here
-	// as narrow references + number of wide triangles
-	UGRT_HIP(hipMemcpyAsync(ctx->h_pinned + UGRT_PIN_RW, (u32 *)G.scan.p + (F - 1), 8, hipMemcpyDeviceToHost, st));
-	UGRT_HIP(hipStreamSynchronize(st));
-	const u32 Rn = ctx->h_pinned[UGRT_PIN_RW], W = ctx->h_pinned[UGRT_PIN_RW + 1];
-	WideBox wb;
-	wb.W = W;
-	wb.ny = (u32)ny;
-	wb.nz = (u32)nz;
-	wb.ylo = (u32)ylo;
-	wb.yhi = (u32)yhi;
-	wb.rw = nullptr;
-	const unsigned long long active = (unsigned long long)(C / ((u32)ny * (u32)nz)) * (u32)(yhi - ylo + 1) * (u32)nz;
-	const unsigned long long Rtot = (unsigned long long)Rn + active * W;
-	if (Rtot > 0xFFFFFFF0ull)
-		return ugrt_fail(UGRT_ENOMEM, "grid build: %llu references exceed the 32-bit lists", Rtot);
-	const u32 R = (u32)Rtot;
-	G.R = R;
-	G.r_exact = true;
-	G.est_rn = Rn;
-	G.est_w = W;
-	G.have_est = true;
-	// (the slots an asynchronous build reports into: never older than this build)
-	ctx->h_pinned[UGRT_PIN_REPORT + 4 * gidx] = Rn;
-	ctx->h_pinned[UGRT_PIN_REPORT + 4 * gidx + 1] = W;
-	// the sort goes key[0] -> key[1]; with wide triangles the merged lists are written back into key[0]
-	size_t rb1 = (size_t)(Rn ? Rn : 1) * 4, rb0 = W ? (size_t)(R ? R : 1) * 4 : rb1;
-	if ((rc = ugrt_buf_reserve(ctx, G.key[0], rb0)) || (rc = ugrt_buf_reserve(ctx, G.val[0], rb0)) ||
-	    (rc = ugrt_buf_reserve(ctx, G.key[1], rb1)) || (rc = ugrt_buf_reserve(ctx, G.val[1], rb1)))
+	BuildPlan p = {};
+	p.G = &G, p.F = F, p.C = C, p.ny = ny, p.nz = nz, p.ylo = ylo, p.yhi = yhi;
+	p.active = (unsigned long long)(C / ((u32)ny * (u32)nz)) * (u32)(yhi - ylo + 1) * (u32)nz;
+	if ((rc = async ? plan_async(ctx, p) : plan_waiting(ctx, p)) || (rc = build_fill(ctx, p)))
 		return rc;
-	if ((rc = ugrt_buf_reserve(ctx, G.parts, ((size_t)Rn / BUILD_THREADS + 2) * 4))) // first triangle per fill workgroup
+	// inside ugrt_grid_build_batch_begin / _end an asynchronous build stops here: its sort shares its launches with the
+	// next build's (a waiting build is built at once)
+	if (async && ctx->batch_open && ctx->nbatch < 2) {
+		ctx->batch[ctx->nbatch++] = p;
+		return UGRT_OK;
+	}
+	if ((rc = build_sort(ctx, &p, 1)))
 		return rc;
-	if ((rc = ugrt_buf_reserve(ctx, G.span, (size_t)C * 8 + 16))) // span[C], run starts[C], cells_used
-		return rc;
-	if ((rc = ugrt_buf_reserve(ctx, G.offset, (size_t)C * 4)))
-		return rc;
-	u32 *k0 = (u32 *)G.key[0].p, *k1 = (u32 *)G.key[1].p, *v0 = (u32 *)G.val[0].p, *v1 = (u32 *)G.val[1].p;
-	u32 *wl = (u32 *)G.wide.p, *wsorted = wl + F;
-	if (Rn) {
-		ugrt_prof_begin(ctx, UGRT_ST_BUILD_FILL);
-		const u32 nparts = (Rn + BUILD_THREADS - 1) / BUILD_THREADS;
-		hipLaunchKernelGGL(k_fill_parts, dim3((nparts + BUILD_THREADS) / BUILD_THREADS), dim3(BUILD_THREADS), 0, st,
-				   (const u32 *)G.scan.p, F, Rn, nparts, (u32 *)G.parts.p, BuildCheck{ nullptr, 0u, 0u, 0ull, 0ull, nullptr, nullptr, nullptr });
-		const bool own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1 && Rn <= (1u << 30);
-		RsFirst hs = { nullptr }; // the fill counts the first digit of its keys for the sort
-		if (own_sort && (rc = ugrt_sort_first_digit(ctx, &hs)))
-			return rc;
-		const u32 fill_blocks = hs.hist ? FILL_MAX_BLOCKS_COUNTING : FILL_MAX_BLOCKS;
-		hipLaunchKernelGGL(k_fill, dim3(nparts < fill_blocks ? nparts : fill_blocks), dim3(BUILD_THREADS), 0, st,
-				   (const u32 *)G.scan.p, (const Rng *)G.rng.p, (const u32 *)G.parts.p, Rn, ny, nz, k0, v0,
-				   (u32 *)G.span.p, 2u * C + 1u, (const u32 *)nullptr, hs);
-		ugrt_prof_end(ctx, UGRT_ST_BUILD_FILL);
-		UGRT_HIP(hipGetLastError());
-		ugrt_prof_begin(ctx, UGRT_ST_BUILD_SORT);
-		rc = own_sort ? ugrt_sort_pairs_u32(ctx, k0, k1, v0, v1, Rn, bits_for(C), nullptr, true)
-			      : ugrt_prim_sort_pairs(ctx, k0, k1, v0, v1, Rn, bits_for(C));
-		ugrt_prof_end(ctx, UGRT_ST_BUILD_SORT);
-		if (rc)
-			return rc;
-	}
-	if (W) {
-		ugrt_prof_begin(ctx, UGRT_ST_BUILD_SORT);
-		if (W <= 4096u) {
-			hipLaunchKernelGGL(k_wide_rank, dim3((W + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS), 0,
-					   st, (const u32 *)wl, W, wsorted, (const u32 *)nullptr);
-			UGRT_HIP(hipGetLastError());
-		} else {
-			// many wide triangles (a tiny grid): radix sort of the ids, the values are not used
-			if ((rc = ugrt_prim_sort_pairs(ctx, wl, wsorted, wl, (u32 *)G.sizes.p, W, bits_for((u32)F))))
-				return rc;
-		}
-		ugrt_prof_end(ctx, UGRT_ST_BUILD_SORT);
-	}
-	ugrt_prof_begin(ctx, UGRT_ST_BUILD_BOUNDS);
-	u32 *cstart = (u32 *)G.span.p + C, *used = cstart + C;
-	if (!Rn)
-		UGRT_HIP(hipMemsetAsync(G.span.p, 0, (size_t)C * 8 + 4, st)); // (otherwise cleared by k_fill)
-	if (R) {
-		if (Rn) {
-			hipLaunchKernelGGL(k_bounds, dim3((Rn + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS), 0,
-					   st, (const u32 *)k1, Rn, cstart, (u32 *)G.span.p, (const u32 *)nullptr);
-			UGRT_HIP(hipGetLastError());
-		}
-	}
-	{
-		// spans + offsets in one kernel (an empty build: the cleared words are the spans)
-		SpanLoad sl = { (const u32 *)cstart, (u32 *)G.span.p, used, wb };
-		SpanTail tl = { (u32 *)nullptr, (const u32 *)used, (const u32 *)nullptr, wide_counter(G, F) };
-		if ((rc = ugrt_scan_launch<false>(ctx, sl, (u32 *)G.offset.p, (size_t)C, tl)))
-			return rc;
-		G.wide_zeroed = wide_counter(G, F);
-	}
-	if (W) {
-		if (Rn) {
-			hipLaunchKernelGGL(k_merge_narrow, dim3((Rn + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS),
-					   0, st, (const u32 *)k1, (const u32 *)v1, Rn, (const u32 *)cstart,
-					   (const u32 *)G.offset.p, (const u32 *)wsorted, wb, k0, v0);
-			UGRT_HIP(hipGetLastError());
-		}
-		u32 blocks = C < 256u * 32u ? C : 256u * 32u;
-		hipLaunchKernelGGL(k_merge_wide, dim3(blocks), dim3(64), 0, st, (const u32 *)v1, (const u32 *)cstart,
-				   (const u32 *)G.span.p, (const u32 *)G.offset.p, (const u32 *)wsorted, C, wb, k0, v0,
-				   (u32 *)nullptr, (const u32 *)nullptr, (const u32 *)nullptr);
-		UGRT_HIP(hipGetLastError());
-		G.keys = k0;
-		G.vals = v0;
-	} else {
-		G.keys = k1;
-		G.vals = v1;
-	}
-	ugrt_prof_end(ctx, UGRT_ST_BUILD_BOUNDS);
-	// "Number of actual cells" (frustum_grid.h:337): fetched lazily by ugrt_grid_get_info
-	UGRT_HIP(hipMemcpyAsync(ctx->h_pinned + UGRT_PIN_CELLS_USED + (&G - ctx->grid), used, 4, hipMemcpyDeviceToHost, st));
-	G.valid = true;
-	return UGRT_OK;
+	return build_finish(ctx, p);
 }
 
 static int build_prologue(ugrt_ctx *ctx, Grid &G, const int *d_facelist, const float *d_vertlist, int F,

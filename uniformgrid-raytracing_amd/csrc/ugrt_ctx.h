@@ -82,7 +82,6 @@ struct Grid {
 
 // layout of ugrt_ctx::d_small (u32 words of device scratch)
 #define UGRT_DSMALL_DDA_RAYS 2     // secondary rays in the DDA's ray list
-#define UGRT_DSMALL_WIDE 3         // wide triangles of the running build
 #define UGRT_DSMALL_DDA_RAYS_B 4   // the DDA's other ray counter (two in turn: a launch clears the next one's)
 #define UGRT_DSMALL_TICKET 8       // group ticket of the beam DDA
 #define UGRT_DSMALL_STATUS 14      // status bits of asynchronous calls
@@ -91,8 +90,6 @@ struct Grid {
 #define UGRT_DSMALL_TEX 32         // [100] the 5x5x4 direction table
 #define UGRT_DSMALL_DDA 132        // u64 [UGRT_DDA_STATS] work counters of the DDA
 #define UGRT_DSMALL_RW 236         // [3][2] checked {narrow references, wide triangles} of an asynchronous build
-#define UGRT_DSMALL_REPORT 242     // [3][4] report of a grid's asynchronous build: {narrow references, wide triangles} as
-                                   // found (what the next build is sized by), cells used, the status word at its end
 #define UGRT_DSMALL_SHADOW 254     // [10] shadow tracer: {pairs, beams} as checked, then its report: {pairs, beams} as
                                    // found, status word, pad, the two u64 work counters at the start of the exact pass
 #define UGRT_DSMALL_PRIMARY 264    // u64 [UGRT_PRIMARY_STATS] work counters of the primary tracer (FLAG_COUNT_WORK)
@@ -105,7 +102,9 @@ struct Grid {
 #define UGRT_PIN_CHUNKS 11      // chunks of ugrt_sort_rays
 #define UGRT_PIN_BEAMS 12       // beams of the shadow pass
 #define UGRT_PIN_SHADOW_WORK (UGRT_PIN_SHADOW + 4) // u64 [2]: cull tests, staged candidates
-#define UGRT_PIN_REPORT 32      // [3][4] copies of UGRT_DSMALL_REPORT (one copy per build)
+#define UGRT_PIN_REPORT 32      // [3][4] report of a grid's asynchronous build, written by its kernels straight into these
+                                // words: {narrow references, wide triangles} as found (what the next build is sized by),
+                                // cells used, the status word at its end
 #define UGRT_PIN_SHADOW 44      // [8] copy of the shadow tracer's report (UGRT_DSMALL_SHADOW + 2 ...)
 #define UGRT_PIN_WORDS 64
 #define UGRT_STATUS_BUILD_OVERFLOW 1u
@@ -114,16 +113,22 @@ struct Grid {
 #define UGRT_DDA_STATS 46
 #define UGRT_PRIMARY_STATS 16
 static_assert(UGRT_DSMALL_DDA + 2 * UGRT_DDA_STATS <= UGRT_DSMALL_RW, "the DDA's counters run into the build counts");
-static_assert(UGRT_DSMALL_REPORT + 12 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
+static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
 
-// an asynchronous grid build between its fill and its sort (ugrt_build.hip: build_async_begin / _sort / _end)
-struct AsyncBuild {
+// What the stages of a grid build (ugrt_build.hip: build_fill, build_sort, build_finish) need.  A waiting build has
+// read the counts back and holds them exactly; an asynchronous build holds the sizes its launches and buffers were
+// made for and `rw`, where its kernels find the counts.  The context keeps the plans of an open batch.
+struct BuildPlan {
 	Grid *G;
 	int F, ny, nz, ylo, yhi;
-	u32 C, launchRn, capW, nparts;
-	unsigned long long capR, active;
-	bool no_wide;
-	bool prehist; // the fill has counted the first digit of the keys for the sort (ugrt_rs_hist.h)
+	u32 C;
+	unsigned long long active; // cells that hold every wide triangle
+	u32 Rn, W, R;              // narrow references, wide triangles, all references: the counts, or (rw) their caps
+	u32 *rw;                   // {narrow references, wide triangles} on the device; nullptr = the host knows them
+	u32 *report, *status;      // asynchronous build: its four report words (UGRT_PIN_REPORT), the device's status word
+	bool no_wide;              // no wide triangle (or: built for none), the sorted references are the final lists
+	bool own_sort;             // the built-in radix sort, not the library's
+	bool prehist;              // the fill counts the first digit of the keys for the sort (ugrt_rs_hist.h)
 };
 
 struct ProfPair {
@@ -149,7 +154,7 @@ struct ugrt_ctx {
 	u32 rs_epoch = 0;             // tag of the last pass's look-back words
 	bool batch_open = false;      // ugrt_grid_build_batch_begin: the builds that follow stop in front of their sorts
 	int nbatch = 0;
-	AsyncBuild batch[2];
+	BuildPlan batch[2];
 	unsigned long long rs_launches = 0; // histogram + pass kernels enqueued so far (ugrt_ctx_get_state "radix_launches")
 	bool rs_prehist = false;      // the first pass's histogram rows hold the counts of a producer whose sort has not run yet
 	int rs_atomic_rank = -1;      // k_rs_selftest: 1 = LDS add-with-return serves equal addresses in lane order on this device
@@ -215,7 +220,6 @@ static inline u32 ugrt_reported_status(const ugrt_ctx *ctx)
 	const u32 *p = ctx->h_pinned;
 	return p[UGRT_PIN_REPORT + 3] | p[UGRT_PIN_REPORT + 7] | p[UGRT_PIN_REPORT + 11] | p[UGRT_PIN_SHADOW + 2];
 }
-static inline u32 *ugrt_wide_counter(ugrt_ctx *ctx) { return ctx->d_small + UGRT_DSMALL_WIDE; }
 void ugrt_prof_begin(ugrt_ctx *ctx, int stage);
 void ugrt_prof_end(ugrt_ctx *ctx, int stage);
 
