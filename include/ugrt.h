@@ -209,6 +209,7 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * one, "sort_items" 8 / 16 pairs per thread of a radix pass (default: by size), "sort_rank" 0 = the passes rank by
  * ballots instead of LDS atomics, "ray_sort" 1 = the deferred ugrt_sort_rays sorts at once also where nothing needs it
  * (see there); "dda_blocks", "primary_waves",
+ * "any_rays_per_wave", "any_coop": ugrt_trace_dda_any (see there);
  * "shadow_waves": number of persistent single-wave workgroups of the bounce, the primary tracer and the two
  * shadow kernels (the primary tracer and the exact shadow pass run one wave per work item by default, "primary_xcd_run" /
  * "shadow_xcd_run" neighbouring items per XCD in turn; "primary_waves" set / "shadow_xcd_run" 0 restore their persistent
@@ -368,6 +369,43 @@ int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d
 			     const int *d_mat_idx, const float *d_mat_list, const float *d_reflect,
 			     int num_materials, const float *d_vertlist, const int *d_trilist, int depth,
 			     const float *d_rays, const int *d_active, const float *d_hit_t, const int *d_hit_id);
+
+/* ---- device: shadows on reflected hits -----------
+ * The hits of the reflection levels 1..D are tested against the light: per level ugrt_occlusion_rays +
+ * ugrt_trace_dda_any behind the level's ugrt_trace_dda, then ugrt_shade_reflect_depth_occluded instead of
+ * ugrt_shade_reflect_depth.  The occlusion flags of the levels are stacked like d_active. */
+/* Occlusion rays from one level's hits, for the context's band: for a pixel with d_active[p], d_hit_t[p] > 0 and
+ * d_hit_id[p] >= 0 (whatever the hit's material), o' = the origin ugrt_reflect_rays_next gives the next ray
+ * (P = o + t*d, n = normalize(e1 x e2) turned so that d.n <= 0, o' = P + eps*n), ray {o', light_pos - o'} (not
+ * normalised: the light lies at t = 1) and d_oactive[p] = 1; every other pixel: six zeros and 0.  light_pos is host
+ * memory and is passed on by value.  Stage UGRT_ST_REFLECT_GEN.  Unlike ugrt_reflect_rays_next the call says nothing
+ * to the ugrt_trace_dda that follows. */
+int ugrt_occlusion_rays(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+			const int *d_hit_id, const float *d_vertlist, const int *d_trilist, const float light_pos[3],
+			float eps, float *d_orays, int *d_oactive);
+/* Any-hit traversal of the context's uniform grid: d_occluded[p] = 1 for an active pixel of the band iff a triangle
+ * in the list of a VISITED cell passes ugrt_trace_dda's exact test with 0 < t < t_max (both strict), else 0.  The
+ * visited cells are those of ugrt_trace_dda's walk (same clip, entry cell, stepping and guard), from the entry cell on
+ * for as long as a cell's entry parameter -- the entry into the grid, then the exit parameter of the cell before -- is
+ * below t_max; a hit need not lie inside the cell whose list holds it.  Inactive pixels of the band get 0, pixels
+ * outside it are not written.  t_max <= 0 or NaN, or a null argument: UGRT_EINVAL; without a built uniform grid the
+ * error of ugrt_trace_dda.  Options "any_rays_per_wave" 1..64 (0 = default: 32) and "any_coop" (list length from which
+ * a ray's cell is tested by the whole wave, default 8) shape the launch, "dda_blocks" caps its waves; none changes a
+ * result.  Stages UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of ugrt_trace_dda
+ * (option "dda_split") and what ugrt_reflect_rays_next told it alone. */
+int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+		       const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_rays,
+		       const int *d_active, float t_max, int *d_occluded);
+/* ugrt_shade_reflect_depth with shadowed levels: where d_occluded (levels 1..depth stacked like d_active) is 1, the
+ * clamped colour L_j of level j >= 1 becomes L_j / 3.0f per component before the level is weighted.  The primary
+ * level and ugrt_shade_add_shadows are untouched; with d_occluded all zero the image is ugrt_shade_reflect_depth's
+ * byte for byte.  A null d_occluded: UGRT_EINVAL. */
+int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
+				      const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+				      const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+				      const float *d_reflect, int num_materials, const float *d_vertlist,
+				      const int *d_trilist, int depth, const float *d_rays, const int *d_active,
+				      const float *d_hit_t, const int *d_hit_id, const int *d_occluded);
 
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */

@@ -152,6 +152,9 @@ PROTOTYPES = {
     "ugrt_shade_reflect": (C.c_int, [_P] * 10 + [C.c_int] + [_P] * 6),
     "ugrt_reflect_rays_next": (C.c_int, [_P] * 7 + [C.c_int, _P, _P, C.c_float, _P, _P]),
     "ugrt_shade_reflect_depth": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 4),
+    "ugrt_occlusion_rays": (C.c_int, [_P] * 7 + [_F3, C.c_float, _P, _P]),
+    "ugrt_trace_dda_any": (C.c_int, [_P] * 8 + [C.c_float, _P]),
+    "ugrt_shade_reflect_depth_occluded": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 5),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

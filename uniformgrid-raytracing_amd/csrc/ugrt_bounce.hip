@@ -68,6 +68,65 @@ extern "C" int ugrt_reflect_rays_next(ugrt_ctx *ctx, const float *d_rays, const 
 	return UGRT_OK;
 }
 
+// Occlusion rays from one level's hits towards the light: the origin is the one the next
+// reflected ray would start from (d_reflect_ray), the direction L - o' is not normalised, so the light lies at t = 1.
+// The hit's material plays no part: a diffuse hit seen in a mirror is shadowed too.
+__global__ __launch_bounds__(PX_THREADS) void k_occlusion_rays(const float *__restrict__ rays,
+								const int *__restrict__ active,
+								const float *__restrict__ hit_t,
+								const int *__restrict__ hit_id,
+								const float *__restrict__ verts, const int *__restrict__ tris,
+								float lx, float ly, float lz, float eps,
+								float *__restrict__ orays, int *__restrict__ oactive, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int p = p0 + i;
+	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+	int act = 0;
+	if (active[p]) {
+		int id = hit_id[p];
+		float t = hit_t[p];
+		if (t > 0 && id >= 0) {
+			const float L[3] = { lx, ly, lz };
+			float tri[9], o[3], d[3];
+			d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				o[k] = rays[p * 6 + k];
+				d[k] = rays[p * 6 + 3 + k];
+			}
+			d_reflect_ray(o, d, t, tri, eps, out);
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				out[3 + k] = L[k] - out[k];
+			act = 1;
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 6; k++)
+		orays[p * 6 + k] = out[k];
+	oactive[p] = act;
+}
+
+extern "C" int ugrt_occlusion_rays(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+				   const int *d_hit_id, const float *d_vertlist, const int *d_trilist,
+				   const float light_pos[3], float eps, float *d_orays, int *d_oactive)
+{
+	if (!ctx || !d_rays || !d_active || !d_hit_t || !d_hit_id || !d_vertlist || !d_trilist || !light_pos || !d_orays ||
+	    !d_oactive)
+		return ugrt_fail(UGRT_EINVAL, "occlusion_rays: null argument");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
+	hipLaunchKernelGGL(k_occlusion_rays, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_rays, d_active, d_hit_t, d_hit_id, d_vertlist, d_trilist, light_pos[0], light_pos[1], light_pos[2], eps,
+			   d_orays, d_oactive, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 struct DepthIn {
 	const float *reflect;
 	const float *verts;
@@ -78,6 +137,7 @@ struct DepthIn {
 	const int *hit_id;
 	size_t level;       // W*H
 	int depth;
+	const int *occluded; // level j at (j-1) * level (ugrt_shade_reflect_depth_occluded; otherwise null and never read)
 };
 
 // the clamped Lambert colour of level j's hit (as k_shade_reflect shades the first bounce's hit); 0 on a miss or a
@@ -116,7 +176,9 @@ __device__ __forceinline__ void d_level_color(const CamBlock &cam, const DepthIn
 
 // acc = 0, w = 1; level j that goes on (active_{j+1}): acc += (w*(1-k_j))*L_j, w *= k_j; the first level that does not
 // (level `depth` at the latest): acc += w*L_j.  At depth 1 this is k_shade_reflect operation for operation.  A pixel
-// reads the levels it reaches and no others.
+// reads the levels it reaches and no others.  OCC: a level j >= 1 whose hit is occluded (in.occluded) is darkened to
+// L_j / 3, the float counterpart of add_shadows' /= 3, before it is weighted.
+template <bool OCC>
 __global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_depth(CamBlock cam, unsigned char *__restrict__ d_img,
 								     const float *__restrict__ dd_normal,
 								     const float *__restrict__ dd_t_value,
@@ -171,11 +233,46 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_depth(CamBlock cam
 				acc[k] = acc[k] + (w * (1.0f - kr)) * color[k];
 			w = w * kr;
 			d_level_color(cam, in, mat_idx, mat_list, mat_count, q, color, &kr);
+			if (OCC && in.occluded[q] == 1) {
+#pragma unroll
+				for (int k = 0; k < 3; k++)
+					color[k] = color[k] / 3.0f;
+			}
 		}
 	}
 	d_img[pixelID * 3 + 0] = d_to_u8(acc[0]);
 	d_img[pixelID * 3 + 1] = d_to_u8(acc[1]);
 	d_img[pixelID * 3 + 2] = d_to_u8(acc[2]);
+}
+
+// both exports: d_occluded null = ugrt_shade_reflect_depth
+static int shade_reflect_depth(ugrt_ctx *ctx, const char *who, unsigned char *d_img, const float *d_normal,
+			       const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+			       const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+			       const float *d_reflect, int num_materials, const float *d_vertlist, const int *d_trilist,
+			       int depth, const float *d_rays, const int *d_active, const float *d_hit_t, const int *d_hit_id,
+			       const int *d_occluded)
+{
+	if (!ctx || !d_img || !d_normal || !d_t_value || !d_ray_dir || !d_intersect_id || !d_cam_position || !d_mat_idx ||
+	    !d_mat_list || !d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id)
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if (depth < 1 || depth > UGRT_MAX_REFLECT_DEPTH)
+		return ugrt_fail(UGRT_EINVAL, "%s: depth %d outside 1..%d", who, depth, UGRT_MAX_REFLECT_DEPTH);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	DepthIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id,
+		       (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, depth, d_occluded };
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	if (d_occluded)
+		hipLaunchKernelGGL(k_shade_reflect_depth<true>, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+				   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
+				   d_mat_idx, d_mat_list, num_materials, in, ctx->p0, ctx->npix);
+	else
+		hipLaunchKernelGGL(k_shade_reflect_depth<false>, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+				   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
+				   d_mat_idx, d_mat_list, num_materials, in, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
 }
 
 extern "C" int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
@@ -185,19 +282,21 @@ extern "C" int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, con
 					const int *d_trilist, int depth, const float *d_rays, const int *d_active,
 					const float *d_hit_t, const int *d_hit_id)
 {
-	if (!ctx || !d_img || !d_normal || !d_t_value || !d_ray_dir || !d_intersect_id || !d_cam_position || !d_mat_idx ||
-	    !d_mat_list || !d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id)
-		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth: null argument");
-	if (depth < 1 || depth > UGRT_MAX_REFLECT_DEPTH)
-		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth: depth %d outside 1..%d", depth, UGRT_MAX_REFLECT_DEPTH);
-	UGRT_HIP(hipSetDevice(ctx->device));
-	DepthIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id,
-		       (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, depth };
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_reflect_depth, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
-			   d_mat_idx, d_mat_list, num_materials, in, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return shade_reflect_depth(ctx, "shade_reflect_depth", d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id,
+				   d_cam_position, d_mat_idx, d_mat_list, d_reflect, num_materials, d_vertlist, d_trilist, depth,
+				   d_rays, d_active, d_hit_t, d_hit_id, nullptr);
+}
+
+extern "C" int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
+						 const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+						 const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+						 const float *d_reflect, int num_materials, const float *d_vertlist,
+						 const int *d_trilist, int depth, const float *d_rays, const int *d_active,
+						 const float *d_hit_t, const int *d_hit_id, const int *d_occluded)
+{
+	if (!d_occluded)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth_occluded: null argument");
+	return shade_reflect_depth(ctx, "shade_reflect_depth_occluded", d_img, d_normal, d_t_value, d_ray_dir,
+				   d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, d_reflect, num_materials, d_vertlist,
+				   d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id, d_occluded);
 }

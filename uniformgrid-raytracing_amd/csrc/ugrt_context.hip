@@ -200,6 +200,7 @@ static const struct {
 	{ "shadow_waves", 64, 1 << 20 }, { "dda_sort", 0, 1 }, { "primary_order", 0, 1 }, { "primary_chunk", 4, 64 }, { "sort_items", 8, 16 }, { "dda_cull_work", 1, 1 << 30 },
 	{ "dda_split", 0, 4 }, { "dda_split_load", 50, 100000 }, { "dda_split_segments", 1, 4 }, { "primary_xcd_run", 0, 4096 }, { "shadow_xcd_run", 0, 4096 },
 	{ "primary_centre", 0, 1 }, { "sort_rank", 0, 1 }, { "ray_sort", 0, 1 }, { "shadow_sieve", 0, 64 },
+	{ "any_rays_per_wave", 0, 64 }, { "any_coop", 1, 1 << 30 },
 };
 
 extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *value)
@@ -246,7 +247,7 @@ extern "C" int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value)
 				return ugrt_fail(UGRT_EINVAL, "ctx_set_option: %s %d outside [%d,%d]", key, value, k_opt[i].lo,
 						 k_opt[i].hi);
 			// 0 keeps meaning "default" for the rays-per-wave option of version 100
-			ctx->opt[i] = (value < 0 || (i == UGRT_OPT_DDA_RPW && value == 0)) ? -1 : value;
+			ctx->opt[i] = (value < 0 || ((i == UGRT_OPT_DDA_RPW || i == UGRT_OPT_ANY_RPW) && value == 0)) ? -1 : value;
 			return UGRT_OK;
 		}
 	return ugrt_fail(UGRT_EINVAL, "ctx_set_option: unknown key '%s'", key);

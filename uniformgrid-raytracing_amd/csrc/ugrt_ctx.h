@@ -51,6 +51,8 @@ enum {
 	UGRT_OPT_SORT_RANK,        // "sort_rank": radix pass: 0 = ranks by ballots, 1 / default = by LDS atomics where the device's self-test allows it
 	UGRT_OPT_RAY_SORT,         // "ray_sort": 1 = the deferred ugrt_sort_rays sorts at once; 0 / default = on demand (see ugrt_sort_rays)
 	UGRT_OPT_SHADOW_SIEVE,     // "shadow_sieve": items a sieve wave of the exact shadow pass looks at (default 16; 0 / 1 = a wave per item)
+	UGRT_OPT_ANY_RPW,          // "any_rays_per_wave": rays per wave of ugrt_trace_dda_any (1..64; 0 = default)
+	UGRT_OPT_ANY_COOP,         // "any_coop": ugrt_trace_dda_any: list length from which a ray's cell is tested by the whole wave
 	UGRT_OPT_COUNT
 };
 

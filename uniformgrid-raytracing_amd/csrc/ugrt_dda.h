@@ -10,6 +10,19 @@ struct DGrid {
 	int dims[3];
 };
 
+// the cell geometry of a built uniform grid, as the bounce kernels take it
+static inline DGrid ugrt_dgrid_of(const Grid &G)
+{
+	DGrid g;
+	for (int k = 0; k < 3; k++) {
+		g.lo[k] = G.ug[k];
+		g.cs[k] = G.ug[3 + k];
+		g.inv[k] = G.ug[6 + k];
+		g.dims[k] = G.dims[k];
+	}
+	return g;
+}
+
 // Segments of the window kernel's long ray groups (ugrt_dda_walk.hip, "split walks"); all pointers null: no splitting
 #define WK_FBW 32      // windows of a group whose job counts are remembered (one byte each; later windows share the last)
 #define WK_MAXSEG 4    // segments a group is cut into at most

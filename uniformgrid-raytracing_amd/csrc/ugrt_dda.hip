@@ -46,7 +46,9 @@ __device__ __forceinline__ unsigned long long d_wave_min_u64(unsigned long long 
 // land in the list in the order their atomics arrive, which changes from launch to launch, but a ray group (16, 32
 // or 64 consecutive entries) then always holds the same pixels, and `chunk` says which span and which of its chunks
 // every 64 entries are -- what the window kernel keeps the groups' history under (null: not wanted).
+// HITS false: the form of ugrt_trace_dda_any, which has no hit arrays: `hit_id` is its occlusion flags, cleared here.
 #define DDA_PREP_SPAN 512
+template <bool HITS>
 __global__ __launch_bounds__(256) void k_dda_prepare(const int *__restrict__ active, int p0, int npix, int W,
 						      float *__restrict__ hit_t, int *__restrict__ hit_id,
 						      u32 *__restrict__ list, u32 *__restrict__ count,
@@ -90,8 +92,9 @@ __global__ __launch_bounds__(256) void k_dda_prepare(const int *__restrict__ act
 		bool a = false;
 		if (i < npix) {
 			a = active[pix[k]] != 0;
-			hit_t[pix[k]] = -1.0f;
-			hit_id[pix[k]] = -2;
+			if (HITS)
+				hit_t[pix[k]] = -1.0f;
+			hit_id[pix[k]] = HITS ? -2 : 0;
 		}
 		flags |= (unsigned long long)a << k;
 		total += (u32)__popcll(__ballot(a));
@@ -346,13 +349,7 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
 	UGRT_HIP(hipSetDevice(ctx->device));
-	DGrid g;
-	for (int k = 0; k < 3; k++) {
-		g.lo[k] = G.ug[k];
-		g.cs[k] = G.ug[3 + k];
-		g.inv[k] = G.ug[6 + k];
-		g.dims[k] = G.dims[k];
-	}
+	const DGrid g = ugrt_dgrid_of(G);
 	int rc;
 	// (k_dda_prepare pads every span of DDA_PREP_SPAN pixels to whole chunks of 64 list entries: the list can be that
 	// much longer than the band has pixels when the band is not a whole number of spans)
@@ -398,7 +395,7 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	    (rc = ugrt_dda_split_state(ctx, DDA_RPW, d_span == (const unsigned *)G.span.p && d_offset == (const unsigned *)G.offset.p ? G.R : 0xFFFFFFFFu,
 				       &sp, &sph)))
 		return rc;
-	hipLaunchKernelGGL(k_dda_prepare, dim3(pix_blocks + bm_blocks), dim3(256), 0, ctx->stream, d_active, ctx->p0, ctx->npix,
+	hipLaunchKernelGGL(k_dda_prepare<true>, dim3(pix_blocks + bm_blocks), dim3(256), 0, ctx->stream, d_active, ctx->p0, ctx->npix,
 			   ctx->cfg.width, d_hit_t, d_hit_id, list, dcount, ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span,
 			   ncell_all, (u32 *)ctx->ubitmap.p, (u32 *)sp.chunk, dcount_next);
 	ctx->dda_turn = turn;
@@ -482,6 +479,34 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 #undef UGRT_LAUNCH_DDA
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+// The ray list, its counter and the occupancy bitmap for ugrt_trace_dda_any (ugrt_dda_any.hip): ugrt_trace_dda's prepare
+// launch in the form that writes no hit defaults (it clears the band's occlusion flags instead), always with the bitmap
+// workgroups, never with the split walks' chunk table.  The two ray counters are taken in turn exactly as above.
+int ugrt_dda_prepare_any(ugrt_ctx *ctx, const DGrid &g, const int *d_active, int *d_occluded, const u32 *d_span,
+			 const u32 **list_out, const u32 **dcount_out)
+{
+	int rc;
+	const size_t list_cap = ((size_t)ctx->npix + DDA_PREP_SPAN - 1) / DDA_PREP_SPAN * DDA_PREP_SPAN;
+	const u32 ncell_all = (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2];
+	if ((rc = ugrt_buf_reserve(ctx, ctx->wscan, list_cap * 4)) ||
+	    (rc = ugrt_buf_reserve(ctx, ctx->ubitmap, ((size_t)ncell_all + 63) / 64 * 8 + 8)))
+		return rc;
+	const u32 turn = ctx->dda_turn ^ 1u;
+	u32 *dcount = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS_B : UGRT_DSMALL_DDA_RAYS);
+	u32 *dcount_next = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS : UGRT_DSMALL_DDA_RAYS_B);
+	const u32 pix_blocks = (u32)((ctx->npix + 4 * DDA_PREP_SPAN - 1) / (4 * DDA_PREP_SPAN));
+	const u32 bm_blocks = (ncell_all + 255u) / 256u < 1024u ? (ncell_all + 255u) / 256u : 1024u;
+	hipLaunchKernelGGL(k_dda_prepare<false>, dim3(pix_blocks + bm_blocks), dim3(256), 0, ctx->stream, d_active, ctx->p0,
+			   ctx->npix, ctx->cfg.width, (float *)nullptr, d_occluded, (u32 *)ctx->wscan.p, dcount,
+			   ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span, ncell_all, (u32 *)ctx->ubitmap.p, (u32 *)nullptr,
+			   dcount_next);
+	ctx->dda_turn = turn;
+	UGRT_HIP(hipGetLastError());
+	*list_out = (const u32 *)ctx->wscan.p;
+	*dcount_out = dcount;
 	return UGRT_OK;
 }
 

@@ -1,0 +1,231 @@
+// ugrt_dda_any.hip -- any-hit traversal of the uniform grid: "is anything in the way between here and there"
+// (not in the reference).
+//
+// Spec: a ray is occluded iff some triangle in the list of some VISITED cell passes ugrt_trace_dda's exact test
+// (d_mt_core, same operands) with 0 < t < t_max.  The visited cells are those of ugrt_trace_dda's walk -- same slab
+// clip, entry cell, tmax / tdelta arithmetic, axis choice and dims-sum guard -- from the entry cell onwards for as long
+// as a cell's entry parameter (tenter, then the exit parameter of the cell before) is below t_max.  The result is an OR
+// over a fixed set of cells, so none of what the closest-hit kernels order their work by is needed here:
+//   * a lane (= ray) is done at its first accepted test, a wave leaves when no lane walks any more;
+//   * a window of ANY_AHEAD steps is planned in registers.  The plan is the cells alone: no exit parameter is kept per
+//     step, because no cell has to be compared with a closest hit -- where the walk ends is decided while planning;
+//   * the window's cells are looked up in the occupancy bitmap (83 % of the visited cells are empty on the bench
+//     frame), and span / offset are fetched for the occupied ones only;
+//   * a short list is tested by its lane; a long one by the wave, 64 triangles per round with the owner's ray
+//     broadcast, and a round is accepted with one ballot: no 64-bit minimum, no LDS, no list position.
+// The kernel reads the grid and the rays and writes its flags: it neither reads nor writes the split walks' history.
+#include "ugrt_dda.h"
+
+#define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
+
+// ugrt_dda.hip
+int ugrt_dda_prepare_any(ugrt_ctx *ctx, const DGrid &g, const int *d_active, int *d_occluded, const u32 *d_span,
+			 const u32 **list_out, const u32 **dcount_out);
+
+// `occluded` of the band was cleared by the prepare kernel: only the flags of occluded rays are written
+template <bool REC>
+__global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__restrict__ value_list,
+							const u32 *__restrict__ span, const u32 *__restrict__ offset,
+							const u32 *__restrict__ bitmap, const float *__restrict__ verts,
+							const int *__restrict__ tris, const float4 *__restrict__ rec,
+							const float *__restrict__ rays, const u32 *__restrict__ list,
+							const u32 *__restrict__ count_p, float t_max, int *__restrict__ occluded,
+							u32 RPW, u32 COOP, u32 *__restrict__ ticket)
+{
+	const int lane = threadIdx.x;
+	const u32 count = *count_p;
+	// groups of RPW rays, the first gridDim.x by workgroup id, the others drawn from the ticket
+	for (u32 grp = blockIdx.x; grp * RPW < count;) {
+		const u32 slot = grp * RPW + (u32)lane;
+		bool inb = (u32)lane < RPW && slot < count;
+		const int p = inb ? (int)list[slot] : 0;
+		inb = inb && p != -1; // (padding: k_dda_prepare)
+		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
+		int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
+		bool walking = false, occ = false;
+		// set-up: the arithmetic of k_trace_dda_ray
+		if (inb) {
+			float tenter = 0.0f, texit = 3.0e38f;
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				o[k] = rays[p * 6 + k];
+				d[k] = rays[p * 6 + 3 + k];
+			}
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
+				if (d[k] != 0.0f) {
+					float inv = 1.0f / d[k];
+					float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
+					if (t0 > t1) {
+						float s = t0;
+						t0 = t1;
+						t1 = s;
+					}
+					if (t0 > tenter)
+						tenter = t0;
+					if (t1 < texit)
+						texit = t1;
+				} else if (o[k] < lo || o[k] > hi) {
+					texit = -1.0f;
+				}
+			}
+			if (tenter <= texit) {
+				walking = tenter < t_max; // the entry cell's entry parameter
+#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					float pe = o[k] + tenter * d[k];
+					c[k] = d_dcell(g, k, pe);
+					if (d[k] > 0.0f) {
+						step[k] = 1;
+						tmax[k] = ((g.lo[k] + (float)(c[k] + 1) * g.cs[k]) - o[k]) / d[k];
+						tdelta[k] = g.cs[k] / d[k];
+					} else if (d[k] < 0.0f) {
+						step[k] = -1;
+						tmax[k] = ((g.lo[k] + (float)c[k] * g.cs[k]) - o[k]) / d[k];
+						tdelta[k] = -g.cs[k] / d[k];
+					} else {
+						step[k] = 0;
+						tmax[k] = 3.0e38f;
+						tdelta[k] = 3.0e38f;
+					}
+				}
+			}
+		}
+		int guard = g.dims[0] + g.dims[1] + g.dims[2] + 3;
+		while (__ballot(walking) != 0ull) {
+			// 1. the window's cells.  The walk ends behind a cell when the ray leaves the grid there, when the guard runs
+			// out, or when the cell's exit parameter -- the next cell's entry parameter -- is not below t_max.
+			u32 pcell[ANY_AHEAD], pvalid = 0u;
+			bool planning = walking;
+#pragma unroll
+			for (int q = 0; q < ANY_AHEAD; q++) {
+				pcell[q] = 0u;
+				if (planning) {
+					pvalid |= 1u << q;
+					pcell[q] = (u32)((c[0] * g.dims[1] + c[1]) * g.dims[2] + c[2]);
+					const int ax = (tmax[0] < tmax[1]) ? ((tmax[0] < tmax[2]) ? 0 : 2) : ((tmax[1] < tmax[2]) ? 1 : 2);
+					const float tnext = ax == 0 ? tmax[0] : (ax == 1 ? tmax[1] : tmax[2]);
+					// step along ax (written out: no dynamically indexed registers)
+					bool outside;
+					if (ax == 0) {
+						c[0] += step[0];
+						outside = step[0] == 0 || c[0] < 0 || c[0] >= g.dims[0];
+						tmax[0] += tdelta[0];
+					} else if (ax == 1) {
+						c[1] += step[1];
+						outside = step[1] == 0 || c[1] < 0 || c[1] >= g.dims[1];
+						tmax[1] += tdelta[1];
+					} else {
+						c[2] += step[2];
+						outside = step[2] == 0 || c[2] < 0 || c[2] >= g.dims[2];
+						tmax[2] += tdelta[2];
+					}
+					if (outside || --guard <= 0 || !(tnext < t_max))
+						planning = false;
+				}
+			}
+			// 2. which of them hold a triangle: one bitmap word per step, then the headers of the occupied cells only
+			u32 pword[ANY_AHEAD], psp[ANY_AHEAD], poff[ANY_AHEAD];
+#pragma unroll
+			for (int q = 0; q < ANY_AHEAD; q++)
+				pword[q] = ((pvalid >> q) & 1u) ? bitmap[pcell[q] >> 5] : 0u;
+#pragma unroll
+			for (int q = 0; q < ANY_AHEAD; q++) {
+				const bool full = (pword[q] >> (pcell[q] & 31u)) & 1u;
+				psp[q] = full ? span[pcell[q]] : 0u;
+				poff[q] = full ? offset[pcell[q]] : 0u;
+			}
+			// 3. the tests, until the ray's first accepted one
+#pragma unroll
+			for (int q = 0; q < ANY_AHEAD; q++) {
+				const u32 sp = walking ? psp[q] : 0u, off = poff[q];
+				if (__ballot(sp != 0u) == 0ull)
+					continue;
+				// short lists: the owning lane
+				if (sp < COOP) {
+					for (u32 r = 0; r < sp; r++) {
+						float t9[9], t;
+						d_load_triangle<REC>(rec, verts, tris, value_list[off + r], o[0], o[1], o[2], t9);
+						if (d_mt_core(&t9[0], &t9[3], &t9[6], d, &t) && t > 0.0f && t < t_max) {
+							occ = true;
+							break;
+						}
+					}
+				}
+				// long lists: one owner at a time, 64 triangles per round, accepted by one ballot
+				unsigned long long heavy = __ballot(sp >= COOP);
+				while (heavy != 0ull) {
+					const int l = (int)__builtin_ctzll(heavy);
+					heavy &= heavy - 1ull;
+					const float ox = d_readlane(o[0], l), oy = d_readlane(o[1], l), oz = d_readlane(o[2], l);
+					const float dl[3] = { d_readlane(d[0], l), d_readlane(d[1], l), d_readlane(d[2], l) };
+					const u32 spl = (u32)__builtin_amdgcn_readlane((int)sp, l), offl = (u32)__builtin_amdgcn_readlane((int)off, l);
+					bool hit = false;
+					for (u32 base = 0; base < spl && !hit; base += 64u) {
+						const u32 r = base + (u32)lane;
+						bool acc = false;
+						if (r < spl) {
+							float t9[9], t;
+							d_load_triangle<REC>(rec, verts, tris, value_list[offl + r], ox, oy, oz, t9);
+							acc = d_mt_core(&t9[0], &t9[3], &t9[6], dl, &t) && t > 0.0f && t < t_max;
+						}
+						hit = __ballot(acc) != 0ull;
+					}
+					if (hit && lane == l)
+						occ = true;
+				}
+				walking = walking && !occ;
+			}
+			walking = walking && planning; // (planning: the walk goes on behind this window)
+		}
+		if (occ)
+			occluded[p] = 1;
+		if (lane == 0)
+			grp = gridDim.x + atomicAdd(ticket, 1u);
+		grp = (u32)__builtin_amdgcn_readfirstlane((int)grp);
+	}
+}
+
+extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				  const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				  const float *d_rays, const int *d_active, float t_max, int *d_occluded)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_occluded)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any: null argument");
+	if (!(t_max > 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any: t_max must be greater than 0");
+	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	if (!G.valid)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const DGrid g = ugrt_dgrid_of(G);
+	const bool use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
+	const float4 *rec = use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+	// launch shape (ugrt_ctx_set_option; no effect on results)
+	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
+	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
+	const u32 *list, *dcount;
+	int rc;
+	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
+	rc = ugrt_dda_prepare_any(ctx, g, d_active, d_occluded, d_span, &list, &dcount);
+	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
+	if (rc)
+		return rc;
+	// persistent single-wave workgroups; "dda_blocks" caps them as it caps ugrt_trace_dda's
+	int blocks = launch_blocks_for((u32)ctx->npix / RPW + 1u);
+	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
+		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
+	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
+	if (use_rec)
+		hipLaunchKernelGGL(k_trace_dda_any<true>, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset,
+				   (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays, list, dcount, t_max, d_occluded, RPW,
+				   COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+	else
+		hipLaunchKernelGGL(k_trace_dda_any<false>, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset,
+				   (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays, list, dcount, t_max, d_occluded, RPW,
+				   COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}

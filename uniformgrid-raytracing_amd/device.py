@@ -244,6 +244,26 @@ class Context:
                                            num_materials, _ptr(verts), _ptr(faces), int(depth), _ptr(rays),
                                            _ptr(active), _ptr(hit_t), _ptr(hit_id)))
 
+    # -- shadows on reflected hits --------------------
+    def occlusion_rays(self, rays, active, hit_t, hit_id, verts, faces, light_pos, eps, orays, oactive):
+        """One level's hits -> rays towards light_pos (three host floats); the light lies at t = 1."""
+        check(lib.ugrt_occlusion_rays(self._h, _ptr(rays), _ptr(active), _ptr(hit_t), _ptr(hit_id), _ptr(verts),
+                                      _ptr(faces), _f3(light_pos), eps, _ptr(orays), _ptr(oactive)))
+
+    def trace_dda_any(self, value, span, offset, verts, faces, rays, active, t_max, occluded):
+        """occluded[p] = 1 where a triangle of a visited cell is hit with 0 < t < t_max."""
+        check(lib.ugrt_trace_dda_any(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                     _ptr(rays), _ptr(active), t_max, _ptr(occluded)))
+
+    def shade_reflect_depth_occluded(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, reflect,
+                                     num_materials, verts, faces, depth, rays, active, hit_t, hit_id, occluded):
+        """shade_reflect_depth with the levels whose hit is occluded (stacked like active) darkened to a third."""
+        check(lib.ugrt_shade_reflect_depth_occluded(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir),
+                                                    _ptr(ids), _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list),
+                                                    _ptr(reflect), num_materials, _ptr(verts), _ptr(faces), int(depth),
+                                                    _ptr(rays), _ptr(active), _ptr(hit_t), _ptr(hit_id),
+                                                    _ptr(occluded)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

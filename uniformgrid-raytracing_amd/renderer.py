@@ -15,7 +15,9 @@ With ``reflect=True`` the shading step becomes: secondary rays -> uniform grid
 build -> 3D-DDA -> shade_reflect (not in the reference).  With
 ``bounces=D > 1`` the reflected rays are followed D levels deep: (next rays ->
 3D-DDA) x (D-1) behind the first bounce, then shade_reflect_depth (DESIGN.md
-section 6).
+section 6).  With ``reflect_shadows=True`` the hits of every reflection level are tested against the
+light behind the level's 3D-DDA (occlusion rays -> any-hit walk) and the shading darkens the
+occluded levels.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -36,6 +38,15 @@ def check_bounces(bounces):
     if isinstance(bounces, bool) or not isinstance(bounces, (int, np.integer)) or not 1 <= bounces <= MAX_REFLECT_DEPTH:
         raise ValueError("bounces must be an integer in 1..%d, not %r" % (MAX_REFLECT_DEPTH, bounces))
     return int(bounces)
+
+
+def check_reflect_shadows(reflect_shadows, reflect):
+    """A bool, and only with reflect, or ValueError (before anything is enqueued)."""
+    if not isinstance(reflect_shadows, (bool, np.bool_)):
+        raise ValueError("reflect_shadows must be a bool, not %r" % (reflect_shadows,))
+    if reflect_shadows and not reflect:
+        raise ValueError("reflect_shadows=True needs reflect=True: it shadows the reflected hits")
+    return bool(reflect_shadows)
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -109,9 +120,11 @@ def reflect_rays(c, f, cam_pos):
                    f.d_faces, f.reflect_eps, f.rays, f.active)
 
 
-def trace_reflections(c, f, bounces):
+def trace_reflections(c, f, bounces, shadow_light=None):
     """3D-DDA of level 1 through c's uniform grid, then levels 2..bounces (next rays -> 3D-DDA) behind it with no
-    host wait (a level without an active ray costs the DDA's prepare kernel and an empty persistent launch)."""
+    host wait (a level without an active ray costs the DDA's prepare kernel and an empty persistent launch).
+    shadow_light (reflect_shadows: the light camera's eye, three host floats): behind every level's 3D-DDA its hits'
+    occlusion rays towards that point and the any-hit walk up to it (t < 1) into f.occluded_levels."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     rays, active, hit_t, hit_id = f.rays, f.active, f.hit_t, f.hit_id
     for j in range(bounces):
@@ -121,11 +134,21 @@ def trace_reflections(c, f, bounces):
                                 f.d_faces, f.reflect_eps, nrays, nactive)
             rays, active, hit_t, hit_id = nrays, nactive, f.hit_t_levels[j], f.hit_id_levels[j]
         c.trace_dda(uvalue, uspan, uoffset, f.d_verts, f.d_faces, rays, active, hit_t, hit_id)
+        if shadow_light is not None:
+            c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_light, f.reflect_eps,
+                             f.occlusion_rays, f.occlusion_active)
+            c.trace_dda_any(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active, 1.0,
+                            f.occluded_levels[j])
 
 
-def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces):
-    """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1), then add_shadows."""
-    if reflect and bounces == 1:
+def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
+    """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
+    depth shading with the occluded levels darkened, at every depth), then add_shadows."""
+    if reflect and reflect_shadows:
+        c.shade_reflect_depth_occluded(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                                       f.d_reflect, f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
+                                       f.active_levels, f.hit_t_levels, f.hit_id_levels, f.occluded_levels)
+    elif reflect and bounces == 1:
         c.shade_reflect(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.d_reflect,
                         f.num_materials, f.d_verts, f.d_faces, f.rays, f.active, f.hit_t, f.hit_id)
     elif reflect:
@@ -191,15 +214,23 @@ class _Frame:
         # the reflection levels 1..D one behind the other (_ensure_reflect_buffers)
         self.rays = self.active = self.hit_t = self.hit_id = None
         self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
+        # reflect_shadows: the levels' occlusion flags, and the occlusion rays of the level that is being traced
+        self.occluded_levels = self.occlusion_rays = self.occlusion_active = None
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
-    def _ensure_reflect_buffers(self, bounces=1):
+    def _ensure_reflect_buffers(self, bounces=1, reflect_shadows=False):
         """rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)], allocated once for the
-        deepest frame asked for; rays / active / hit_t / hit_id are level 1's views."""
+        deepest frame asked for; rays / active / hit_t / hit_id are level 1's views.  reflect_shadows: also
+        occluded_levels [depth, W*H] and one level's occlusion rays [6 W*H] and their active flags [W*H]."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if reflect_shadows and (self.occluded_levels is None or self.occluded_levels.shape[0] < bounces):
+            self.occluded_levels = t.empty((bounces, N), dtype=t.int32, device=dev)
+            if self.occlusion_rays is None:
+                self.occlusion_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+                self.occlusion_active = t.empty(N, dtype=t.int32, device=dev)
         if self.rays_levels is not None and self.rays_levels.shape[0] >= bounces:
             return
-        t, N, dev = self.torch, self.N, self.image.device
         self.rays_levels = t.empty((bounces, 6 * N), dtype=t.float32, device=dev)
         self.active_levels = t.empty((bounces, N), dtype=t.int32, device=dev)
         self.hit_t_levels = t.empty((bounces, N), dtype=t.float32, device=dev)
@@ -345,19 +376,22 @@ class Renderer(_Frame, _Band):
             self._worker.join()
             self._worker = None
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
-        1's views."""
+        1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
+        point the primary shadow pass is cast from); occluded_levels holds the levels' flags."""
         bounces = check_bounces(bounces)
+        reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         if reflect and shade:
-            self._ensure_reflect_buffers(bounces)
+            self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
             two_streams = self._display_two_streams_inline if self._inline else self._display_overlapped
-            return two_streams(setup, frame_cnt, shadows, reflect, bounces)
+            return two_streams(setup, frame_cnt, shadows, reflect, bounces, reflect_shadows)
         ctx = self.ctx
         camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
-        use_light_camera(ctx, make_camera(setup.light_camera, setup.fovy, self.aspect))
+        lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
+        use_light_camera(ctx, lcam)
         if shadows:
             map_rays(ctx, self, self)
             build_grid(ctx, self, GRID_SPHERICAL, self.shards)
@@ -369,10 +403,10 @@ class Renderer(_Frame, _Band):
         if reflect:
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
-            trace_reflections(ctx, self, bounces)
-        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
+            trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
 
-    def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces):
+    def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
         uniform grid, then - once the primary hits exist - secondary rays and the 3D-DDA.  Main stream: screen
         grid, primary rays, ray mapping and sort, shadow rays (after the light grid), shading (after the DDA).
@@ -407,7 +441,7 @@ class Renderer(_Frame, _Band):
                     return
                 side.wait_event(ev_primary)
                 reflect_rays(aux, self, self.cam_pos)
-                trace_reflections(aux, self, bounces)
+                trace_reflections(aux, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
 
         self._jobs.put(side_job)
         failed = None
@@ -440,9 +474,9 @@ class Renderer(_Frame, _Band):
             raise failed
         if err is not None:
             raise err
-        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
 
-    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect, bounces):
+    def _display_two_streams_inline(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """The two-stream frame from ONE host thread: with option async_build no call waits for the device, so the
         side stream's work is simply enqueued first (light grid, uniform grid), then the camera pass on the main
         stream, then what depends on the primary hits on either stream; events join them as in _display_overlapped."""
@@ -477,7 +511,7 @@ class Renderer(_Frame, _Band):
         if reflect:
             side.wait_event(ev_primary)
             reflect_rays(aux, self, self.cam_pos)
-            trace_reflections(aux, self, bounces)
+            trace_reflections(aux, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
         use_light_camera(ctx, lcam)
         if shadows:
             map_rays(ctx, self, self)
@@ -485,7 +519,7 @@ class Renderer(_Frame, _Band):
             main.wait_event(ev_light_grid)
             trace_shadows(ctx, self, self, aux.grid_ptrs(GRID_SPHERICAL))
         main.wait_stream(side)
-        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
 
     def synchronize(self):
         """Both contexts are synchronised before anything is raised: an overflow reported by one must not leave the
@@ -557,11 +591,12 @@ class BandedRenderer(_Frame):
     def contexts(self):
         return [self.aux] + [b.ctx for b in self._per_band]
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False):
         bounces = check_bounces(bounces)
+        reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         t, aux, main, side = self.torch, self.aux, self.main_stream, self.side_stream
         if reflect:
-            self._ensure_reflect_buffers(bounces)
+            self._ensure_reflect_buffers(bounces, reflect_shadows)
         cam = make_camera(setup.camera, setup.fovy, self.aspect)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         ev_grids, ev_dda = t.cuda.Event(), t.cuda.Event()
@@ -584,7 +619,7 @@ class BandedRenderer(_Frame):
                 for ev in ev_prim:
                     side.wait_event(ev)
                 reflect_rays(aux, self, self._per_band[0].cam_pos)
-                trace_reflections(aux, self, bounces)
+                trace_reflections(aux, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
                 ev_dda.record(side)
         for b, st in zip(self._per_band, self.streams):
             with t.cuda.stream(st):
@@ -598,7 +633,7 @@ class BandedRenderer(_Frame):
             with t.cuda.stream(st):
                 if reflect:
                     st.wait_event(ev_dda)
-                shade_frame(b.ctx, self, b.cam_pos, frame_cnt, shadows, reflect, bounces)
+                shade_frame(b.ctx, self, b.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
         for st in self.streams[1:] + [side]:
             main.wait_stream(st)
 
