@@ -198,6 +198,7 @@ struct ugrt_ctx {
 	// asynchronous shadow pass: candidate pairs and beams of the last pass
 	u32 est_pairs = 0, est_beams = 0;
 	bool have_shadow_est = false, shadow_async_pending = false;
+	u32 shadow_key_bits = 0; // key bits the last shadow pass sorted its rays on (ugrt_ctx_get_state "shadow_key_bits")
 	unsigned long long stats[8] = { 0 };
 	unsigned long long dda_stats[UGRT_DDA_STATS] = { 0 }; // ugrt_stats_dda
 	unsigned long long primary_stats[UGRT_PRIMARY_STATS] = { 0 }; // ugrt_stats_primary

@@ -1022,7 +1022,9 @@ int ShadowPass::beams()
 {
 	int rc;
 	ugrt_prof_begin(ctx, UGRT_ST_SHADOW_PREP);
-	// key = (light cell, direction code): 32 bits when the cell index leaves >= 12 bits for the code
+	// key = (light cell, direction code).  The cell field also holds the two values behind the last cell (C = nothing can
+	// shadow the ray, C + 1 = not traced), so it is as wide as C + 1 needs: 32-bit keys while that leaves >= 12 bits for
+	// the code (C + 2 <= 2^20: a 1024 x 512 light grid still, 1024 x 1024 no longer), 64-bit keys above
 	const u32 cellbits = (u32)bits_of(ncellk);
 	const bool key64 = cellbits > 20u || ctx->opt[UGRT_OPT_SHADOW_KEY64] == 1;
 	u32 mbits = 32u - cellbits;
@@ -1030,6 +1032,7 @@ int ShadowPass::beams()
 		mbits = (u32)ctx->opt[UGRT_OPT_SHADOW_MBITS];
 	mbits = mbits > 24u ? 24u : mbits;
 	own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1;
+	ctx->shadow_key_bits = (key64 ? 30u : mbits) + cellbits;
 	const u32 kblocks = (u32)((n + WL_THREADS - 1) / WL_THREADS) < 768u ? (u32)((n + WL_THREADS - 1) / WL_THREADS) : 768u;
 	// (the kernels that write this pass's sort keys count their first digit: no histogram kernel before the sorts;
 	// 64-bit keys go to the library's sort and are not counted)
