@@ -228,8 +228,9 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * atomics (the context's self-test found them served in lane order on this device), 0 = by ballots, -1 = no sort
  * has run yet; "shadow_key_bits" key bits the last ugrt_trace_shadow sorted its rays on (0 = no pass has sorted yet);
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and
- * returns the number of operands whose result differs from 1.0f / x (0), "lane_reduce_mismatches" compares the tracers'
- * DPP / permlane-swap reductions with the same reductions by __shfl_xor (0): both wait for the stream.
+ * returns the number of operands whose result differs from 1.0f / x (0), "f2i_mismatches" does the same for the device
+ * forms of ugrt_f2i / ugrt_f2u / ugrt_floor2i against the portable ones of ugrt_fmath.h (0), "lane_reduce_mismatches"
+ * compares the tracers' DPP / permlane-swap reductions with the same reductions by __shfl_xor (0): all three wait for the stream.
  * Unknown key: UGRT_EINVAL. */
 int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *value);
 int ugrt_ctx_synchronize(ugrt_ctx *ctx);

@@ -999,8 +999,7 @@ static int build_prologue(ugrt_ctx *ctx, Grid &G, const int *d_facelist, const f
 		return rc;
 	// the geometry may have changed since the last build (animation, a new frame file): refresh the records,
 	// unless the caller vouches for it (UGRT_FLAG_STATIC_GEOMETRY) and these are the arrays last seen
-	if ((ctx->cfg.flags & UGRT_FLAG_STATIC_GEOMETRY) && ctx->rec_valid && ctx->rec_verts == d_vertlist &&
-	    ctx->rec_tris == d_facelist && ctx->rec_faces == F) {
+	if ((ctx->cfg.flags & UGRT_FLAG_STATIC_GEOMETRY) && ugrt_trirec_of(ctx, d_vertlist, d_facelist) && ctx->rec_faces == F) {
 		if (G.wide_zeroed != wide_counter(G, F)) // (the last build of this grid left it at zero: SpanTail)
 			UGRT_HIP(hipMemsetAsync(wide_counter(G, F), 0, 4, ctx->stream));
 		G.wide_zeroed = nullptr; // the count kernel dirties it; the build's last scan clears it again

@@ -50,7 +50,7 @@ enum {
 	UGRT_OPT_PRIMARY_CENTRE,   // "primary_centre": primary tracer, one wave per item: 0 = the runs of items in list order (default 1: from the middle of the list outwards)
 	UGRT_OPT_SORT_RANK,        // "sort_rank": radix pass: 0 = ranks by ballots, 1 / default = by LDS atomics where the device's self-test allows it
 	UGRT_OPT_RAY_SORT,         // "ray_sort": 1 = the deferred ugrt_sort_rays sorts at once; 0 / default = on demand (see ugrt_sort_rays)
-	UGRT_OPT_SHADOW_SIEVE,     // "shadow_sieve": items a sieve wave of the exact shadow pass looks at (default 16; 0 / 1 = a wave per item)
+	UGRT_OPT_SHADOW_SIEVE,     // "shadow_sieve": items a sieve wave of the exact shadow pass looks at (default 8; 0 / 1 = a wave per item)
 	UGRT_OPT_ANY_RPW,          // "any_rays_per_wave": rays per wave of ugrt_trace_dda_any (1..64; 0 = default)
 	UGRT_OPT_ANY_COOP,         // "any_coop": ugrt_trace_dda_any: list length from which a ray's cell is tested by the whole wave
 	UGRT_OPT_COUNT
@@ -213,6 +213,13 @@ struct ugrt_ctx {
 	} while (0)
 
 int ugrt_buf_reserve(ugrt_ctx *ctx, DevBuf &b, size_t bytes);
+// the context's triangle records, if they are valid and were made of these arrays (the kernels' REC variants gather
+// them); null: the kernels gather the vertices themselves
+static inline const float4 *ugrt_trirec_of(const ugrt_ctx *ctx, const float *d_vertlist, const int *d_trilist)
+{
+	const bool use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
+	return use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+}
 // NUM_SLABS > 1: span/offset over all slabs of each of the C light cells (ugrt_build.hip)
 int ugrt_slab_union(ugrt_ctx *ctx, const u32 *d_span, const u32 *d_offset, u32 C, u32 slabs, const u32 **uspan,
 		    const u32 **uoffset);

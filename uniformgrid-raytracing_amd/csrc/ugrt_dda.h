@@ -1,5 +1,6 @@
-// ugrt_dda.h -- pieces shared by the bounce kernels (ugrt_dda.hip: per-ray and beam kernels of rounds 1 and 2;
-// ugrt_dda_walk.hip: the window kernel): grid geometry, the bundle cull, triangle records.
+// ugrt_dda.h -- pieces shared by the kernels that walk the uniform grid (ugrt_dda.hip: the per-ray kernel; ugrt_dda_walk.hip:
+// the window kernel and the sort keys; ugrt_dda_any.hip: the any-hit kernel): grid geometry, the walk's arithmetic
+// (d_dda_clip, d_dda_axes, d_dda_step: the one text of DESIGN.md A13's clip, start and step), the bundle cull, triangle records.
 #ifndef UGRT_DDA_H
 #define UGRT_DDA_H
 
@@ -62,6 +63,86 @@ __device__ __forceinline__ int d_dcell(const DGrid &g, int k, float p)
 {
 	int c = ugrt_floor2i((p - g.lo[k]) * g.inv[k]);
 	return d_clampi(c, 0, g.dims[k] - 1);
+}
+
+// The walk of DESIGN.md A13, written once: every kernel that walks the grid visits the same cells because it runs these
+// float operations (the build is -ffp-contract=off), and the CPU restatements of the tests spell them out independently.
+//
+// Slab clip of the ray o + t d against the grid box: tenter = the parameter where it enters (0 for an origin inside);
+// true = the ray meets the box.
+__device__ __forceinline__ bool d_dda_clip(const DGrid &g, const float *o, const float *d, float &tenter)
+{
+	float texit = 3.0e38f;
+	tenter = 0.0f;
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
+		if (d[k] != 0.0f) {
+			float inv = 1.0f / d[k];
+			float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
+			if (t0 > t1) {
+				float s = t0;
+				t0 = t1;
+				t1 = s;
+			}
+			if (t0 > tenter)
+				tenter = t0;
+			if (t1 < texit)
+				texit = t1;
+		} else if (o[k] < lo || o[k] > hi) {
+			texit = -1.0f;
+		}
+	}
+	return tenter <= texit;
+}
+
+// Start of the walk per axis: the entry cell c, the direction of travel `step`, the parameter tmax at which the ray leaves
+// the cell along the axis and its increment per cell, tdelta
+__device__ __forceinline__ void d_dda_axes(const DGrid &g, const float *o, const float *d, float tenter, int *c, int *step,
+					   float *tmax, float *tdelta)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		float pe = o[k] + tenter * d[k];
+		c[k] = d_dcell(g, k, pe);
+		if (d[k] > 0.0f) {
+			step[k] = 1;
+			tmax[k] = ((g.lo[k] + (float)(c[k] + 1) * g.cs[k]) - o[k]) / d[k];
+			tdelta[k] = g.cs[k] / d[k];
+		} else if (d[k] < 0.0f) {
+			step[k] = -1;
+			tmax[k] = ((g.lo[k] + (float)c[k] * g.cs[k]) - o[k]) / d[k];
+			tdelta[k] = -g.cs[k] / d[k];
+		} else {
+			step[k] = 0;
+			tmax[k] = 3.0e38f;
+			tdelta[k] = 3.0e38f;
+		}
+	}
+}
+
+// One step: to the neighbour across the nearest cell wall.  tnext = the exit parameter of the cell that is left (the entry
+// parameter of the one entered); true = the ray has left the grid, c is no cell any more.
+__device__ __forceinline__ bool d_dda_step(const DGrid &g, int *c, const int *step, float *tmax, const float *tdelta, float &tnext)
+{
+	const int ax = (tmax[0] < tmax[1]) ? ((tmax[0] < tmax[2]) ? 0 : 2) : ((tmax[1] < tmax[2]) ? 1 : 2);
+	tnext = ax == 0 ? tmax[0] : (ax == 1 ? tmax[1] : tmax[2]);
+	// step along ax (written out: no dynamically indexed registers)
+	bool outside;
+	if (ax == 0) {
+		c[0] += step[0];
+		outside = step[0] == 0 || c[0] < 0 || c[0] >= g.dims[0];
+		tmax[0] += tdelta[0];
+	} else if (ax == 1) {
+		c[1] += step[1];
+		outside = step[1] == 0 || c[1] < 0 || c[1] >= g.dims[1];
+		tmax[1] += tdelta[1];
+	} else {
+		c[2] += step[2];
+		outside = step[2] == 0 || c[2] < 0 || c[2] >= g.dims[2];
+		tmax[2] += tdelta[2];
+	}
+	return outside;
 }
 
 // Cull of one triangle against a BUNDLE of rays with different origins.  Moller-Trumbore's numerators do

@@ -3,10 +3,11 @@
 // Spec: clip the ray against the grid box, walk the cells front to back
 // (Amanatides & Woo), test every triangle of a cell's list in ascending id with the reference's
 // Moller-Trumbore (signed t, 0 < t < best), stop at the first cell whose best hit lies before the cell's
-// exit.  Two kernels compute it:
+// exit.  The clip, the walk's start and its step are written once, in ugrt_dda.h (d_dda_clip, d_dda_axes, d_dda_step).
+// Two kernels compute it:
 //   k_trace_dda_walk (ugrt_dda_walk.hip, the default) -- the window kernel of round 3;
 //   k_trace_dda_ray (option "dda_kernel" = 1) -- round 1's kernel: every ray walks and tests alone, long
-//     lists are tested by the whole wave for one owner at a time.  Kept as the plain GPU form of the specification
+//     lists are tested by the whole wave for one owner at a time, the walk is the three helpers as they stand.  Kept as the plain GPU form of the specification
 //     that the window kernel is compared with (tests/test_gpu_parity.py::test_bounce_kernels_agree).
 // (Round 2's beam kernel, which shared the work inside a cell among the rays that stood in it, was the window kernel's
 // predecessor; it went in round 4, when nothing used it any more.)
@@ -156,52 +157,15 @@ __global__ __launch_bounds__(64) void k_trace_dda_ray(DGrid g, const u32 *__rest
 	const bool is_active = inb;
 	bool walking = false;
 	if (is_active) {
-		float tenter = 0.0f, texit = 3.0e38f;
 #pragma unroll
 		for (int k = 0; k < 3; k++) {
 			o[k] = rays[p * 6 + k];
 			d[k] = rays[p * 6 + 3 + k];
 		}
-#pragma unroll
-		for (int k = 0; k < 3; k++) {
-			float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
-			if (d[k] != 0.0f) {
-				float inv = 1.0f / d[k];
-				float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
-				if (t0 > t1) {
-					float s = t0;
-					t0 = t1;
-					t1 = s;
-				}
-				if (t0 > tenter)
-					tenter = t0;
-				if (t1 < texit)
-					texit = t1;
-			} else if (o[k] < lo || o[k] > hi) {
-				texit = -1.0f;
-			}
-		}
-		if (tenter <= texit) {
-			walking = true;
-#pragma unroll
-			for (int k = 0; k < 3; k++) {
-				float pe = o[k] + tenter * d[k];
-				c[k] = d_dcell(g, k, pe);
-				if (d[k] > 0.0f) {
-					step[k] = 1;
-					tmax[k] = ((g.lo[k] + (float)(c[k] + 1) * g.cs[k]) - o[k]) / d[k];
-					tdelta[k] = g.cs[k] / d[k];
-				} else if (d[k] < 0.0f) {
-					step[k] = -1;
-					tmax[k] = ((g.lo[k] + (float)c[k] * g.cs[k]) - o[k]) / d[k];
-					tdelta[k] = -g.cs[k] / d[k];
-				} else {
-					step[k] = 0;
-					tmax[k] = 3.0e38f;
-					tdelta[k] = 3.0e38f;
-				}
-			}
-		}
+		float tenter;
+		walking = d_dda_clip(g, o, d, tenter);
+		if (walking)
+			d_dda_axes(g, o, d, tenter, c, step, tmax, tdelta);
 	}
 	// every step leaves a cell for good, so dims[0]+dims[1]+dims[2] bounds the walk
 	int guard = g.dims[0] + g.dims[1] + g.dims[2] + 3;
@@ -220,23 +184,7 @@ __global__ __launch_bounds__(64) void k_trace_dda_ray(DGrid g, const u32 *__rest
 			ptnext[q] = 0.0f;
 			if (planning) {
 				pcell[q] = (u32)((c[0] * g.dims[1] + c[1]) * g.dims[2] + c[2]);
-				int ax = (tmax[0] < tmax[1]) ? ((tmax[0] < tmax[2]) ? 0 : 2) : ((tmax[1] < tmax[2]) ? 1 : 2);
-				ptnext[q] = ax == 0 ? tmax[0] : (ax == 1 ? tmax[1] : tmax[2]);
-				// step along ax (written out: no dynamically indexed registers)
-				bool outside;
-				if (ax == 0) {
-					c[0] += step[0];
-					outside = step[0] == 0 || c[0] < 0 || c[0] >= g.dims[0];
-					tmax[0] += tdelta[0];
-				} else if (ax == 1) {
-					c[1] += step[1];
-					outside = step[1] == 0 || c[1] < 0 || c[1] >= g.dims[1];
-					tmax[1] += tdelta[1];
-				} else {
-					c[2] += step[2];
-					outside = step[2] == 0 || c[2] < 0 || c[2] >= g.dims[2];
-					tmax[2] += tdelta[2];
-				}
+				const bool outside = d_dda_step(g, c, step, tmax, tdelta, ptnext[q]);
 				if (outside || --guard <= 0) {
 					pend[q] = true; // the walk ends after this cell unless it ends there with a hit
 					planning = false;
@@ -335,6 +283,55 @@ int ugrt_dda_split_state(ugrt_ctx *ctx, u32 RPW, u32 total_refs, WalkSplit *sp, 
 int ugrt_dda_sort_keys_launch(ugrt_ctx *ctx, const DGrid &g, const float *d_rays, const u32 *list, const u32 *dcount, u32 cap,
 			      u32 *keys);
 
+// entries of the ray list's buffer: k_dda_prepare pads every span of DDA_PREP_SPAN pixels to whole chunks of 64 list entries,
+// so the list can be that much longer than the band has pixels when the band is not a whole number of spans
+static inline size_t dda_list_cap(const ugrt_ctx *ctx)
+{
+	return ((size_t)ctx->npix + DDA_PREP_SPAN - 1) / DDA_PREP_SPAN * DDA_PREP_SPAN;
+}
+
+// The one k_dda_prepare launch of ugrt_trace_dda and ugrt_trace_dda_any (ugrt_dda_any.hip): the band's defaults, the ray list
+// and its counter, and (with_bitmap: extra workgroups of the same launch) the occupancy bitmap of the grid's cells.
+// d_hit_t null: the form of ugrt_trace_dda_any, whose `d_hit_id` is its occlusion flags.  chunk: the split walks' table, or null.
+int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
+		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out)
+{
+	int rc;
+	const u32 ncell_all = (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2];
+	if ((rc = ugrt_buf_reserve(ctx, ctx->wscan, dda_list_cap(ctx) * 4)) ||
+	    (with_bitmap && (rc = ugrt_buf_reserve(ctx, ctx->ubitmap, ((size_t)ncell_all + 63) / 64 * 8 + 8))))
+		return rc;
+	// (two ray counters in turn: a launch's prepare kernel clears the other one for the launch that follows -- no fill)
+	// (the turn is taken at the launch: a call that fails before leaves both as they were)
+	const u32 turn = ctx->dda_turn ^ 1u;
+	u32 *dcount = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS_B : UGRT_DSMALL_DDA_RAYS);
+	u32 *dcount_next = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS : UGRT_DSMALL_DDA_RAYS_B);
+	const u32 pix_blocks = (u32)((ctx->npix + 4 * DDA_PREP_SPAN - 1) / (4 * DDA_PREP_SPAN));
+	const u32 bm_blocks = with_bitmap ? ((ncell_all + 255u) / 256u < 1024u ? (ncell_all + 255u) / 256u : 1024u) : 0u;
+	hipLaunchKernelGGL(d_hit_t ? k_dda_prepare<true> : k_dda_prepare<false>, dim3(pix_blocks + bm_blocks), dim3(256), 0,
+			   ctx->stream, d_active, ctx->p0, ctx->npix, ctx->cfg.width, d_hit_t, d_hit_id, (u32 *)ctx->wscan.p, dcount,
+			   ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span, ncell_all, (u32 *)ctx->ubitmap.p, chunk, dcount_next);
+	ctx->dda_turn = turn;
+	UGRT_HIP(hipGetLastError());
+	*list_out = (u32 *)ctx->wscan.p;
+	*dcount_out = dcount;
+	return UGRT_OK;
+}
+
+// read-back of a counting launch (UGRT_FLAG_COUNT_WORK; waits for the stream)
+static int dda_read_counters(ugrt_ctx *ctx, const unsigned long long *dc)
+{
+	unsigned long long h[DS_END];
+	UGRT_HIP(hipMemcpyAsync(h, dc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+	UGRT_HIP(hipStreamSynchronize(ctx->stream));
+	ctx->stats[3] = h[0];
+	ctx->stats[4] = h[1];
+	ctx->stats[5] = h[2];
+	for (int i = 0; i < UGRT_DDA_STATS; i++)
+		ctx->dda_stats[i] = DS_ITER + i < DS_END ? h[DS_ITER + i] : 0ull;
+	return UGRT_OK;
+}
+
 extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
 			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
 			      const float *d_rays, const int *d_active, float *d_hit_t, int *d_hit_id)
@@ -351,29 +348,11 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	UGRT_HIP(hipSetDevice(ctx->device));
 	const DGrid g = ugrt_dgrid_of(G);
 	int rc;
-	// (k_dda_prepare pads every span of DDA_PREP_SPAN pixels to whole chunks of 64 list entries: the list can be that
-	// much longer than the band has pixels when the band is not a whole number of spans)
-	const size_t list_cap = ((size_t)ctx->npix + DDA_PREP_SPAN - 1) / DDA_PREP_SPAN * DDA_PREP_SPAN;
-	if ((rc = ugrt_buf_reserve(ctx, ctx->wscan, list_cap * 4)))
-		return rc;
-	// (two ray counters in turn: a launch's prepare kernel clears the other one for the launch that follows -- no fill)
-	// (the turn is taken where the prepare kernel is launched: a call that fails before leaves both as they were)
-	const u32 turn = ctx->dda_turn ^ 1u;
-	u32 *list = (u32 *)ctx->wscan.p, *dcount = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS_B : UGRT_DSMALL_DDA_RAYS);
-	u32 *dcount_next = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS : UGRT_DSMALL_DDA_RAYS_B);
-	const bool use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
-	const float4 *rec = use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
 	const bool counting = (ctx->cfg.flags & UGRT_FLAG_COUNT_WORK) != 0;
 	unsigned long long *dc = (unsigned long long *)(ctx->d_small + UGRT_DSMALL_DDA);
 	if (!counting)
 		ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	// (the window kernel's occupancy bitmap is written by extra workgroups of the same launch)
-	const bool walk = ctx->opt[UGRT_OPT_DDA_KERNEL] <= 0;
-	const u32 ncell_all = (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2];
-	if (walk && (rc = ugrt_buf_reserve(ctx, ctx->ubitmap, ((size_t)ncell_all + 63) / 64 * 8 + 8)))
-		return rc;
-	const u32 pix_blocks = (u32)((ctx->npix + 4 * DDA_PREP_SPAN - 1) / (4 * DDA_PREP_SPAN));
-	const u32 bm_blocks = walk ? ((ncell_all + 255u) / 256u < 1024u ? (ncell_all + 255u) / 256u : 1024u) : 0u;
 	// launch shape (ugrt_ctx_set_option; no effect on results): which kernel, rays per wave, list length from
 	// which a lone ray's cell is tested by the whole wave, list length from which a shared cell is culled first
 	// 0 window, 1 per-ray (the window kernel packs the steps left per axis into 10 bits each: ugrt_ctx_create admits at
@@ -395,15 +374,14 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 	    (rc = ugrt_dda_split_state(ctx, DDA_RPW, d_span == (const unsigned *)G.span.p && d_offset == (const unsigned *)G.offset.p ? G.R : 0xFFFFFFFFu,
 				       &sp, &sph)))
 		return rc;
-	hipLaunchKernelGGL(k_dda_prepare<true>, dim3(pix_blocks + bm_blocks), dim3(256), 0, ctx->stream, d_active, ctx->p0, ctx->npix,
-			   ctx->cfg.width, d_hit_t, d_hit_id, list, dcount, ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span,
-			   ncell_all, (u32 *)ctx->ubitmap.p, (u32 *)sp.chunk, dcount_next);
-	ctx->dda_turn = turn;
+	// (the window kernel's occupancy bitmap is written by extra workgroups of the prepare launch; the per-ray kernel has none)
+	u32 *list, *dcount;
+	if ((rc = ugrt_dda_prepare(ctx, g, d_active, d_hit_t, d_hit_id, d_span, kernel == 0, (u32 *)sp.chunk, &list, &dcount)))
+		return rc;
 	if (!counting) {
 		ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
 		ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
 	}
-	UGRT_HIP(hipGetLastError());
 	// the launch is persistent (groups of rays are drawn from a ticket); "dda_blocks" caps its waves, which a context
 	// that runs beside another stream's kernels uses to leave registers and LDS of every CU to them
 	int blocks = launch_blocks_for((u32)ctx->npix / DDA_RPW + 1u);
@@ -411,7 +389,7 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	// option dda_sort (SURVEY 8f.2 as written): the list sorted by (entry cell, octant) with the frame's pair sort
 	if (ctx->opt[UGRT_OPT_DDA_SORT] == 1) {
-		const u32 cap = (u32)list_cap;
+		const u32 cap = (u32)dda_list_cap(ctx);
 		if ((rc = ugrt_buf_reserve(ctx, ctx->dsort, (size_t)cap * 12)))
 			return rc;
 		u32 *k0 = (u32 *)ctx->dsort.p, *k1 = k0 + cap, *l1 = k1 + cap;
@@ -427,86 +405,28 @@ extern "C" int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const
 			return rc;
 		list = l1;
 	}
+	// counting variants (never the timed ones): the same traversal + atomics per ray / per wave
+	if (counting)
+		UGRT_HIP(hipMemsetAsync(dc, 0, DS_END * sizeof(unsigned long long), ctx->stream));
+	unsigned long long *counters = counting ? dc : (unsigned long long *)nullptr;
 	if (kernel == 0) {
 		// window kernel (ugrt_dda_walk.hip)
-		if (counting)
-			UGRT_HIP(hipMemsetAsync(dc, 0, DS_END * sizeof(unsigned long long), ctx->stream));
 		if ((rc = ugrt_dda_walk_launch(ctx, g, d_value_list, d_span, d_offset, (u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
-					       d_rays, (const u32 *)list, (const u32 *)dcount, d_hit_t, d_hit_id,
-					       counting ? dc : (unsigned long long *)nullptr, counting, DDA_RPW, CULL_MIN,
-					       ctx->opt[UGRT_OPT_DDA_CULL_WORK] > 0 ? (u32)ctx->opt[UGRT_OPT_DDA_CULL_WORK] : 10u * DDA_RPW, blocks, sp, sph)))
+					       d_rays, (const u32 *)list, (const u32 *)dcount, d_hit_t, d_hit_id, counters, counting, DDA_RPW,
+					       CULL_MIN, ctx->opt[UGRT_OPT_DDA_CULL_WORK] > 0 ? (u32)ctx->opt[UGRT_OPT_DDA_CULL_WORK] : 10u * DDA_RPW,
+					       blocks, sp, sph)))
 			return rc;
-		if (counting) {
-			unsigned long long h[DS_END];
-			UGRT_HIP(hipMemcpyAsync(h, dc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-			UGRT_HIP(hipStreamSynchronize(ctx->stream));
-			ctx->stats[3] = h[0];
-			ctx->stats[4] = h[1];
-			ctx->stats[5] = h[2];
-			for (int i = 0; i < UGRT_DDA_STATS; i++)
-				ctx->dda_stats[i] = DS_ITER + i < DS_END ? h[DS_ITER + i] : 0ull;
-			return UGRT_OK;
-		}
-		ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-		return UGRT_OK;
-	}
-#define UGRT_LAUNCH_DDA(CNTV, RECV, DC)                                                                               \
-	hipLaunchKernelGGL((k_trace_dda_ray<CNTV, RECV>), dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span,    \
-			   d_offset, d_vertlist, d_trilist, rec, d_rays, (const u32 *)list, (const u32 *)dcount, d_hit_t,     \
-			   d_hit_id, DC, DDA_RPW, DDA_COOP)
-	if (counting) {
-		// counting variant (never the timed one): same traversal + atomics per ray / per wave
-		UGRT_HIP(hipMemsetAsync(dc, 0, DS_END * sizeof(unsigned long long), ctx->stream));
-		if (use_rec)
-			UGRT_LAUNCH_DDA(true, true, dc);
-		else
-			UGRT_LAUNCH_DDA(true, false, dc);
+	} else {
+		const auto ray_kernel = counting ? (rec ? k_trace_dda_ray<true, true> : k_trace_dda_ray<true, false>)
+						 : (rec ? k_trace_dda_ray<false, true> : k_trace_dda_ray<false, false>);
+		hipLaunchKernelGGL(ray_kernel, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, d_vertlist,
+				   d_trilist, rec, d_rays, (const u32 *)list, (const u32 *)dcount, d_hit_t, d_hit_id, counters, DDA_RPW,
+				   DDA_COOP);
 		UGRT_HIP(hipGetLastError());
-		unsigned long long h[DS_END];
-		UGRT_HIP(hipMemcpyAsync(h, dc, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-		UGRT_HIP(hipStreamSynchronize(ctx->stream));
-		ctx->stats[3] = h[0];
-		ctx->stats[4] = h[1];
-		ctx->stats[5] = h[2];
-		for (int i = 0; i < UGRT_DDA_STATS; i++)
-			ctx->dda_stats[i] = DS_ITER + i < DS_END ? h[DS_ITER + i] : 0ull;
-		return UGRT_OK;
 	}
-	if (use_rec)
-		UGRT_LAUNCH_DDA(false, true, (unsigned long long *)nullptr);
-	else
-		UGRT_LAUNCH_DDA(false, false, (unsigned long long *)nullptr);
-#undef UGRT_LAUNCH_DDA
+	if (counting)
+		return dda_read_counters(ctx, dc);
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
-}
-
-// The ray list, its counter and the occupancy bitmap for ugrt_trace_dda_any (ugrt_dda_any.hip): ugrt_trace_dda's prepare
-// launch in the form that writes no hit defaults (it clears the band's occlusion flags instead), always with the bitmap
-// workgroups, never with the split walks' chunk table.  The two ray counters are taken in turn exactly as above.
-int ugrt_dda_prepare_any(ugrt_ctx *ctx, const DGrid &g, const int *d_active, int *d_occluded, const u32 *d_span,
-			 const u32 **list_out, const u32 **dcount_out)
-{
-	int rc;
-	const size_t list_cap = ((size_t)ctx->npix + DDA_PREP_SPAN - 1) / DDA_PREP_SPAN * DDA_PREP_SPAN;
-	const u32 ncell_all = (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2];
-	if ((rc = ugrt_buf_reserve(ctx, ctx->wscan, list_cap * 4)) ||
-	    (rc = ugrt_buf_reserve(ctx, ctx->ubitmap, ((size_t)ncell_all + 63) / 64 * 8 + 8)))
-		return rc;
-	const u32 turn = ctx->dda_turn ^ 1u;
-	u32 *dcount = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS_B : UGRT_DSMALL_DDA_RAYS);
-	u32 *dcount_next = ctx->d_small + (turn ? UGRT_DSMALL_DDA_RAYS : UGRT_DSMALL_DDA_RAYS_B);
-	const u32 pix_blocks = (u32)((ctx->npix + 4 * DDA_PREP_SPAN - 1) / (4 * DDA_PREP_SPAN));
-	const u32 bm_blocks = (ncell_all + 255u) / 256u < 1024u ? (ncell_all + 255u) / 256u : 1024u;
-	hipLaunchKernelGGL(k_dda_prepare<false>, dim3(pix_blocks + bm_blocks), dim3(256), 0, ctx->stream, d_active, ctx->p0,
-			   ctx->npix, ctx->cfg.width, (float *)nullptr, d_occluded, (u32 *)ctx->wscan.p, dcount,
-			   ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span, ncell_all, (u32 *)ctx->ubitmap.p, (u32 *)nullptr,
-			   dcount_next);
-	ctx->dda_turn = turn;
-	UGRT_HIP(hipGetLastError());
-	*list_out = (const u32 *)ctx->wscan.p;
-	*dcount_out = dcount;
 	return UGRT_OK;
 }
 

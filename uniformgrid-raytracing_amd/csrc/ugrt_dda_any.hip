@@ -2,8 +2,8 @@
 // (not in the reference).
 //
 // Spec: a ray is occluded iff some triangle in the list of some VISITED cell passes ugrt_trace_dda's exact test
-// (d_mt_core, same operands) with 0 < t < t_max.  The visited cells are those of ugrt_trace_dda's walk -- same slab
-// clip, entry cell, tmax / tdelta arithmetic, axis choice and dims-sum guard -- from the entry cell onwards for as long
+// (d_mt_core, same operands) with 0 < t < t_max.  The visited cells are those of ugrt_trace_dda's walk -- d_dda_clip,
+// d_dda_axes and d_dda_step of ugrt_dda.h, which the per-ray kernel calls too, and its dims-sum guard -- from the entry cell onwards for as long
 // as a cell's entry parameter (tenter, then the exit parameter of the cell before) is below t_max.  The result is an OR
 // over a fixed set of cells, so none of what the closest-hit kernels order their work by is needed here:
 //   * a lane (= ray) is done at its first accepted test, a wave leaves when no lane walks any more;
@@ -19,8 +19,8 @@
 #define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
 
 // ugrt_dda.hip
-int ugrt_dda_prepare_any(ugrt_ctx *ctx, const DGrid &g, const int *d_active, int *d_occluded, const u32 *d_span,
-			 const u32 **list_out, const u32 **dcount_out);
+int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
+		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out);
 
 // `occluded` of the band was cleared by the prepare kernel: only the flags of occluded rays are written
 template <bool REC>
@@ -43,53 +43,16 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
 		int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
 		bool walking = false, occ = false;
-		// set-up: the arithmetic of k_trace_dda_ray
 		if (inb) {
-			float tenter = 0.0f, texit = 3.0e38f;
 #pragma unroll
 			for (int k = 0; k < 3; k++) {
 				o[k] = rays[p * 6 + k];
 				d[k] = rays[p * 6 + 3 + k];
 			}
-#pragma unroll
-			for (int k = 0; k < 3; k++) {
-				float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
-				if (d[k] != 0.0f) {
-					float inv = 1.0f / d[k];
-					float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
-					if (t0 > t1) {
-						float s = t0;
-						t0 = t1;
-						t1 = s;
-					}
-					if (t0 > tenter)
-						tenter = t0;
-					if (t1 < texit)
-						texit = t1;
-				} else if (o[k] < lo || o[k] > hi) {
-					texit = -1.0f;
-				}
-			}
-			if (tenter <= texit) {
+			float tenter;
+			if (d_dda_clip(g, o, d, tenter)) {
 				walking = tenter < t_max; // the entry cell's entry parameter
-#pragma unroll
-				for (int k = 0; k < 3; k++) {
-					float pe = o[k] + tenter * d[k];
-					c[k] = d_dcell(g, k, pe);
-					if (d[k] > 0.0f) {
-						step[k] = 1;
-						tmax[k] = ((g.lo[k] + (float)(c[k] + 1) * g.cs[k]) - o[k]) / d[k];
-						tdelta[k] = g.cs[k] / d[k];
-					} else if (d[k] < 0.0f) {
-						step[k] = -1;
-						tmax[k] = ((g.lo[k] + (float)c[k] * g.cs[k]) - o[k]) / d[k];
-						tdelta[k] = -g.cs[k] / d[k];
-					} else {
-						step[k] = 0;
-						tmax[k] = 3.0e38f;
-						tdelta[k] = 3.0e38f;
-					}
-				}
+				d_dda_axes(g, o, d, tenter, c, step, tmax, tdelta);
 			}
 		}
 		int guard = g.dims[0] + g.dims[1] + g.dims[2] + 3;
@@ -104,23 +67,8 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 				if (planning) {
 					pvalid |= 1u << q;
 					pcell[q] = (u32)((c[0] * g.dims[1] + c[1]) * g.dims[2] + c[2]);
-					const int ax = (tmax[0] < tmax[1]) ? ((tmax[0] < tmax[2]) ? 0 : 2) : ((tmax[1] < tmax[2]) ? 1 : 2);
-					const float tnext = ax == 0 ? tmax[0] : (ax == 1 ? tmax[1] : tmax[2]);
-					// step along ax (written out: no dynamically indexed registers)
-					bool outside;
-					if (ax == 0) {
-						c[0] += step[0];
-						outside = step[0] == 0 || c[0] < 0 || c[0] >= g.dims[0];
-						tmax[0] += tdelta[0];
-					} else if (ax == 1) {
-						c[1] += step[1];
-						outside = step[1] == 0 || c[1] < 0 || c[1] >= g.dims[1];
-						tmax[1] += tdelta[1];
-					} else {
-						c[2] += step[2];
-						outside = step[2] == 0 || c[2] < 0 || c[2] >= g.dims[2];
-						tmax[2] += tdelta[2];
-					}
+					float tnext;
+					const bool outside = d_dda_step(g, c, step, tmax, tdelta, tnext);
 					if (outside || --guard <= 0 || !(tnext < t_max))
 						planning = false;
 				}
@@ -200,15 +148,15 @@ extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, c
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
 	UGRT_HIP(hipSetDevice(ctx->device));
 	const DGrid g = ugrt_dgrid_of(G);
-	const bool use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
-	const float4 *rec = use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
 	// launch shape (ugrt_ctx_set_option; no effect on results)
 	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
 	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	const u32 *list, *dcount;
-	int rc;
+	// the prepare launch in the form that writes no hit defaults (it clears the band's occlusion flags instead), always with
+	// the bitmap workgroups, never with the split walks' chunk table
+	u32 *list, *dcount;
 	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	rc = ugrt_dda_prepare_any(ctx, g, d_active, d_occluded, d_span, &list, &dcount);
+	const int rc = ugrt_dda_prepare(ctx, g, d_active, nullptr, d_occluded, d_span, true, nullptr, &list, &dcount);
 	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
 	if (rc)
 		return rc;
@@ -217,14 +165,9 @@ extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, c
 	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	if (use_rec)
-		hipLaunchKernelGGL(k_trace_dda_any<true>, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset,
-				   (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays, list, dcount, t_max, d_occluded, RPW,
-				   COOP, ctx->d_small + UGRT_DSMALL_TICKET);
-	else
-		hipLaunchKernelGGL(k_trace_dda_any<false>, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset,
-				   (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays, list, dcount, t_max, d_occluded, RPW,
-				   COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+	hipLaunchKernelGGL(rec ? k_trace_dda_any<true> : k_trace_dda_any<false>, dim3(blocks), dim3(64), 0, ctx->stream, g,
+			   d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays,
+			   (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET);
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;

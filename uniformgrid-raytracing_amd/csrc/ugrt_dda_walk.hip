@@ -1,6 +1,7 @@
 // ugrt_dda_walk.hip -- reflection bounce, window kernel (round 3; DESIGN.md A13, section 5 "Window DDA").
 //
-// Same specification and the same arithmetic as k_trace_dda_ray / k_trace_dda_beam (ugrt_dda.hip): clip, walk the
+// Same specification as k_trace_dda_ray (ugrt_dda.hip) and the same arithmetic (ugrt_dda.h: d_dda_clip as it stands,
+// d_dda_axes and d_dda_step in this kernel's packed form): clip, walk the
 // cells front to back (Amanatides & Woo), per cell every triangle in ascending id with the reference's
 // Moller-Trumbore (signed t, 0 < t < best), stop at the first cell whose best hit lies before the cell's exit.
 // What the round-2 beam kernel spent its time on, by its own phase stamps (profiles/r02_dda_phases.json), and
@@ -51,21 +52,13 @@ __global__ __launch_bounds__(256) void k_dda_sort_keys(DGrid g, const float *__r
 		keys[i] = 0xFFFFFFFFu >> 8;
 		return;
 	}
-	float o[3], d[3], tenter = 0.0f;
+	float o[3], d[3], tenter;
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
 		o[k] = rays[p * 6 + k];
 		d[k] = rays[p * 6 + 3 + k];
 	}
-#pragma unroll
-	for (int k = 0; k < 3; k++)
-		if (d[k] != 0.0f) {
-			const float inv = 1.0f / d[k];
-			const float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
-			const float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
-			const float tn = t0 < t1 ? t0 : t1;
-			tenter = tn > tenter ? tn : tenter;
-		}
+	d_dda_clip(g, o, d, tenter); // (a ray that misses the grid is keyed all the same)
 	u32 cell = 0;
 #pragma unroll
 	for (int k = 0; k < 3; k++)
@@ -198,36 +191,18 @@ __global__ __launch_bounds__(64, 3) void k_trace_dda_walk(DGrid g, const u32 *__
 		bool left = false;                      // (cut groups) the ray has left the grid (tcur is then the exit of its last cell) or misses it
 		u32 widx = 0u;                          // window number
 		u32 nwin = 0u;                          // windows this ray has walked
-		// set-up: exactly the arithmetic of the per-ray kernel and of the specification
+		// set-up: d_dda_clip, then d_dda_axes (ugrt_dda.h) in this kernel's packed form -- the same tmax / tdelta operations,
+		// the cell as its linear index and the steps left per axis; the two must agree
 		{
 			float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 };
 			if (inb) {
-				float tenter = 0.0f, texit = 3.0e38f;
 #pragma unroll
 				for (int k = 0; k < 3; k++) {
 					o[k] = rays[p * 6 + k];
 					d[k] = rays[p * 6 + 3 + k];
 				}
-#pragma unroll
-				for (int k = 0; k < 3; k++) {
-					float lo = g.lo[k], hi = g.lo[k] + g.cs[k] * (float)g.dims[k];
-					if (d[k] != 0.0f) {
-						float inv = 1.0f / d[k];
-						float t0 = (lo - o[k]) * inv, t1 = (hi - o[k]) * inv;
-						if (t0 > t1) {
-							float s = t0;
-							t0 = t1;
-							t1 = s;
-						}
-						if (t0 > tenter)
-							tenter = t0;
-						if (t1 < texit)
-							texit = t1;
-					} else if (o[k] < lo || o[k] > hi) {
-						texit = -1.0f;
-					}
-				}
-				if (tenter <= texit) {
+				float tenter;
+				if (d_dda_clip(g, o, d, tenter)) {
 					walking = true;
 					tcur = tenter;
 					const int stride[3] = { g.dims[1] * g.dims[2], g.dims[2], 1 };

@@ -652,8 +652,8 @@ extern "C" int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, c
 	const u32 C = (u32)ctx->nbx * (u32)ctx->nby;
 	const float *tex = ugrt_ctx_tex(ctx); // (stores the current camera's direction table first, if it is new)
 	// the kernels' REC variants gather the context's triangle records, if those were made of these arrays
-	const bool use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
-	const float4 *rec = use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	const bool use_rec = rec != nullptr;
 	const PrimaryOut out = { d_normal, d_t_value, d_ray_dir, d_shadowed, d_intersect_id };
 	if (ctx->cfg.slabs > 1) { // NUM_SLABS > 1: the slab walk of trace_kernel.cu:132-229, one wave per tile
 		ugrt_prof_begin(ctx, UGRT_ST_TRACE_PRIMARY);

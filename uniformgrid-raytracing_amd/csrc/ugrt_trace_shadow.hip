@@ -1321,8 +1321,8 @@ extern "C" int ugrt_trace_shadow(ugrt_ctx *ctx, const unsigned *d_value_list, co
 		return rc;
 	if (s.traced == 0 || s.n == 0)
 		return UGRT_OK;
-	s.use_rec = ctx->rec_valid && ctx->rec_verts == d_vertlist && ctx->rec_tris == d_trilist;
-	s.rec = s.use_rec ? (const float4 *)ctx->trirec.p : (const float4 *)nullptr;
+	s.rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	s.use_rec = s.rec != nullptr;
 	if ((rc = s.reserve()) || (rc = s.beams()) || (rc = s.cull()))
 		return rc;
 	if (!s.async && (s.P == 0 || s.G == 0))

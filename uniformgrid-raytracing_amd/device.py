@@ -150,7 +150,8 @@ class Context:
     def get_state(self, key):
         """Counters and findings of the context: "radix_launches", "sort_rank_atomic", "shadow_key_bits" (key bits the
         last shadow pass sorted its rays on), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
-        on the device)."""
+        on the device), "f2i_mismatches" (the same for the device's float -> integer conversions), "lane_reduce_mismatches"
+        (the tracers' DPP / permlane-swap reductions against __shfl_xor)."""
         v = C.c_longlong(0)
         check(lib.ugrt_ctx_get_state(self._h, key.encode(), C.byref(v)))
         return int(v.value)
