@@ -327,6 +327,25 @@ int ugrt_shade_add_shadows(ugrt_ctx *ctx, unsigned char *d_img, const int *d_is_
 int ugrt_shade_perlin(ugrt_ctx *ctx, unsigned char *d_img, const float *d_t_value, const float *d_ray_dir,
 		      const float *d_cam_position, const int *d_intersect_id);
 
+/* ---- device: several lights ----------------------
+ * The reference's frame loops over h_numLights (main.cu:148-203) but runs with one, and its shading kernels index
+ * light 0 (shader_kernel.cu:52-56); this is the shading for 1..UGRT_MAX_LIGHTS lights, own spec. */
+#define UGRT_MAX_LIGHTS 8
+/* ugrt_shade_simple + ugrt_shade_add_shadows once per light and the mean of the results, in one pass.  light_pos is
+ * host memory ([3 * num_lights], passed on by value); light l's flags are d_is_shadowed[l * W*H + p], indexed by
+ * absolute pixel p as every per-pixel array (the stacking of the reflection levels); d_is_shadowed may be NULL: no
+ * light is shadowed.  d_intersect_id is rewritten to material indices as ugrt_shade_simple does.  A pixel whose
+ * material index is out of range or whose t is not > 0 is black.  Every other pixel gets, per component,
+ * (sum over l of b_l) / num_lights in unsigned integers, where b_l is the byte ugrt_shade_simple would write with
+ * light l in place of ugrt_set_light_position's and the context's current camera block, divided by 3 (integer) where
+ * light l's flag == 1.  num_lights == 1 gives the bytes of ugrt_shade_simple + ugrt_shade_add_shadows.  Stage
+ * UGRT_ST_SHADE.  num_lights outside 1..UGRT_MAX_LIGHTS or a null argument other than d_is_shadowed: UGRT_EINVAL and
+ * nothing is enqueued. */
+int ugrt_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+		      const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+		      const float *d_mat_list, int num_materials, int num_lights, const float *light_pos,
+		      const int *d_is_shadowed);
+
 /* ---- device: reflection bounce (not in the reference) ---- */
 /* secondary rays for hit pixels whose material has reflect > 0 */
 int ugrt_reflect_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value,

@@ -54,6 +54,7 @@ FLAG_STRICT_TEXTURE = 8
 CHUNKS_ON_DEVICE = 0xFFFFFFFF
 GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM = 0, 1, 2
 MAX_REFLECT_DEPTH = 8  # UGRT_MAX_REFLECT_DEPTH
+MAX_LIGHTS = 8  # UGRT_MAX_LIGHTS
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -147,6 +148,7 @@ PROTOTYPES = {
     "ugrt_shade_spotlight": (C.c_int, [_P] * 9 + [C.c_int, _P]),
     "ugrt_shade_add_shadows": (C.c_int, [_P, _P, _P]),
     "ugrt_shade_perlin": (C.c_int, [_P] * 6),
+    "ugrt_shade_lights": (C.c_int, [_P] * 9 + [C.c_int, C.c_int, _F3, _P]),
     "ugrt_reflect_rays": (C.c_int, [_P] * 7 + [C.c_int, _P, _P, C.c_float, _P, _P]),
     "ugrt_trace_dda": (C.c_int, [_P] * 10),
     "ugrt_shade_reflect": (C.c_int, [_P] * 10 + [C.c_int] + [_P] * 6),

@@ -334,6 +334,48 @@ __device__ __forceinline__ void d_lambert(const CamBlock &cam, const float *poin
 	}
 }
 
+// d_lambert<false> for several lights, cut where the light enters.  d_lambert_view is the part
+// that does not know the light: the view-space point pv and the normalised view-space normal nv.  d_lambert_from is the
+// rest with an explicit light position in place of cam.light.  Together they are d_lambert<false>'s operations in
+// d_lambert<false>'s order per value, so color gets the same bits.
+__device__ __forceinline__ void d_lambert_view(const CamBlock &cam, const float *point, const float *normal, float *pv,
+					       float *nv)
+{
+	const float *cc = cam.cc;
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		pv[k] = cc[16 + k] * point[0] + cc[16 + 4 + k] * point[1] + cc[16 + 8 + k] * point[2];
+		nv[k] = cc[16 + k] * normal[0] + cc[16 + 4 + k] * normal[1] + cc[16 + 8 + k] * normal[2];
+	}
+	D_NORMALIZE(nv);
+}
+__device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float *light, const float *pv, const float *nv,
+					       float *color, const float *material)
+{
+	const float *cc = cam.cc;
+	float lpv[3], light_dir[3];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		lpv[k] = cc[16 + k] * light[0] + cc[16 + 4 + k] * light[1] + cc[16 + 8 + k] * light[2];
+	light_dir[0] = pv[0] - lpv[0];
+	light_dir[1] = pv[1] - lpv[1];
+	light_dir[2] = pv[2] - lpv[2];
+	D_NORMALIZE(light_dir);
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		color[k] += material[k] * 0.5f;
+	float dot_diffuse = D_DOT(light_dir, nv);
+	if (dot_diffuse > 0)
+		dot_diffuse *= 1;
+	else
+		dot_diffuse *= -1;
+	if (dot_diffuse > 0) {
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			color[k] += material[3 + k] * 1.0f * dot_diffuse;
+	}
+}
+
 // the reflection bounce's next ray: hit point P = o + t*d on the staged triangle tri
 // ({., e1, e2}: d_stage_triangle), n = normalize(e1 x e2) turned against d, out = {P + eps*n, d - 2(d.n)n}.
 // o is the camera for the first bounce (k_reflect_rays) and the ray's own origin after that (k_reflect_rays_next).

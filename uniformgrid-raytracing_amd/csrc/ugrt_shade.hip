@@ -388,6 +388,91 @@ extern "C" int ugrt_shade_add_shadows(ugrt_ctx *ctx, unsigned char *d_img, const
 	return UGRT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// several lights (the reference's loop over h_numLights, main.cu:148-203, runs with one and
+// its shading kernels index light 0): k_shade<false> and k_add_shadows once per light and the mean of the bytes, in
+// one pass over the per-pixel arrays.
+// ---------------------------------------------------------------------------
+struct LightsIn {
+	float pos[3 * UGRT_MAX_LIGHTS]; // by value: uniform over the launch, read from the kernarg segment
+	int count;
+};
+
+__global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsigned char *__restrict__ d_img,
+							      const float *__restrict__ dd_normal,
+							      const float *__restrict__ dd_t_value,
+							      const float *__restrict__ dd_dir,
+							      int *__restrict__ dd_intersect_id,
+							      const float *__restrict__ d_cam_pos,
+							      const int *__restrict__ mat_idx,
+							      const float *__restrict__ mat_list, int mat_count,
+							      LightsIn lights, const int *__restrict__ is_shadowed,
+							      size_t level, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	u32 sum[3] = { 0u, 0u, 0u };
+	int tri_intersected = dd_intersect_id[pixelID];
+	int idx = tri_intersected >= 0 ? mat_idx[tri_intersected] : tri_intersected; // as k_shade
+	float t_value = dd_t_value[pixelID];
+	dd_intersect_id[pixelID] = idx;
+	if (idx >= 0 && idx < mat_count && t_value > 0) {
+		float dir[3] = { dd_dir[pixelID * 3 + 0], dd_dir[pixelID * 3 + 1], dd_dir[pixelID * 3 + 2] };
+		float nrm[3] = { dd_normal[pixelID * 3 + 0], dd_normal[pixelID * 3 + 1], dd_normal[pixelID * 3 + 2] };
+		float point[3], material[6], pv[3], nv[3];
+#pragma unroll
+		for (int k = 0; k < 3; k++) {
+			point[k] = d_cam_pos[k] + t_value * dir[k];
+			material[k] = mat_list[idx * 6 + 3 + k];
+			material[3 + k] = mat_list[idx * 6 + 3 + k];
+		}
+		d_lambert_view(cam, point, nrm, pv, nv);
+		for (int l = 0; l < lights.count; l++) {
+			float color[3] = { 0.0f, 0.0f, 0.0f };
+			d_lambert_from(cam, &lights.pos[3 * l], pv, nv, color, material);
+			const bool dark = is_shadowed && is_shadowed[(size_t)l * level + (size_t)pixelID] == 1;
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				unsigned char b = d_to_u8(color[k] > 1.0f ? 1.0f : color[k]);
+				sum[k] += dark ? (u32)(b / 3) : (u32)b;
+			}
+		}
+	}
+	d_img[pixelID * 3 + 0] = (unsigned char)(sum[0] / (u32)lights.count);
+	d_img[pixelID * 3 + 1] = (unsigned char)(sum[1] / (u32)lights.count);
+	d_img[pixelID * 3 + 2] = (unsigned char)(sum[2] / (u32)lights.count);
+}
+
+extern "C" int ugrt_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+				 const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+				 const int *d_mat_idx, const float *d_mat_list, int num_materials, int num_lights,
+				 const float *light_pos, const int *d_is_shadowed)
+{
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, "shade_lights");
+	if (rc)
+		return rc;
+	if (!light_pos)
+		return ugrt_fail(UGRT_EINVAL, "shade_lights: null argument");
+	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
+		return ugrt_fail(UGRT_EINVAL, "shade_lights: num_lights %d is not in 1..%d", num_lights, UGRT_MAX_LIGHTS);
+	LightsIn lights = {};
+	for (int k = 0; k < 3 * num_lights; k++)
+		lights.pos[k] = light_pos[k];
+	lights.count = num_lights;
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_lights, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
+			   d_mat_idx, d_mat_list, num_materials, lights, d_is_shadowed,
+			   (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 // shader_kernel.cu:4-44 Noise / InterPolation / PerlinNoise with octaves = 1
 __device__ __forceinline__ float d_noise(int x)
 {

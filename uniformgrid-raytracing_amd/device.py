@@ -202,6 +202,15 @@ class Context:
         check(lib.ugrt_shade_simple(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids),
                                     _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list), num_materials))
 
+    def shade_lights(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, light_pos,
+                     is_shadowed=None):
+        """shade_simple + shade_add_shadows per light and the mean, in one pass.  light_pos: one
+        position (three host floats) per light; is_shadowed: the lights' flags stacked [L, W*H], or None."""
+        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
+        n = 0 if light_pos is None else len(light_pos)
+        check(lib.ugrt_shade_lights(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                    _ptr(mat_idx), _ptr(mat_list), num_materials, n, pos, _ptr(is_shadowed)))
+
     def shade_spotlight(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, dump=None):
         check(lib.ugrt_shade_spotlight(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids),
                                        _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list), num_materials, _ptr(dump)))

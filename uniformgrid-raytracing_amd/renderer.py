@@ -17,7 +17,8 @@ build -> 3D-DDA -> shade_reflect (not in the reference).  With
 3D-DDA) x (D-1) behind the first bounce, then shade_reflect_depth (DESIGN.md
 section 6).  With ``reflect_shadows=True`` the hits of every reflection level are tested against the
 light behind the level's 3D-DDA (occlusion rays -> any-hit walk) and the shading darkens the
-occluded levels.
+occluded levels.  With ``FrameSetup.lights`` the per-light part of the sequence runs once
+per light and one shading pass averages the lights (one-stream frame, no reflections).
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -27,7 +28,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_REFLECT_DEPTH
+from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -47,6 +48,45 @@ def check_reflect_shadows(reflect_shadows, reflect):
     if reflect_shadows and not reflect:
         raise ValueError("reflect_shadows=True needs reflect=True: it shadows the reflected hits")
     return bool(reflect_shadows)
+
+
+_CAMERA_KEYS = ("eye", "look", "up", "near", "far")
+
+
+def _three_floats(v):
+    v = tuple(float(x) for x in v)
+    if len(v) != 3:
+        raise ValueError("three floats expected, not %d" % len(v))
+    return v
+
+
+def check_lights(lights, reflect, two_streams):
+    """FrameSetup.lights as a list of (light_camera_params, (x, y, z)) with 1..MAX_LIGHTS entries, or ValueError (before
+    anything is enqueued).  Not with reflect (the reflection shading knows one light) and not in the two-stream or
+    banded frames (two_streams: they keep one light grid on a side context); DESIGN.md section 6.3."""
+    if reflect:
+        raise ValueError("lights cannot be combined with reflect=True: the reflection shading knows one light")
+    if two_streams:
+        raise ValueError("lights need the one-stream Renderer: the two-stream and banded frames keep one light grid")
+    try:
+        entries = list(lights)
+    except TypeError:
+        raise ValueError("lights must be a sequence of (light_camera, shading_light) pairs, not %r" % (lights,))
+    if not 1 <= len(entries) <= MAX_LIGHTS:
+        raise ValueError("lights must hold 1..%d entries, not %d" % (MAX_LIGHTS, len(entries)))
+    out = []
+    for k, entry in enumerate(entries):
+        try:
+            params, pos = entry
+            if not isinstance(params, dict):
+                raise TypeError("the light camera must be a dict")
+            for key in ("eye", "look", "up"):
+                _three_floats(params[key])
+            float(params["near"]), float(params["far"])
+            out.append((params, _three_floats(pos)))
+        except (TypeError, ValueError, KeyError) as e:
+            raise ValueError("lights[%d] is not (dict with %s, three floats): %r" % (k, "/".join(_CAMERA_KEYS), e))
+    return out
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -107,11 +147,18 @@ def sort_rays(c, b):
     b._num_chunks = c.sort_rays(b._d_map, b._prefix, deferred=True)
 
 
-def trace_shadows(c, f, b, light_grid):
-    """check_for_shadows through the light grid; light_grid: its grid_ptrs()."""
+def trace_shadows(c, f, b, light_grid, is_shadowed=None):
+    """check_for_shadows through the light grid; light_grid: its grid_ptrs().  is_shadowed: the flags the pass sets
+    (it only ever sets them, and skips the rays whose flag is set), f.is_shadowed unless given."""
     lvalue, lspan, loffset, _ = light_grid
-    c.trace_shadow(lvalue, f.d_verts, f.d_faces, lspan, loffset, f.t, f.dir, f.is_shadowed, b._d_map, b._prefix,
-                   b.cam_pos, b._num_chunks)
+    c.trace_shadow(lvalue, f.d_verts, f.d_faces, lspan, loffset, f.t, f.dir,
+                   f.is_shadowed if is_shadowed is None else is_shadowed, b._d_map, b._prefix, b.cam_pos, b._num_chunks)
+
+
+def shade_lights(c, f, cam_pos, lights, shadows):
+    """The Lambertian shading of every light and its shadows, averaged, in one pass."""
+    c.shade_lights(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.num_materials,
+                   [pos for _, pos in lights], f.shadowed_lights if shadows else None)
 
 
 def reflect_rays(c, f, cam_pos):
@@ -166,14 +213,18 @@ def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_sha
 
 
 class FrameSetup:
-    def __init__(self, camera, light_camera, shading_light, fovy=45.0):
+    def __init__(self, camera, light_camera, shading_light, fovy=45.0, lights=None):
+        """lights: a sequence of (light_camera_params, shading_light) pairs, 1..MAX_LIGHTS of them, that the
+        one-stream Renderer renders instead of light_camera / shading_light; None: the
+        single-light frame."""
         self.camera, self.light_camera, self.shading_light, self.fovy = camera, light_camera, shading_light, fovy
+        self.lights = lights
 
     @staticmethod
-    def from_scene(info, cam="ref"):
+    def from_scene(info, cam="ref", lights=None):
         cams = info["cameras"]
         return FrameSetup(cams[cam] if cam in cams else next(iter(cams.values())), info["light_camera"],
-                          info["shading_light"])
+                          info["shading_light"], lights=lights)
 
 
 def make_camera(params, fovy, aspect):
@@ -216,8 +267,16 @@ class _Frame:
         self.rays_levels = self.active_levels = self.hit_t_levels = self.hit_id_levels = None
         # reflect_shadows: the levels' occlusion flags, and the occlusion rays of the level that is being traced
         self.occluded_levels = self.occlusion_rays = self.occlusion_active = None
+        # FrameSetup.lights: the lights' shadow flags one behind the other (_ensure_light_buffers)
+        self.shadowed_lights = None
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
+
+    def _ensure_light_buffers(self, num_lights):
+        """shadowed_lights [L, W*H]: light l's is_shadowed, allocated once for the most lights asked for."""
+        t = self.torch
+        if self.shadowed_lights is None or self.shadowed_lights.shape[0] < num_lights:
+            self.shadowed_lights = t.empty((num_lights, self.N), dtype=t.int32, device=self.image.device)
 
     def _ensure_reflect_buffers(self, bounces=1, reflect_shadows=False):
         """rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)], allocated once for the
@@ -380,9 +439,13 @@ class Renderer(_Frame, _Band):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
-        point the primary shadow pass is cast from); occluded_levels holds the levels' flags."""
+        point the primary shadow pass is cast from); occluded_levels holds the levels' flags.
+        setup.lights (one-stream renderer, reflect=False): the shadow stage once per light into shadowed_lights, then one
+        Lambertian shading pass over all of them, whatever frame_cnt says."""
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
+        if getattr(setup, "lights", None) is not None:
+            return self._display_lights(setup, check_lights(setup.lights, reflect, self.aux is not None), shadows, shade)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
@@ -405,6 +468,27 @@ class Renderer(_Frame, _Band):
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
+
+    def _display_lights(self, setup, lights, shadows, shade):
+        """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
+        shadow stage into its row of shadowed_lights, then ONE shading pass.  dd_camcoords is the last light's when
+        the shading runs, as the reference's loop leaves it."""
+        ctx = self.ctx
+        if shadows:
+            self._ensure_light_buffers(len(lights))
+        camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
+        if shadows:
+            self.shadowed_lights[:len(lights)].zero_()  # the shadow pass only sets flags: rows of earlier frames are stale
+        for l, (params, _) in enumerate(lights):
+            use_light_camera(ctx, make_camera(params, setup.fovy, self.aspect))
+            if shadows:
+                map_rays(ctx, self, self)
+                build_grid(ctx, self, GRID_SPHERICAL, self.shards)
+                light_grid = ctx.grid_ptrs(GRID_SPHERICAL)
+                sort_rays(ctx, self)
+                trace_shadows(ctx, self, self, light_grid, self.shadowed_lights[l])
+        if shade:
+            shade_lights(ctx, self, self.cam_pos, lights, shadows)
 
     def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
@@ -594,6 +678,8 @@ class BandedRenderer(_Frame):
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False):
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
+        if getattr(setup, "lights", None) is not None:
+            check_lights(setup.lights, reflect, True)  # raises: one light grid on the side context
         t, aux, main, side = self.torch, self.aux, self.main_stream, self.side_stream
         if reflect:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
