@@ -282,6 +282,32 @@ int ugrt_geometry_changed(ugrt_ctx *ctx);
  * built-in one (same result). */
 int ugrt_sort_pairs(ugrt_ctx *ctx, const unsigned *d_keys_in, unsigned *d_keys_out, const unsigned *d_values_in,
 		    unsigned *d_values_out, size_t n, int key_bits, int use_library);
+/* The built-in radix sort in the forms the frame uses beyond ugrt_sort_pairs: 1 or 2 independent lists in shared
+ * launches (one histogram kernel, one kernel per pass level of 8 key bits; a list with fewer passes drops out), a pair
+ * count that only the device knows, and a sort in place.  Every argument but ctx is a host array of nlists entries;
+ * list j sorts n[j] pairs on key bits [0, key_bits[j]).  d_counts may be NULL; d_counts[j] NULL: n[j] is the count.
+ * Otherwise d_counts[j] points at one device word and n[j] is the capacity the launches are sized by: the first
+ * min(*d_counts[j], n[j]) outputs are the stable sort of the first min(*d_counts[j], n[j]) inputs and nothing is
+ * written behind them.  Inputs are left untouched unless list j is sorted in place: d_keys_in[j] == d_keys_out[j]
+ * together with d_values_in[j] == d_values_out[j] is accepted exactly when the list takes 2 or 4 passes (key_bits[j]
+ * in 9..16 or 25..32: the input is then read in the first pass only, which writes the context's own buffers).
+ * UGRT_EINVAL: nlists outside 1..2, key_bits[j] outside 1..32, a null argument (a list's arrays only with n[j] > 0), an
+ * in-place list with 1 or 3 passes, one of a list's two arrays aliased without the other, an output that is another
+ * array of the call.  Option "sort_library" does not apply.  No reference counterpart. */
+int ugrt_sort_pairs_lists(ugrt_ctx *ctx, int nlists, const unsigned *const *d_keys_in, unsigned *const *d_keys_out,
+			  const unsigned *const *d_values_in, unsigned *const *d_values_out, const size_t *n,
+			  const int *key_bits, const unsigned *const *d_counts);
+/* cudppScan(plan, out, in, n) with CUDPP_ADD on uint (cudpp/cudpp.h:426-471; call sites frustum_grid.h:249 inclusive,
+ * frustum_grid.h:361 exclusive, decision_data.h:209): the single-kernel prefix sum the builds and the ray sort run
+ * on, sums modulo 2^32, exposed like ugrt_sort_pairs.  inclusive != 0: d_out[i] = d_in[0] + ... + d_in[i], otherwise
+ * without d_in[i].  The arrays need no alignment beyond their words' (16-byte accesses are used where both allow them).
+ * n == 0 enqueues nothing.  A null argument with n > 0 or d_in == d_out: UGRT_EINVAL. */
+int ugrt_scan(ugrt_ctx *ctx, const unsigned *d_in, unsigned *d_out, size_t n, int inclusive);
+/* Two scans of n words each, which must not depend on each other, in ONE launch (the first half of the workgroups
+ * serves a, the second b).  UGRT_EINVAL as for ugrt_scan, and for d_out_a == d_out_b or an output that is the other
+ * scan's input. */
+int ugrt_scan_pair(ugrt_ctx *ctx, const unsigned *d_in_a, unsigned *d_out_a, const unsigned *d_in_b, unsigned *d_out_b,
+		   size_t n, int inclusive);
 
 /* ---- device: tracing --------------------------------------------------- */
 /* FrustumTracer::trace(...), frustum_tracer.h:20-23 -> rckernel_alpha */

@@ -139,6 +139,10 @@ PROTOTYPES = {
                                          C.POINTER(C.c_uint)]),
     "ugrt_geometry_changed": (C.c_int, [_P]),
     "ugrt_sort_pairs": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int, C.c_int]),
+    "ugrt_sort_pairs_lists": (C.c_int, [_P, C.c_int, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), C.POINTER(_P),
+                                        C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(_P)]),
+    "ugrt_scan": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
+    "ugrt_scan_pair": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int]),
     "ugrt_trace_primary": (C.c_int, [_P] * 11),
     "ugrt_map_rays_to_light": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_float]),
     "ugrt_sort_rays": (C.c_int, [_P, _P, _P, C.c_uint, C.POINTER(C.c_uint)]),

@@ -79,3 +79,46 @@ extern "C" int ugrt_sort_pairs(ugrt_ctx *ctx, const unsigned *d_keys_in, unsigne
 		return ugrt_prim_sort_pairs_rocprim(ctx, d_keys_in, d_keys_out, d_values_in, d_values_out, n, key_bits);
 	return ugrt_prim_sort_pairs(ctx, d_keys_in, d_keys_out, d_values_in, d_values_out, n, key_bits);
 }
+
+// ugrt_sort_pairs_batch as a C-ABI call: two lists per launch, device counts, in place (ugrt.h)
+extern "C" int ugrt_sort_pairs_lists(ugrt_ctx *ctx, int nlists, const unsigned *const *d_keys_in, unsigned *const *d_keys_out,
+				     const unsigned *const *d_values_in, unsigned *const *d_values_out, const size_t *n,
+				     const int *key_bits, const unsigned *const *d_counts)
+{
+	if (!ctx)
+		return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: null argument");
+	if (nlists < 1 || nlists > 2)
+		return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: %d lists (1..2)", nlists);
+	if (!d_keys_in || !d_keys_out || !d_values_in || !d_values_out || !n || !key_bits)
+		return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: null argument");
+	RsJob jobs[2];
+	const void *arr[2][4];
+	for (int j = 0; j < nlists; j++) {
+		if (key_bits[j] < 1 || key_bits[j] > 32)
+			return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: key_bits %d of list %d outside [1,32]", key_bits[j], j);
+		jobs[j] = { d_keys_in[j], d_values_in[j], d_keys_out[j], d_values_out[j], n[j], key_bits[j], d_counts ? d_counts[j] : nullptr };
+		arr[j][0] = d_keys_in[j], arr[j][1] = d_values_in[j], arr[j][2] = d_keys_out[j], arr[j][3] = d_values_out[j];
+		if (!n[j])
+			continue;
+		if (!d_keys_in[j] || !d_keys_out[j] || !d_values_in[j] || !d_values_out[j])
+			return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: null argument (list %d)", j);
+		const bool kalias = d_keys_in[j] == d_keys_out[j], valias = d_values_in[j] == d_values_out[j];
+		if (kalias != valias)
+			return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: list %d aliases only one of its two arrays", j);
+		// in place: an even number of passes reads the input in the first pass only, which writes the sort's own buffers
+		if (kalias && ((key_bits[j] + 7) / 8) % 2 != 0)
+			return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: list %d in place needs 2 or 4 passes, %d key bits take %d", j,
+					 key_bits[j], (key_bits[j] + 7) / 8);
+	}
+	// an output may be no other array of the call (but its own input, checked above)
+	for (int j = 0; j < nlists; j++)
+		for (int o = 2; o < 4 && n[j]; o++)
+			for (int k = 0; k < nlists; k++)
+				for (int a = 0; a < 4 && n[k]; a++) {
+					const bool self = k == j && (a == o || a == o - 2);
+					if (!self && arr[j][o] == arr[k][a])
+						return ugrt_fail(UGRT_EINVAL, "sort_pairs_lists: an output of list %d is another array of the call", j);
+				}
+	UGRT_HIP(hipSetDevice(ctx->device));
+	return ugrt_sort_pairs_batch(ctx, jobs, nlists);
+}

@@ -22,3 +22,30 @@ static int scan_u32(ugrt_ctx *ctx, const u32 *in, u32 *out, size_t n, bool inclu
 
 int ugrt_prim_inclusive_scan(ugrt_ctx *ctx, const u32 *in, u32 *out, size_t n) { return scan_u32(ctx, in, out, n, true); }
 int ugrt_prim_exclusive_scan(ugrt_ctx *ctx, const u32 *in, u32 *out, size_t n) { return scan_u32(ctx, in, out, n, false); }
+
+// the scans as C-ABI calls (ugrt.h): for callers that drive a stage themselves, and for the tests
+extern "C" int ugrt_scan(ugrt_ctx *ctx, const unsigned *d_in, unsigned *d_out, size_t n, int inclusive)
+{
+	if (!ctx || (n && (!d_in || !d_out)))
+		return ugrt_fail(UGRT_EINVAL, "scan: null argument");
+	if (n && d_in == d_out)
+		return ugrt_fail(UGRT_EINVAL, "scan: the output aliases the input");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	return scan_u32(ctx, d_in, d_out, n, inclusive != 0);
+}
+
+extern "C" int ugrt_scan_pair(ugrt_ctx *ctx, const unsigned *d_in_a, unsigned *d_out_a, const unsigned *d_in_b,
+			      unsigned *d_out_b, size_t n, int inclusive)
+{
+	if (!ctx || (n && (!d_in_a || !d_out_a || !d_in_b || !d_out_b)))
+		return ugrt_fail(UGRT_EINVAL, "scan_pair: null argument");
+	if (n && (d_in_a == d_out_a || d_in_b == d_out_b || d_out_a == d_out_b || d_in_a == d_out_b || d_in_b == d_out_a))
+		return ugrt_fail(UGRT_EINVAL, "scan_pair: an output aliases another array of the call");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	// (16-byte loads per input; the launch decides on 16-byte stores from both outputs)
+	const ScanLoadArray load_a = { d_in_a, (((uintptr_t)d_in_a) & 15u) == 0 ? 1u : 0u };
+	const ScanLoadArray load_b = { d_in_b, (((uintptr_t)d_in_b) & 15u) == 0 ? 1u : 0u };
+	if (inclusive)
+		return ugrt_scan_launch_pair<true>(ctx, load_a, d_out_a, load_b, d_out_b, n);
+	return ugrt_scan_launch_pair<false>(ctx, load_a, d_out_a, load_b, d_out_b, n);
+}

@@ -165,6 +165,27 @@ class Context:
         check(lib.ugrt_sort_pairs(self._h, _ptr(keys_in), _ptr(keys_out), _ptr(values_in), _ptr(values_out),
                                   keys_in.numel(), key_bits, 1 if library else 0))
 
+    def sort_pairs_lists(self, lists):
+        """The built-in sort of one or two lists in shared launches.  Each list is a tuple (keys_in, keys_out, values_in,
+        values_out, key_bits[, count[, n]]): count is None (a host count) or one device word holding the pair count, n
+        the count or the capacity (default keys_in.numel()); keys_in is keys_out and values_in is values_out sorts in
+        place (2 or 4 passes only)."""
+        m = len(lists)
+        full = [tuple(l) + (None,) * (7 - len(l)) for l in lists]
+        arr = lambda i: (_P * m)(*[_ptr(l[i]) for l in full])
+        ns = (C.c_size_t * m)(*[int(l[0].numel() if l[6] is None else l[6]) for l in full])
+        bits = (C.c_int * m)(*[int(l[4]) for l in full])
+        check(lib.ugrt_sort_pairs_lists(self._h, m, arr(0), arr(1), arr(2), arr(3), ns, bits, arr(5)))
+
+    def scan(self, d_in, d_out, inclusive=True, n=None):
+        """cudppScan: prefix sums modulo 2^32 of the first n (default d_in.numel()) words."""
+        check(lib.ugrt_scan(self._h, _ptr(d_in), _ptr(d_out), d_in.numel() if n is None else int(n), 1 if inclusive else 0))
+
+    def scan_pair(self, in_a, out_a, in_b, out_b, inclusive=True, n=None):
+        """Two independent scans of n (default in_a.numel()) words each in one launch."""
+        check(lib.ugrt_scan_pair(self._h, _ptr(in_a), _ptr(out_a), _ptr(in_b), _ptr(out_b),
+                                 in_a.numel() if n is None else int(n), 1 if inclusive else 0))
+
     # -- tracing -----------------------------------------------------------
     def trace_primary(self, value, span, offset, normal, t, ray_dir, shadowed, ids, verts, faces):
         check(lib.ugrt_trace_primary(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(normal), _ptr(t),
