@@ -220,7 +220,10 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * buffers and launches by what the build before needed plus a quarter, every kernel takes the real counts from
  * device memory, and a count that does not fit raises a flag instead of writing out of bounds:
  * ugrt_ctx_synchronize then returns UGRT_EOVERFLOW once (the frames since the last synchronisation are
- * incomplete) and the next calls run in the waiting form again, which sizes everything exactly.
+ * incomplete) and the next calls run in the waiting form again, which sizes everything exactly: every build and
+ * shadow pass up to the next ugrt_ctx_synchronize, so that the repeat of a frame which builds a grid or traces shadows
+ * more than once (one pass per light) succeeds whatever the passes need.  A pass takes its estimate from the pass
+ * before it, which in such a frame is another light's.
  * ugrt_grid_info.total_refs of such a build is final once the stream has been synchronised. */
 int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
 /* counters and findings of this context (no reference counterpart; the bench line and the tests read them):
@@ -453,6 +456,45 @@ int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d_img, const
 				      const float *d_reflect, int num_materials, const float *d_vertlist,
 				      const int *d_trilist, int depth, const float *d_rays, const int *d_active,
 				      const float *d_hit_t, const int *d_hit_id, const int *d_occluded);
+
+/* ---- device: reflections under several lights -----
+ * Sections 6.1-6.3 composed: the hits of the reflection levels are tested against every light in one launch per level,
+ * and one shading pass blends the levels under every light and averages the lights.  Per level: ugrt_trace_dda, ONE
+ * ugrt_occlusion_rays (with any light: only the origins are used), ugrt_trace_dda_any_lights; then
+ * ugrt_shade_reflect_lights. */
+/* The any-hit walk towards num_lights (1..UGRT_MAX_LIGHTS) points from one set of origins: for light l and pixel p of
+ * the band, d_occluded[l * W*H + p] is exactly what ugrt_trace_dda_any(..., t_max = 1) writes for the rays
+ * {o, light_pos[l] - o} (the subtraction per component in fp32, as ugrt_occlusion_rays forms it), o = the first three
+ * floats of d_orays[6 * p]; the last three are not read.  light_pos is host memory ([3 * num_lights], passed on by
+ * value).  Inactive pixels of the band get 0 in all num_lights layers; pixels outside the band and layers >= num_lights
+ * are not written.  One prepare launch and one ray list serve all lights; a wave's rays all walk towards one light.
+ * Options "any_rays_per_wave", "any_coop" and "dda_blocks" shape the launch as they shape ugrt_trace_dda_any's and
+ * change no result.  Stages UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of
+ * ugrt_trace_dda and what ugrt_reflect_rays_next told it alone.  num_lights out of range or a null argument:
+ * UGRT_EINVAL and nothing is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+			      const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
+			      int *d_occluded);
+/* ugrt_shade_reflect_depth_occluded + ugrt_shade_add_shadows once per light and the mean of the results, in one pass.
+ * light_pos is host memory ([3 * num_lights], passed on by value); light l's primary shadow flags are
+ * d_is_shadowed[l * W*H + p] (may be NULL: no light is shadowed), the occlusion flag of level j (1..depth) and light l
+ * is d_occluded[((j-1) * num_lights + l) * W*H + p] (may be NULL: nothing is occluded).  d_intersect_id is rewritten to
+ * material indices as ugrt_shade_reflect_depth does; a pixel whose material index is out of range is black.  Every
+ * other pixel walks its level chain once (it does not depend on the light); light l has its own accumulator, which
+ * receives ugrt_shade_reflect_depth's operations in its order with the levels' colours taken under light_pos[l]
+ * (clamped to 1; for j >= 1 divided by 3.0f where the flag == 1); b_l = its byte, divided by 3 (integer) where
+ * d_is_shadowed[l] == 1; the component is (sum over l of b_l) / num_lights in unsigned integers.  num_lights == 1 with
+ * ugrt_set_light_position's position gives the bytes of ugrt_shade_reflect_depth_occluded + ugrt_shade_add_shadows
+ * (d_occluded NULL: of ugrt_shade_reflect_depth); a frame without an active level-1 ray gives ugrt_shade_lights'.
+ * Stage UGRT_ST_SHADE.  depth outside 1..UGRT_MAX_REFLECT_DEPTH, num_lights outside 1..UGRT_MAX_LIGHTS or a null
+ * argument other than the two flag arrays: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_shade_reflect_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+			      const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+			      const int *d_mat_idx, const float *d_mat_list, const float *d_reflect, int num_materials,
+			      const float *d_vertlist, const int *d_trilist, int depth, const float *d_rays,
+			      const int *d_active, const float *d_hit_t, const int *d_hit_id, int num_lights,
+			      const float *light_pos, const int *d_is_shadowed, const int *d_occluded);
 
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */

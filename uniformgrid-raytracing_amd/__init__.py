@@ -161,6 +161,8 @@ PROTOTYPES = {
     "ugrt_occlusion_rays": (C.c_int, [_P] * 7 + [_F3, C.c_float, _P, _P]),
     "ugrt_trace_dda_any": (C.c_int, [_P] * 8 + [C.c_float, _P]),
     "ugrt_shade_reflect_depth_occluded": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 5),
+    "ugrt_trace_dda_any_lights": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P]),
+    "ugrt_shade_reflect_lights": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 4 + [C.c_int, _F3, _P, _P]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

@@ -300,3 +300,160 @@ extern "C" int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d
 				   d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, d_reflect, num_materials, d_vertlist,
 				   d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id, d_occluded);
 }
+
+// ---------------------------------------------------------------------------
+// reflections under several lights: the depth composition of k_shade_reflect_depth<OCC> and
+// k_add_shadows once per light and the mean of the bytes, in one pass.  The level chain (active_{j+1}, k_j, w) does not
+// know the light: it is walked once, every level's hit is fetched once and brought to view space once (d_lambert_view),
+// and shaded per light from registers (d_lambert_from) into the light's own accumulator.
+// ---------------------------------------------------------------------------
+struct ReflectLightsIn {
+	float pos[3 * UGRT_MAX_LIGHTS]; // by value: uniform over the launch, read from the kernarg segment
+	int count;
+	const int *is_shadowed; // [count][level], or null
+	const int *occluded;    // [depth][count][level], or null
+};
+
+__global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_lights(CamBlock cam, unsigned char *__restrict__ d_img,
+								      const float *__restrict__ dd_normal,
+								      const float *__restrict__ dd_t_value,
+								      const float *__restrict__ dd_dir,
+								      int *__restrict__ dd_intersect_id,
+								      const float *__restrict__ d_cam_pos,
+								      const int *__restrict__ mat_idx,
+								      const float *__restrict__ mat_list, int mat_count,
+								      DepthIn in, ReflectLightsIn lights, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	u32 sum[3] = { 0u, 0u, 0u };
+	int tri = dd_intersect_id[pixelID];
+	int idx = tri >= 0 ? mat_idx[tri] : tri;
+	dd_intersect_id[pixelID] = idx;
+	if (idx >= 0 && idx < mat_count) {
+		// the hit of the level at hand: lit = it has a colour at all; view-space point and normal; Kd
+		float pv[3] = { 0.0f, 0.0f, 0.0f }, nv[3] = { 0.0f, 0.0f, 0.0f }, kd[3];
+		float t_value = dd_t_value[pixelID];
+		bool lit = t_value > 0;
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			kd[k] = mat_list[idx * 6 + 3 + k];
+		if (lit) {
+			float point[3], nrm[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				point[k] = d_cam_pos[k] + t_value * dd_dir[pixelID * 3 + k];
+				nrm[k] = dd_normal[pixelID * 3 + k];
+			}
+			d_lambert_view(cam, point, nrm, pv, nv);
+		}
+		float acc[UGRT_MAX_LIGHTS][3];
+#pragma unroll
+		for (int l = 0; l < UGRT_MAX_LIGHTS; l++)
+			acc[l][0] = acc[l][1] = acc[l][2] = 0.0f;
+		float w = 1.0f, kr = in.reflect[idx];
+		// level j (0 = the primary hit) goes on when active_{j+1}, which lies at j * level
+		for (int j = 0;; j++) {
+			const size_t q = (size_t)j * in.level + (size_t)pixelID;
+			const bool goes_on = j < in.depth && in.active[q];
+			const float wt = goes_on ? w * (1.0f - kr) : w;
+			const float material[6] = { kd[0], kd[1], kd[2], kd[0], kd[1], kd[2] };
+			// (the lights unrolled with a uniform guard: acc stays in registers)
+#pragma unroll
+			for (int l = 0; l < UGRT_MAX_LIGHTS; l++) {
+				if (l < lights.count) {
+					float color[3] = { 0.0f, 0.0f, 0.0f };
+					if (lit) {
+						d_lambert_from(cam, &lights.pos[3 * l], pv, nv, color, material);
+						const bool dark = j >= 1 && lights.occluded &&
+								  lights.occluded[((size_t)(j - 1) * (size_t)lights.count + (size_t)l) * in.level + (size_t)pixelID] == 1;
+#pragma unroll
+						for (int k = 0; k < 3; k++) {
+							color[k] = color[k] > 1.0f ? 1.0f : color[k];
+							if (dark)
+								color[k] = color[k] / 3.0f;
+						}
+					}
+#pragma unroll
+					for (int k = 0; k < 3; k++)
+						acc[l][k] = acc[l][k] + wt * color[k];
+				}
+			}
+			if (!goes_on)
+				break;
+			w = w * kr;
+			// level j + 1's hit (d_level_color's inputs): a miss or a material out of range has no colour and leaves kr
+			lit = false;
+			int hid = in.hit_id[q];
+			if (hid >= 0) {
+				int hm = mat_idx[hid];
+				if (hm >= 0 && hm < mat_count) {
+					float t9[9], nn[3], hp[3];
+					float ht = in.hit_t[q];
+					kr = in.reflect[hm];
+					d_stage_triangle(in.verts, in.tris, (u32)hid, 0.0f, 0.0f, 0.0f, t9);
+					float *e1 = &t9[3], *e2 = &t9[6];
+#pragma unroll
+					for (int k = 0; k < 3; k++) {
+						hp[k] = in.rays[q * 6 + k] + ht * in.rays[q * 6 + 3 + k];
+						kd[k] = mat_list[hm * 6 + 3 + k];
+					}
+					D_NORMALIZE(e1);
+					D_NORMALIZE(e2);
+					D_CROSS(nn, e1, e2);
+					D_NORMALIZE(nn);
+					d_lambert_view(cam, hp, nn, pv, nv);
+					lit = true;
+				}
+			}
+		}
+#pragma unroll
+		for (int l = 0; l < UGRT_MAX_LIGHTS; l++) {
+			if (l < lights.count) {
+				const bool dark = lights.is_shadowed && lights.is_shadowed[(size_t)l * in.level + (size_t)pixelID] == 1;
+#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					unsigned char b = d_to_u8(acc[l][k]);
+					sum[k] += dark ? (u32)(b / 3) : (u32)b;
+				}
+			}
+		}
+	}
+	d_img[pixelID * 3 + 0] = (unsigned char)(sum[0] / (u32)lights.count);
+	d_img[pixelID * 3 + 1] = (unsigned char)(sum[1] / (u32)lights.count);
+	d_img[pixelID * 3 + 2] = (unsigned char)(sum[2] / (u32)lights.count);
+}
+
+extern "C" int ugrt_shade_reflect_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+					 const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+					 const int *d_mat_idx, const float *d_mat_list, const float *d_reflect, int num_materials,
+					 const float *d_vertlist, const int *d_trilist, int depth, const float *d_rays,
+					 const int *d_active, const float *d_hit_t, const int *d_hit_id, int num_lights,
+					 const float *light_pos, const int *d_is_shadowed, const int *d_occluded)
+{
+	if (!ctx || !d_img || !d_normal || !d_t_value || !d_ray_dir || !d_intersect_id || !d_cam_position || !d_mat_idx ||
+	    !d_mat_list || !d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id || !light_pos)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_lights: null argument");
+	if (depth < 1 || depth > UGRT_MAX_REFLECT_DEPTH)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_lights: depth %d outside 1..%d", depth, UGRT_MAX_REFLECT_DEPTH);
+	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_lights: num_lights %d is not in 1..%d", num_lights, UGRT_MAX_LIGHTS);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	DepthIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id,
+		       (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, depth, nullptr };
+	ReflectLightsIn lights = {};
+	for (int k = 0; k < 3 * num_lights; k++)
+		lights.pos[k] = light_pos[k];
+	lights.count = num_lights;
+	lights.is_shadowed = d_is_shadowed;
+	lights.occluded = d_occluded;
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_reflect_lights, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
+			   d_mat_idx, d_mat_list, num_materials, in, lights, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}

@@ -948,9 +948,9 @@ static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, in
 		G.est_w = ctx->h_pinned[UGRT_PIN_REPORT + 4 * gi + 1];
 	}
 	// asynchronous when asked for, when this grid has been built before (an estimate exists), when no overflow is
-	// pending, and when the wide list fits the rank kernel
+	// pending or being repaired, and when the wide list fits the rank kernel
 	const bool async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && G.have_est && G.est_w <= 3000u && ctx->cfg.slabs == 1 &&
-			   ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen;
+			   ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen && !ctx->overflow_repair;
 	if (!async) {
 		if (ugrt_reported_status(ctx) != 0u)
 			ctx->overflow_seen = true; // reported by ugrt_ctx_synchronize; until then every call waits and sizes exactly

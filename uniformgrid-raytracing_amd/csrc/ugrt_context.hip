@@ -270,8 +270,8 @@ extern "C" int ugrt_ctx_synchronize(ugrt_ctx *ctx)
 		return ugrt_fail(UGRT_EINVAL, "synchronize: null ctx");
 	UGRT_HIP(hipStreamSynchronize(ctx->stream));
 	// asynchronous builds / shadow passes: a count that did not fit the capacity it was given (sized by the call
-	// before) left that call's results incomplete.  Reported once; the next build and shadow pass run in the
-	// synchronous form and size the buffers exactly.
+	// before) left that call's results incomplete.  Reported once; every build and shadow pass up to the next
+	// synchronisation (the repeat of the frames) runs in the synchronous form and sizes the buffers exactly.
 	if (ugrt_reported_status(ctx) != 0u || ctx->overflow_seen) {
 		const unsigned bits = ugrt_reported_status(ctx);
 		ctx->overflow_seen = false;
@@ -283,10 +283,12 @@ extern "C" int ugrt_ctx_synchronize(ugrt_ctx *ctx)
 		for (int g = 0; g < 3; g++)
 			ctx->grid[g].have_est = false;
 		ctx->have_shadow_est = false;
+		ctx->overflow_repair = true;
 		return ugrt_fail(UGRT_EOVERFLOW, "an asynchronous call needed more room than its estimate gave it (status %u: "
 						  "1 grid build, 2 shadow candidate pairs, 4 shadow work items): the frames since the last "
 						  "synchronisation are incomplete, repeat them", bits);
 	}
+	ctx->overflow_repair = false;
 	return UGRT_OK;
 }
 

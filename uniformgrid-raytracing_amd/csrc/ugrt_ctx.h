@@ -195,6 +195,10 @@ struct ugrt_ctx {
 	std::vector<ProfPair> prof[UGRT_ST_COUNT];
 	std::vector<ProfPair> prof_pool;
 	bool overflow_seen = false; // an asynchronous call exceeded a capacity: reported by ugrt_ctx_synchronize
+	// the overflow has been reported: the repeat of the frames, every call up to the next synchronisation, waits and
+	// sizes exactly (a frame with several lights runs the light grid's build and the shadow pass once per light: an
+	// estimate taken from the light before would fail the repeat as it failed the frame)
+	bool overflow_repair = false;
 	// asynchronous shadow pass: candidate pairs and beams of the last pass
 	u32 est_pairs = 0, est_beams = 0;
 	bool have_shadow_est = false, shadow_async_pending = false;

@@ -14,6 +14,8 @@
 //   * a short list is tested by its lane; a long one by the wave, 64 triangles per round with the owner's ray
 //     broadcast, and a round is accepted with one ballot: no 64-bit minimum, no LDS, no list position.
 // The kernel reads the grid and the rays and writes its flags: it neither reads nor writes the split walks' history.
+// ugrt_trace_dda_any_lights is the same kernel over (light, ray group): the walk towards several
+// points from one set of origins, with one prepare launch and one ray list.
 #include "ugrt_dda.h"
 
 #define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
@@ -22,21 +24,58 @@
 int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
 		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out);
 
-// `occluded` of the band was cleared by the prepare kernel: only the flags of occluded rays are written
-template <bool REC>
+// What the rays of a launch aim at.  AnyRays: the rays as they are stored, up to t_max (ugrt_trace_dda_any).  AnyLights: from
+// the stored origins towards num_lights points (ugrt_trace_dda_any_lights): the index space is
+// (light, ray group), light-major -- group G of the launch is group G % per_light of the ray list under light
+// G / per_light, so a wave never mixes lights, its light's position is three scalars of the by-value block, and waves
+// that run side by side walk neighbouring rays towards one light.  The direction light - o is formed in the kernel, per
+// component, as k_occlusion_rays forms it: the rays' own last three floats are not read.  The light lies at t = 1, and
+// light l's flags lie at l * level.
+struct AnyRays {
+	typedef float Arg; // t_max
+	static constexpr bool lights = false;
+};
+struct AnyLights {
+	struct Arg {
+		float pos[3 * UGRT_MAX_LIGHTS]; // by value: uniform over the launch, read from the kernarg segment
+		int count;
+		size_t level; // W*H
+	};
+	static constexpr bool lights = true;
+};
+
+// `occluded` of the band was cleared by the prepare kernel (AnyLights: layer 0; the layers behind by the host call): only
+// the flags of occluded rays are written
+template <bool REC, class Aim>
 __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__restrict__ value_list,
 							const u32 *__restrict__ span, const u32 *__restrict__ offset,
 							const u32 *__restrict__ bitmap, const float *__restrict__ verts,
 							const int *__restrict__ tris, const float4 *__restrict__ rec,
 							const float *__restrict__ rays, const u32 *__restrict__ list,
-							const u32 *__restrict__ count_p, float t_max, int *__restrict__ occluded,
+							const u32 *__restrict__ count_p, const typename Aim::Arg aim, int *__restrict__ occluded,
 							u32 RPW, u32 COOP, u32 *__restrict__ ticket)
 {
 	const int lane = threadIdx.x;
 	const u32 count = *count_p;
+	float t_max;
+	if constexpr (Aim::lights)
+		t_max = 1.0f;
+	else
+		t_max = aim;
+	// AnyLights: the ray count is the device's, so is the number of groups per light (no ray: no group, no division)
+	u32 per_light = 0u, groups = 0u;
+	if constexpr (Aim::lights) {
+		per_light = (count + RPW - 1u) / RPW;
+		groups = per_light * (u32)aim.count;
+	}
 	// groups of RPW rays, the first gridDim.x by workgroup id, the others drawn from the ticket
-	for (u32 grp = blockIdx.x; grp * RPW < count;) {
-		const u32 slot = grp * RPW + (u32)lane;
+	for (u32 grp = blockIdx.x; Aim::lights ? grp < groups : grp * RPW < count;) {
+		u32 light = 0u, lgrp = grp; // (uniform)
+		if constexpr (Aim::lights) {
+			light = grp / per_light;
+			lgrp = grp - light * per_light;
+		}
+		const u32 slot = lgrp * RPW + (u32)lane;
 		bool inb = (u32)lane < RPW && slot < count;
 		const int p = inb ? (int)list[slot] : 0;
 		inb = inb && p != -1; // (padding: k_dda_prepare)
@@ -47,7 +86,10 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 #pragma unroll
 			for (int k = 0; k < 3; k++) {
 				o[k] = rays[p * 6 + k];
-				d[k] = rays[p * 6 + 3 + k];
+				if constexpr (Aim::lights)
+					d[k] = aim.pos[3u * light + (u32)k] - o[k];
+				else
+					d[k] = rays[p * 6 + 3 + k];
 			}
 			float tenter;
 			if (d_dda_clip(g, o, d, tenter)) {
@@ -127,8 +169,12 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 			}
 			walking = walking && planning; // (planning: the walk goes on behind this window)
 		}
-		if (occ)
-			occluded[p] = 1;
+		if (occ) {
+			if constexpr (Aim::lights)
+				(occluded + (size_t)light * aim.level)[p] = 1; // (the layer's base is uniform)
+			else
+				occluded[p] = 1;
+		}
 		if (lane == 0)
 			grp = gridDim.x + atomicAdd(ticket, 1u);
 		grp = (u32)__builtin_amdgcn_readfirstlane((int)grp);
@@ -165,9 +211,67 @@ extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, c
 	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	hipLaunchKernelGGL(rec ? k_trace_dda_any<true> : k_trace_dda_any<false>, dim3(blocks), dim3(64), 0, ctx->stream, g,
-			   d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays,
+	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays> : k_trace_dda_any<false, AnyRays>), dim3(blocks), dim3(64), 0,
+			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays,
 			   (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					 const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
+					 int *d_occluded)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !light_pos ||
+	    !d_occluded)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_lights: null argument");
+	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_lights: num_lights %d is not in 1..%d", num_lights, UGRT_MAX_LIGHTS);
+	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	if (!G.valid)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const DGrid g = ugrt_dgrid_of(G);
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	AnyLights::Arg lights = {};
+	for (int k = 0; k < 3 * num_lights; k++)
+		lights.pos[k] = light_pos[k];
+	lights.count = num_lights;
+	lights.level = (size_t)ctx->cfg.width * (size_t)ctx->cfg.height;
+	// launch shape: ugrt_trace_dda_any's options
+	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
+	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
+	// ONE prepare launch and one ray list for all lights, taken as ugrt_trace_dda_any takes them (the turn of the ray
+	// counters, the ticket, the bitmap); it clears layer 0 of the band's flags, the layers behind are cleared here in
+	// stream order: one fill where the band is the frame (the layers are contiguous), one per layer otherwise
+	const size_t level = lights.level;
+	u32 *list, *dcount;
+	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
+	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, d_occluded, d_span, true, nullptr, &list, &dcount);
+	hipError_t he = hipSuccess;
+	if (!rc && num_lights > 1) {
+		if ((size_t)ctx->npix == level)
+			he = hipMemsetAsync(d_occluded + level, 0, (size_t)(num_lights - 1) * level * sizeof(int), ctx->stream);
+		else
+			for (int l = 1; l < num_lights && he == hipSuccess; l++)
+				he = hipMemsetAsync(d_occluded + (size_t)l * level + (size_t)ctx->p0, 0, (size_t)ctx->npix * sizeof(int),
+						    ctx->stream);
+	}
+	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
+	if (rc)
+		return rc;
+	UGRT_HIP(he);
+	// persistent single-wave workgroups over (light, group); "dda_blocks" caps them as it caps ugrt_trace_dda's
+	int blocks = launch_blocks_for(((u32)ctx->npix / RPW + 1u) * (u32)num_lights);
+	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
+		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
+	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
+	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights> : k_trace_dda_any<false, AnyLights>), dim3(blocks), dim3(64), 0,
+			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
+			   (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
+			   ctx->d_small + UGRT_DSMALL_TICKET);
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;

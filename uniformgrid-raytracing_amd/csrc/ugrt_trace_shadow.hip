@@ -1102,7 +1102,8 @@ int ShadowPass::cull()
 		ctx->est_pairs = ctx->h_pinned[UGRT_PIN_SHADOW];
 		ctx->est_beams = ctx->h_pinned[UGRT_PIN_SHADOW + 1];
 	}
-	async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && ctx->have_shadow_est && ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen;
+	async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && ctx->have_shadow_est && ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen &&
+		!ctx->overflow_repair;
 	if (!async && ugrt_reported_status(ctx) != 0u)
 		ctx->overflow_seen = true;
 	size_t cap, want = (size_t)4 << 22; // bytes per candidate buffer

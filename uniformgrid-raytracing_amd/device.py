@@ -296,6 +296,27 @@ class Context:
                                                     _ptr(rays), _ptr(active), _ptr(hit_t), _ptr(hit_id),
                                                     _ptr(occluded)))
 
+    # -- reflections under several lights -------------
+    def trace_dda_any_lights(self, value, span, offset, verts, faces, orays, oactive, light_pos, occluded):
+        """occluded[l, p] = trace_dda_any's flag (t_max 1) of the ray from orays' origin of p towards light_pos[l]; light_pos:
+        one point (three host floats) per light; occluded: the lights' flags stacked [L, W*H]."""
+        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
+        n = 0 if light_pos is None else len(light_pos)
+        check(lib.ugrt_trace_dda_any_lights(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                            _ptr(orays), _ptr(oactive), n, pos, _ptr(occluded)))
+
+    def shade_reflect_lights(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, reflect, num_materials,
+                             verts, faces, depth, rays, active, hit_t, hit_id, light_pos, is_shadowed=None,
+                             occluded=None):
+        """shade_reflect_depth_occluded + shade_add_shadows per light and the mean, in one pass.  light_pos: one position
+        (three host floats) per light; is_shadowed: [L, W*H] or None; occluded: [depth, L, W*H] or None."""
+        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
+        n = 0 if light_pos is None else len(light_pos)
+        check(lib.ugrt_shade_reflect_lights(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids),
+                                            _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list), _ptr(reflect), num_materials,
+                                            _ptr(verts), _ptr(faces), int(depth), _ptr(rays), _ptr(active), _ptr(hit_t),
+                                            _ptr(hit_id), n, pos, _ptr(is_shadowed), _ptr(occluded)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

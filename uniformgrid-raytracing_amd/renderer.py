@@ -18,7 +18,8 @@ build -> 3D-DDA -> shade_reflect (not in the reference).  With
 section 6).  With ``reflect_shadows=True`` the hits of every reflection level are tested against the
 light behind the level's 3D-DDA (occlusion rays -> any-hit walk) and the shading darkens the
 occluded levels.  With ``FrameSetup.lights`` the per-light part of the sequence runs once
-per light and one shading pass averages the lights (one-stream frame, no reflections).
+per light and one shading pass averages the lights (one-stream frame, no reflections); with
+``reflect_lights=True`` as well, the reflections are rendered under all of them.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -60,11 +61,23 @@ def _three_floats(v):
     return v
 
 
-def check_lights(lights, reflect, two_streams):
+def check_reflect_lights(reflect_lights, reflect, lights):
+    """A bool, and only with reflect and FrameSetup.lights, or ValueError (before anything is enqueued)."""
+    if not isinstance(reflect_lights, (bool, np.bool_)):
+        raise ValueError("reflect_lights must be a bool, not %r" % (reflect_lights,))
+    if reflect_lights and not reflect:
+        raise ValueError("reflect_lights=True needs reflect=True: it renders the reflections under every light")
+    if reflect_lights and lights is None:
+        raise ValueError("reflect_lights=True needs FrameSetup.lights")
+    return bool(reflect_lights)
+
+
+def check_lights(lights, reflect, two_streams, reflect_lights=False):
     """FrameSetup.lights as a list of (light_camera_params, (x, y, z)) with 1..MAX_LIGHTS entries, or ValueError (before
-    anything is enqueued).  Not with reflect (the reflection shading knows one light) and not in the two-stream or
-    banded frames (two_streams: they keep one light grid on a side context); DESIGN.md section 6.3."""
-    if reflect:
+    anything is enqueued).  Not with reflect unless reflect_lights says so (the reflection shading of sections 6.1 and 6.2
+    knows one light; DESIGN.md section 6.4 is the frame that knows all) and not in the two-stream or banded frames
+    (two_streams: they keep one light grid on a side context); DESIGN.md section 6.3."""
+    if reflect and not reflect_lights:
         raise ValueError("lights cannot be combined with reflect=True: the reflection shading knows one light")
     if two_streams:
         raise ValueError("lights need the one-stream Renderer: the two-stream and banded frames keep one light grid")
@@ -161,17 +174,29 @@ def shade_lights(c, f, cam_pos, lights, shadows):
                    [pos for _, pos in lights], f.shadowed_lights if shadows else None)
 
 
+def shade_reflect_lights(c, f, cam_pos, lights, bounces, shadows, reflect_shadows):
+    """The reflection levels blended under every light, its shadows and its occluded levels, averaged, in one pass
+    (DESIGN.md section 6.4)."""
+    c.shade_reflect_lights(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.d_reflect,
+                           f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels, f.active_levels, f.hit_t_levels,
+                           f.hit_id_levels, [pos for _, pos in lights], f.shadowed_lights if shadows else None,
+                           f.occluded_lights if reflect_shadows else None)
+
+
 def reflect_rays(c, f, cam_pos):
     """Level 1's secondary rays from the primary hits."""
     c.reflect_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
                    f.d_faces, f.reflect_eps, f.rays, f.active)
 
 
-def trace_reflections(c, f, bounces, shadow_light=None):
+def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
     """3D-DDA of level 1 through c's uniform grid, then levels 2..bounces (next rays -> 3D-DDA) behind it with no
     host wait (a level without an active ray costs the DDA's prepare kernel and an empty persistent launch).
     shadow_light (reflect_shadows: the light camera's eye, three host floats): behind every level's 3D-DDA its hits'
-    occlusion rays towards that point and the any-hit walk up to it (t < 1) into f.occluded_levels."""
+    occlusion rays towards that point and the any-hit walk up to it (t < 1) into f.occluded_levels.
+    shadow_lights (reflect_lights with reflect_shadows: the eyes of the L light cameras): the occlusion rays ONCE per
+    level (towards the first eye; only their origins are used) and one any-hit launch towards all L eyes into level j's
+    [L, N] layers of f.occluded_lights."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     rays, active, hit_t, hit_id = f.rays, f.active, f.hit_t, f.hit_id
     for j in range(bounces):
@@ -186,6 +211,11 @@ def trace_reflections(c, f, bounces, shadow_light=None):
                              f.occlusion_rays, f.occlusion_active)
             c.trace_dda_any(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active, 1.0,
                             f.occluded_levels[j])
+        if shadow_lights is not None:
+            c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_lights[0], f.reflect_eps,
+                             f.occlusion_rays, f.occlusion_active)
+            c.trace_dda_any_lights(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active,
+                                   shadow_lights, f.occluded_lights[j])
 
 
 def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
@@ -269,6 +299,9 @@ class _Frame:
         self.occluded_levels = self.occlusion_rays = self.occlusion_active = None
         # FrameSetup.lights: the lights' shadow flags one behind the other (_ensure_light_buffers)
         self.shadowed_lights = None
+        # reflect_lights with reflect_shadows: the levels' occlusion flags per light, a contiguous [D, L, W*H] view of
+        # _occluded_lights_store (_ensure_reflect_lights_buffers)
+        self.occluded_lights = self._occluded_lights_store = None
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -277,6 +310,21 @@ class _Frame:
         t = self.torch
         if self.shadowed_lights is None or self.shadowed_lights.shape[0] < num_lights:
             self.shadowed_lights = t.empty((num_lights, self.N), dtype=t.int32, device=self.image.device)
+
+    def _ensure_reflect_lights_buffers(self, bounces, num_lights, reflect_shadows):
+        """The reflect buffers, and with reflect_shadows occluded_lights [bounces, num_lights, W*H]: a view of a store that
+        is allocated once for the most (D, L) asked for, contiguous so that the kernels' light stride is this frame's L;
+        the occlusion rays and their active flags are one level's, as in the single-light frame."""
+        t, N, dev = self.torch, self.N, self.image.device
+        self._ensure_reflect_buffers(bounces, False)
+        if not reflect_shadows:
+            return
+        if self._occluded_lights_store is None or self._occluded_lights_store.numel() < bounces * num_lights * N:
+            self._occluded_lights_store = t.empty(bounces * num_lights * N, dtype=t.int32, device=dev)
+        self.occluded_lights = self._occluded_lights_store[:bounces * num_lights * N].view(bounces, num_lights, N)
+        if self.occlusion_rays is None:
+            self.occlusion_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.occlusion_active = t.empty(N, dtype=t.int32, device=dev)
 
     def _ensure_reflect_buffers(self, bounces=1, reflect_shadows=False):
         """rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)], allocated once for the
@@ -435,15 +483,23 @@ class Renderer(_Frame, _Band):
             self._worker.join()
             self._worker = None
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
+                reflect_lights=False):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
         point the primary shadow pass is cast from); occluded_levels holds the levels' flags.
         setup.lights (one-stream renderer, reflect=False): the shadow stage once per light into shadowed_lights, then one
-        Lambertian shading pass over all of them, whatever frame_cnt says."""
+        Lambertian shading pass over all of them, whatever frame_cnt says.
+        reflect_lights (one-stream renderer; needs reflect=True and setup.lights): the reflections of depth `bounces` under
+        all of setup.lights -- per light its shadow stage, per level one any-hit launch towards every light (with
+        reflect_shadows; occluded_lights holds the flags [D, L, W*H]), one shading pass."""
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
+        reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
+        if reflect_lights:
+            lights = check_lights(setup.lights, reflect, self.aux is not None, True)
+            return self._display_reflect_lights(setup, lights, shadows, shade, bounces, reflect_shadows)
         if getattr(setup, "lights", None) is not None:
             return self._display_lights(setup, check_lights(setup.lights, reflect, self.aux is not None), shadows, shade)
         if reflect and shade:
@@ -489,6 +545,36 @@ class Renderer(_Frame, _Band):
                 trace_shadows(ctx, self, self, light_grid, self.shadowed_lights[l])
         if shade:
             shade_lights(ctx, self, self.cam_pos, lights, shadows)
+
+    def _display_reflect_lights(self, setup, lights, shadows, shade, bounces, reflect_shadows):
+        """_display_lights' camera pass and per-light shadow stages, then the reflection levels once (the uniform grid and
+        the reflected rays do not know the light) with every level's hits tested against the eyes of all light cameras in
+        one launch, then ONE shading pass.  No host wait is added."""
+        ctx = self.ctx
+        if shadows:
+            self._ensure_light_buffers(len(lights))
+        if shade:
+            self._ensure_reflect_lights_buffers(bounces, len(lights), reflect_shadows)
+        camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
+        if shadows:
+            self.shadowed_lights[:len(lights)].zero_()  # the shadow pass only sets flags: rows of earlier frames are stale
+        eyes = []
+        for l, (params, _) in enumerate(lights):
+            lcam = make_camera(params, setup.fovy, self.aspect)
+            eyes.append(tuple(float(x) for x in lcam.worldori[:3]))
+            use_light_camera(ctx, lcam)
+            if shadows:
+                map_rays(ctx, self, self)
+                build_grid(ctx, self, GRID_SPHERICAL, self.shards)
+                light_grid = ctx.grid_ptrs(GRID_SPHERICAL)
+                sort_rays(ctx, self)
+                trace_shadows(ctx, self, self, light_grid, self.shadowed_lights[l])
+        if not shade:
+            return
+        reflect_rays(ctx, self, self.cam_pos)
+        build_grid(ctx, self, GRID_UNIFORM, self.shards)
+        trace_reflections(ctx, self, bounces, shadow_lights=eyes if reflect_shadows else None)
+        shade_reflect_lights(ctx, self, self.cam_pos, lights, bounces, shadows, reflect_shadows)
 
     def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
