@@ -496,6 +496,43 @@ int ugrt_shade_reflect_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *
 			      const int *d_active, const float *d_hit_t, const int *d_hit_id, int num_lights,
 			      const float *light_pos, const int *d_is_shadowed, const int *d_occluded);
 
+/* ---- device: ambient occlusion --------------------
+ * How enclosed a primary hit is: num_dirs short rays over the hemisphere of its normal, walked through the uniform grid
+ * with the any-hit walk of section 6.2, and a last integer pass that scales the image by the share of open rays.  Per
+ * frame: ugrt_ao_rays + ugrt_trace_dda_any_hemi before the shading call that rewrites the ids, ugrt_shade_ao behind the
+ * shading (and ugrt_shade_add_shadows).  All arithmetic is fp32 without contraction. */
+#define UGRT_MAX_AO_DIRS 32
+/* The hemisphere's origins and normals from the primary hits, for the context's band; the primary arrays are read as
+ * ugrt_reflect_rays reads them (triangle ids: before any shading call).  For a pixel with d_t_value[p] > 0 and
+ * d_intersect_id[p] >= 0, whatever its material: d_orays[6 * p ..] = {o', n} and d_oactive[p] = 1, with
+ * P = cam + t*d, n = normalize(e1 x e2) turned so that d.n <= 0 and o' = P + eps*n (the origin and the flipped normal of
+ * ugrt_reflect_rays); every other pixel: six zeros and 0.  Stage UGRT_ST_REFLECT_GEN.  The call says nothing to the
+ * ugrt_trace_dda that follows.  A null argument: UGRT_EINVAL. */
+int ugrt_ao_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
+		 const int *d_intersect_id, const float *d_vertlist, const int *d_trilist, float eps, float *d_orays,
+		 int *d_oactive);
+/* The any-hit walk along num_dirs (1..UGRT_MAX_AO_DIRS) directions of the hemisphere over each stored normal: for an
+ * active pixel p of the band, bit s of d_mask[p] is exactly what ugrt_trace_dda_any(..., t_max = radius) writes for the
+ * ray {o, D_s}; o = floats 0..2 and n = floats 3..5 of d_orays[6 * p].  dirs is host memory ([3 * num_dirs], passed on by
+ * value): local directions (x_s, y_s, z_s) with z along the normal.  The basis: a = the index of the smallest |n[k]|
+ * (strict <, 1 against 0, then 2 against the winner: ties go to the lowest k); u = n x e_a, i.e. (0, n2, -n1),
+ * (-n2, 0, n0) or (n1, -n0, 0); T = u * (1 / sqrt(u0*u0 + u1*u1 + u2*u2)); B = n x T, each component n_i*T_j - n_j*T_i;
+ * D_s[k] = (x_s*T[k] + y_s*B[k]) + z_s*n[k].  Directions are not normalised: radius is measured in units of |D_s|.  Bits
+ * >= num_dirs are 0, inactive pixels of the band get 0, pixels outside the band are not written.  One prepare launch
+ * and one ray list serve all directions; a wave's rays all walk along one local direction; the directions are formed in
+ * registers and never stored.  Options "any_rays_per_wave", "any_coop" and "dda_blocks" shape the launch as they shape
+ * ugrt_trace_dda_any's and change no result.  Stages UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk
+ * history of ugrt_trace_dda and what ugrt_reflect_rays_next told it alone.  num_dirs out of range, radius <= 0 or NaN, or
+ * a null argument: UGRT_EINVAL and nothing is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+			    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
+			    const int *d_oactive, int num_dirs, const float *dirs, float radius, unsigned *d_mask);
+/* The image scaled by the share of open hemisphere rays, for the context's band: open = num_dirs - popcount(d_mask[p] &
+ * the low num_dirs bits), and each of the pixel's three bytes b becomes (b * open) / num_dirs in unsigned 32-bit
+ * integers.  A zero mask leaves the pixel as it is.  Stage UGRT_ST_SHADE.  num_dirs outside 1..UGRT_MAX_AO_DIRS or a null
+ * argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_dirs);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

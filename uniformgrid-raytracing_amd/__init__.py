@@ -55,6 +55,7 @@ CHUNKS_ON_DEVICE = 0xFFFFFFFF
 GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM = 0, 1, 2
 MAX_REFLECT_DEPTH = 8  # UGRT_MAX_REFLECT_DEPTH
 MAX_LIGHTS = 8  # UGRT_MAX_LIGHTS
+MAX_AO_DIRS = 32  # UGRT_MAX_AO_DIRS
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -163,6 +164,9 @@ PROTOTYPES = {
     "ugrt_shade_reflect_depth_occluded": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 5),
     "ugrt_trace_dda_any_lights": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P]),
     "ugrt_shade_reflect_lights": (C.c_int, [_P] * 10 + [C.c_int, _P, _P, C.c_int] + [_P] * 4 + [C.c_int, _F3, _P, _P]),
+    "ugrt_ao_rays": (C.c_int, [_P] * 7 + [C.c_float, _P, _P]),
+    "ugrt_trace_dda_any_hemi": (C.c_int, [_P] * 8 + [C.c_int, _F3, C.c_float, _P]),
+    "ugrt_shade_ao": (C.c_int, [_P, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

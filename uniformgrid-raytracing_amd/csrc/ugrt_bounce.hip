@@ -127,6 +127,62 @@ extern "C" int ugrt_occlusion_rays(ugrt_ctx *ctx, const float *d_rays, const int
 	return UGRT_OK;
 }
 
+// Ambient occlusion: per primary hit, whatever its material, the origin d_reflect_ray gives the
+// reflected ray and the flipped unit normal -- {o', n} of D_HIT_FRAME from the camera.  The hemisphere directions are
+// formed from these six floats in the walk (k_trace_dda_any<., AnyHemi>) and never written.  The primary arrays are read
+// as k_reflect_rays reads them: the ids are triangle ids (no shading call has run yet).
+__global__ __launch_bounds__(PX_THREADS) void k_ao_rays(const float *__restrict__ cam_pos,
+							 const float *__restrict__ t_list,
+							 const float *__restrict__ dir_list,
+							 const int *__restrict__ id_list, const float *__restrict__ verts,
+							 const int *__restrict__ tris, float eps, float *__restrict__ orays,
+							 int *__restrict__ oactive, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int p = p0 + i;
+	int id = id_list[p];
+	float t = t_list[p];
+	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+	int act = 0;
+	if (t > 0 && id >= 0) {
+		float tri[9], d[3], P[3], nn[3], dn;
+		d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			d[k] = dir_list[p * 3 + k];
+		D_HIT_FRAME(cam_pos, d, t, tri, P, nn, dn);
+#pragma unroll
+		for (int k = 0; k < 3; k++) {
+			out[k] = P[k] + eps * nn[k];
+			out[3 + k] = nn[k];
+		}
+		act = 1;
+	}
+#pragma unroll
+	for (int k = 0; k < 6; k++)
+		orays[p * 6 + k] = out[k];
+	oactive[p] = act;
+}
+
+extern "C" int ugrt_ao_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
+			    const int *d_intersect_id, const float *d_vertlist, const int *d_trilist, float eps,
+			    float *d_orays, int *d_oactive)
+{
+	if (!ctx || !d_cam_position || !d_t_value || !d_ray_dir || !d_intersect_id || !d_vertlist || !d_trilist || !d_orays ||
+	    !d_oactive)
+		return ugrt_fail(UGRT_EINVAL, "ao_rays: null argument");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
+	hipLaunchKernelGGL(k_ao_rays, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_cam_position, d_t_value, d_ray_dir, d_intersect_id, d_vertlist, d_trilist, eps, d_orays, d_oactive,
+			   ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 struct DepthIn {
 	const float *reflect;
 	const float *verts;

@@ -15,7 +15,9 @@
 //     broadcast, and a round is accepted with one ballot: no 64-bit minimum, no LDS, no list position.
 // The kernel reads the grid and the rays and writes its flags: it neither reads nor writes the split walks' history.
 // ugrt_trace_dda_any_lights is the same kernel over (light, ray group): the walk towards several
-// points from one set of origins, with one prepare launch and one ray list.
+// points from one set of origins, with one prepare launch and one ray list.  ugrt_trace_dda_any_hemi (DESIGN.md section
+// 6.5) is the same kernel over (direction, ray group): S directions of the hemisphere over each stored normal, formed in
+// registers, one bit of a mask word per direction.
 #include "ugrt_dda.h"
 
 #define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
@@ -33,7 +35,7 @@ int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *
 // light l's flags lie at l * level.
 struct AnyRays {
 	typedef float Arg; // t_max
-	static constexpr bool lights = false;
+	static constexpr bool lights = false, hemi = false;
 };
 struct AnyLights {
 	struct Arg {
@@ -41,11 +43,57 @@ struct AnyLights {
 		int count;
 		size_t level; // W*H
 	};
-	static constexpr bool lights = true;
+	static constexpr bool lights = true, hemi = false;
+};
+// AnyHemi: from the stored origins along num_dirs directions of the hemisphere over the stored normal
+// (ugrt_trace_dda_any_hemi), up to `radius`.  The index space is (direction, ray group),
+// direction-major as AnyLights is light-major: a wave never mixes directions, its local direction is three scalars of the
+// by-value block, and waves side by side walk neighbouring pixels along one local direction.  The slot's last three floats
+// are the unit normal; d_hemi_dir turns the local direction into the world's.  Direction s is bit s of the pixel's mask.
+struct AnyHemi {
+	struct Arg {
+		float dirs[3 * UGRT_MAX_AO_DIRS]; // by value: uniform over the launch, read from the kernarg segment
+		int count;
+		float radius;
+	};
+	static constexpr bool lights = false, hemi = true;
 };
 
+// D = (x*T + y*B) + z*n over the normal n: a = the axis of the smallest |n[k]| (strict <, 1 against 0, then 2 against the
+// winner: ties go to the lowest k), T = normalize(n x e_a) -- a swizzle with one exact negation --, B = n x T.
+__device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, float z, float *D)
+{
+	int a = 0;
+	float m = __builtin_fabsf(n[0]);
+	if (__builtin_fabsf(n[1]) < m) {
+		a = 1;
+		m = __builtin_fabsf(n[1]);
+	}
+	if (__builtin_fabsf(n[2]) < m)
+		a = 2;
+	float T[3], B[3];
+	if (a == 0) {
+		T[0] = 0.0f;
+		T[1] = n[2];
+		T[2] = -n[1];
+	} else if (a == 1) {
+		T[0] = -n[2];
+		T[1] = 0.0f;
+		T[2] = n[0];
+	} else {
+		T[0] = n[1];
+		T[1] = -n[0];
+		T[2] = 0.0f;
+	}
+	D_NORMALIZE(T);
+	D_CROSS(B, n, T);
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		D[k] = (x * T[k] + y * B[k]) + z * n[k];
+}
+
 // `occluded` of the band was cleared by the prepare kernel (AnyLights: layer 0; the layers behind by the host call): only
-// the flags of occluded rays are written
+// the flags of occluded rays are written (AnyHemi: `occluded` is the mask words, bit s is OR-ed in by direction s's lane)
 template <bool REC, class Aim>
 __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__restrict__ value_list,
 							const u32 *__restrict__ span, const u32 *__restrict__ offset,
@@ -57,21 +105,24 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 {
 	const int lane = threadIdx.x;
 	const u32 count = *count_p;
+	constexpr bool layered = Aim::lights || Aim::hemi; // the index space is (light or direction, ray group)
 	float t_max;
 	if constexpr (Aim::lights)
 		t_max = 1.0f;
+	else if constexpr (Aim::hemi)
+		t_max = aim.radius;
 	else
 		t_max = aim;
 	// AnyLights: the ray count is the device's, so is the number of groups per light (no ray: no group, no division)
 	u32 per_light = 0u, groups = 0u;
-	if constexpr (Aim::lights) {
+	if constexpr (layered) {
 		per_light = (count + RPW - 1u) / RPW;
 		groups = per_light * (u32)aim.count;
 	}
 	// groups of RPW rays, the first gridDim.x by workgroup id, the others drawn from the ticket
-	for (u32 grp = blockIdx.x; Aim::lights ? grp < groups : grp * RPW < count;) {
-		u32 light = 0u, lgrp = grp; // (uniform)
-		if constexpr (Aim::lights) {
+	for (u32 grp = blockIdx.x; layered ? grp < groups : grp * RPW < count;) {
+		u32 light = 0u, lgrp = grp; // (uniform; AnyHemi: the direction)
+		if constexpr (layered) {
 			light = grp / per_light;
 			lgrp = grp - light * per_light;
 		}
@@ -90,6 +141,10 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 					d[k] = aim.pos[3u * light + (u32)k] - o[k];
 				else
 					d[k] = rays[p * 6 + 3 + k];
+			}
+			if constexpr (Aim::hemi) {
+				const float nrm[3] = { d[0], d[1], d[2] };
+				d_hemi_dir(nrm, aim.dirs[3u * light], aim.dirs[3u * light + 1u], aim.dirs[3u * light + 2u], d);
 			}
 			float tenter;
 			if (d_dda_clip(g, o, d, tenter)) {
@@ -172,6 +227,8 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 		if (occ) {
 			if constexpr (Aim::lights)
 				(occluded + (size_t)light * aim.level)[p] = 1; // (the layer's base is uniform)
+			else if constexpr (Aim::hemi)
+				atomicOr((u32 *)occluded + p, 1u << light); // (each (p, s) has one lane: this merges a word's S writers)
 			else
 				occluded[p] = 1;
 		}
@@ -272,6 +329,53 @@ extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_
 			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
 			   (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
 			   ctx->d_small + UGRT_DSMALL_TICKET);
+	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				       const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				       const float *d_orays, const int *d_oactive, int num_dirs, const float *dirs, float radius,
+				       unsigned *d_mask)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !dirs ||
+	    !d_mask)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: null argument");
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
+	if (!(radius > 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: radius must be greater than 0");
+	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	if (!G.valid)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const DGrid g = ugrt_dgrid_of(G);
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	AnyHemi::Arg hemi = {};
+	for (int k = 0; k < 3 * num_dirs; k++)
+		hemi.dirs[k] = dirs[k];
+	hemi.count = num_dirs;
+	hemi.radius = radius;
+	// launch shape: ugrt_trace_dda_any's options
+	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
+	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
+	// ONE prepare launch and one ray list for all directions, taken as ugrt_trace_dda_any takes them (the turn of the ray
+	// counters, the ticket, the bitmap); it clears the band's mask words, which the walk then only ORs into
+	u32 *list, *dcount;
+	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
+	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, (int *)d_mask, d_span, true, nullptr, &list, &dcount);
+	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
+	if (rc)
+		return rc;
+	// persistent single-wave workgroups over (direction, group); "dda_blocks" caps them as it caps ugrt_trace_dda's
+	int blocks = launch_blocks_for(((u32)ctx->npix / RPW + 1u) * (u32)num_dirs);
+	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
+		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
+	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
+	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyHemi> : k_trace_dda_any<false, AnyHemi>), dim3(blocks), dim3(64), 0,
+			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
+			   (const u32 *)list, (const u32 *)dcount, hemi, (int *)d_mask, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET);
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;

@@ -376,26 +376,32 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 	}
 }
 
-// the reflection bounce's next ray: hit point P = o + t*d on the staged triangle tri
-// ({., e1, e2}: d_stage_triangle), n = normalize(e1 x e2) turned against d, out = {P + eps*n, d - 2(d.n)n}.
+// where a ray leaves a hit: hit point P = o + t*d on the staged triangle tri ({., e1, e2}: d_stage_triangle),
+// nn = normalize(e1 x e2) turned against d, dn = d.nn (<= 0).  The text d_reflect_ray and k_ao_rays share (a macro, like
+// D_CROSS: the kernels that had it written out keep their code to the instruction).
+#define D_HIT_FRAME(o, d, t, tri, P, nn, dn)              \
+	do {                                              \
+		const float *e1_ = &(tri)[3], *e2_ = &(tri)[6]; \
+		_Pragma("unroll") for (int k_ = 0; k_ < 3; k_++) \
+			P[k_] = o[k_] + t * d[k_];        \
+		D_CROSS(nn, e1_, e2_);                    \
+		D_NORMALIZE(nn);                          \
+		dn = D_DOT(d, nn);                        \
+		if (dn > 0) {                             \
+			nn[0] = -nn[0];                   \
+			nn[1] = -nn[1];                   \
+			nn[2] = -nn[2];                   \
+			dn = -dn;                         \
+		}                                         \
+	} while (0)
+
+// the reflection bounce's next ray: out = {P + eps*n, d - 2(d.n)n} of D_HIT_FRAME.
 // o is the camera for the first bounce (k_reflect_rays) and the ray's own origin after that (k_reflect_rays_next).
 __device__ __forceinline__ void d_reflect_ray(const float *o, const float *d, float t, const float *tri, float eps,
 					      float *out)
 {
-	const float *e1 = &tri[3], *e2 = &tri[6];
-	float nn[3], P[3];
-#pragma unroll
-	for (int k = 0; k < 3; k++)
-		P[k] = o[k] + t * d[k];
-	D_CROSS(nn, e1, e2);
-	D_NORMALIZE(nn);
-	float dn = D_DOT(d, nn);
-	if (dn > 0) {
-		nn[0] = -nn[0];
-		nn[1] = -nn[1];
-		nn[2] = -nn[2];
-		dn = -dn;
-	}
+	float nn[3], P[3], dn;
+	D_HIT_FRAME(o, d, t, tri, P, nn, dn);
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
 		out[k] = P[k] + eps * nn[k];

@@ -388,6 +388,40 @@ extern "C" int ugrt_shade_add_shadows(ugrt_ctx *ctx, unsigned char *d_img, const
 	return UGRT_OK;
 }
 
+// Ambient occlusion (not in the reference): a last integer pass over the image, like
+// k_add_shadows.  bit s of mask = hemisphere ray s is occluded; each byte is scaled by the share of open rays.
+__global__ __launch_bounds__(PX_THREADS) void k_shade_ao(unsigned char *__restrict__ d_img, const u32 *__restrict__ mask,
+							  u32 num_dirs, u32 low_bits, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	const u32 m = mask[pixelID] & low_bits;
+	if (m != 0u) {
+		const u32 open = num_dirs - (u32)__popc(m);
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			d_img[pixelID * 3 + k] = (unsigned char)(((u32)d_img[pixelID * 3 + k] * open) / num_dirs);
+	}
+}
+
+extern "C" int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_dirs)
+{
+	if (!ctx || !d_img || !d_mask)
+		return ugrt_fail(UGRT_EINVAL, "shade_ao: null argument");
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "shade_ao: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const u32 low_bits = num_dirs == 32 ? 0xFFFFFFFFu : (1u << num_dirs) - 1u;
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_ao, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_img, d_mask, (u32)num_dirs, low_bits, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // several lights (the reference's loop over h_numLights, main.cu:148-203, runs with one and
 // its shading kernels index light 0): k_shade<false> and k_add_shadows once per light and the mean of the bytes, in

@@ -317,6 +317,26 @@ class Context:
                                             _ptr(verts), _ptr(faces), int(depth), _ptr(rays), _ptr(active), _ptr(hit_t),
                                             _ptr(hit_id), n, pos, _ptr(is_shadowed), _ptr(occluded)))
 
+    # -- ambient occlusion ------------------------------
+    def ao_rays(self, cam_pos, t, ray_dir, ids, verts, faces, eps, orays, oactive):
+        """The primary hits (triangle ids: before any shading call) -> {o', n} per pixel: the origin reflect_rays gives
+        the reflected ray and the flipped unit normal."""
+        check(lib.ugrt_ao_rays(self._h, _ptr(cam_pos), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(verts), _ptr(faces), eps,
+                               _ptr(orays), _ptr(oactive)))
+
+    def trace_dda_any_hemi(self, value, span, offset, verts, faces, orays, oactive, dirs, radius, mask):
+        """Bit s of mask[p] = trace_dda_any's flag (t_max radius) of the ray from orays' origin of p along dirs[s] in the
+        basis of orays' normal of p; dirs: host floats [S, 3] (scenes.ao_directions), z along the normal; mask: uint32
+        words (an int32 tensor serves)."""
+        flat = None if dirs is None else _f3(np.asarray(dirs, np.float32).reshape(-1))
+        n = 0 if dirs is None else len(flat) // 3
+        check(lib.ugrt_trace_dda_any_hemi(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                          _ptr(orays), _ptr(oactive), n, flat, radius, _ptr(mask)))
+
+    def shade_ao(self, img, mask, num_dirs):
+        """Each byte b of a pixel becomes (b * open) // num_dirs, open = num_dirs - popcount(mask & low num_dirs bits)."""
+        check(lib.ugrt_shade_ao(self._h, _ptr(img), _ptr(mask), int(num_dirs)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

@@ -19,7 +19,9 @@ section 6).  With ``reflect_shadows=True`` the hits of every reflection level ar
 light behind the level's 3D-DDA (occlusion rays -> any-hit walk) and the shading darkens the
 occluded levels.  With ``FrameSetup.lights`` the per-light part of the sequence runs once
 per light and one shading pass averages the lights (one-stream frame, no reflections); with
-``reflect_lights=True`` as well, the reflections are rendered under all of them.
+``reflect_lights=True`` as well, the reflections are rendered under all of them.  With ``ao=S`` every
+one-stream frame ends with ambient occlusion: S hemisphere rays per primary hit through the uniform grid, and a last
+pass that scales the image by the share of open rays.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -29,7 +31,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -100,6 +102,24 @@ def check_lights(lights, reflect, two_streams, reflect_lights=False):
         except (TypeError, ValueError, KeyError) as e:
             raise ValueError("lights[%d] is not (dict with %s, three floats): %r" % (k, "/".join(_CAMERA_KEYS), e))
     return out
+
+
+def check_ao(ao, ao_radius, two_streams=False):
+    """ao: an integer 0..MAX_AO_DIRS (0: off, and ao_radius is not looked at); ao > 0 needs a number ao_radius > 0 and the
+    one-stream Renderer (two_streams: the two-stream and banded frames keep the uniform grid on a side context), or
+    ValueError (before anything is enqueued); DESIGN.md section 6.5.  Returns (ao, radius or None)."""
+    if isinstance(ao, (bool, np.bool_)) or not isinstance(ao, (int, np.integer)) or not 0 <= ao <= MAX_AO_DIRS:
+        raise ValueError("ao must be an integer in 0..%d, not %r" % (MAX_AO_DIRS, ao))
+    if ao == 0:
+        return 0, None
+    if isinstance(ao_radius, (bool, np.bool_)) or not isinstance(ao_radius, (int, float, np.integer, np.floating)):
+        raise ValueError("ao=%d needs ao_radius, a number greater than 0, not %r" % (ao, ao_radius))
+    if not float(np.float32(ao_radius)) > 0.0:
+        raise ValueError("ao_radius must be greater than 0, not %r" % (ao_radius,))
+    if two_streams:
+        raise ValueError("ao needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
+                         "side context")
+    return int(ao), float(np.float32(ao_radius))
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -218,6 +238,15 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
                                    shadow_lights, f.occluded_lights[j])
 
 
+def ao_pass(c, f, cam_pos, dirs, radius):
+    """Ambient occlusion's rays and walk: {origin, normal} of every primary hit, then the any-hit
+    walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  Runs behind the
+    uniform grid's build and before the shading call that rewrites the ids."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    c.trace_dda_any_hemi(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, dirs, radius, f.ao_mask)
+
+
 def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
     depth shading with the occluded levels darkened, at every depth), then add_shadows."""
@@ -302,8 +331,26 @@ class _Frame:
         # reflect_lights with reflect_shadows: the levels' occlusion flags per light, a contiguous [D, L, W*H] view of
         # _occluded_lights_store (_ensure_reflect_lights_buffers)
         self.occluded_lights = self._occluded_lights_store = None
+        # ao: the hemisphere rays' origins and normals, their active flags and the mask of occluded directions
+        # (_ensure_ao_buffers); the direction sets asked for so far, by their size
+        self.ao_rays = self.ao_active = self.ao_mask = None
+        self._ao_dirs = {}
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
+
+    def _ensure_ao_buffers(self, ao):
+        """ao_rays [6 W*H], ao_active [W*H] and ao_mask [W*H] (uint32 words in an int32 tensor), allocated on first use;
+        returns the ao directions of scenes.ao_directions."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.ao_mask is None:
+            self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+            self.ao_mask = t.zeros(N, dtype=t.int32, device=dev)
+        if ao not in self._ao_dirs:
+            from .scenes import ao_directions
+
+            self._ao_dirs[ao] = ao_directions(ao)
+        return self._ao_dirs[ao]
 
     def _ensure_light_buffers(self, num_lights):
         """shadowed_lights [L, W*H]: light l's is_shadowed, allocated once for the most lights asked for."""
@@ -484,7 +531,7 @@ class Renderer(_Frame, _Band):
             self._worker = None
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
-                reflect_lights=False):
+                reflect_lights=False, ao=0, ao_radius=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -493,15 +540,22 @@ class Renderer(_Frame, _Band):
         Lambertian shading pass over all of them, whatever frame_cnt says.
         reflect_lights (one-stream renderer; needs reflect=True and setup.lights): the reflections of depth `bounces` under
         all of setup.lights -- per light its shadow stage, per level one any-hit launch towards every light (with
-        reflect_shadows; occluded_lights holds the flags [D, L, W*H]), one shading pass."""
+        reflect_shadows; occluded_lights holds the flags [D, L, W*H]), one shading pass.
+        ao (one-stream renderer, every frame above; 0: off): ambient occlusion with ao = 1..32 hemisphere rays
+        (scenes.ao_directions) of length ao_radius per primary hit; ao_mask holds the occluded directions' bits and the
+        image is scaled by the share of open rays behind the frame's own shading."""
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
+        ao, ao_radius = check_ao(ao, ao_radius, self.aux is not None)
         if reflect_lights:
             lights = check_lights(setup.lights, reflect, self.aux is not None, True)
-            return self._display_reflect_lights(setup, lights, shadows, shade, bounces, reflect_shadows)
+            return self._display_reflect_lights(setup, lights, shadows, shade, bounces, reflect_shadows,
+                                                self._ao_stage(ao, ao_radius, shade))
         if getattr(setup, "lights", None) is not None:
-            return self._display_lights(setup, check_lights(setup.lights, reflect, self.aux is not None), shadows, shade)
+            lights = check_lights(setup.lights, reflect, self.aux is not None)
+            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade))
+        ao = self._ao_stage(ao, ao_radius, shade)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
@@ -523,9 +577,20 @@ class Renderer(_Frame, _Band):
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
+        elif ao:
+            build_grid(ctx, self, GRID_UNIFORM, self.shards)
+        if ao:
+            ao_pass(ctx, self, self.cam_pos, *ao)
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
+        if ao:
+            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
 
-    def _display_lights(self, setup, lights, shadows, shade):
+    def _ao_stage(self, ao, ao_radius, shade):
+        """(directions, radius) for ao_pass and shade_ao, with the buffers in place; None: the frame has no ambient
+        occlusion (ao == 0, or nothing is shaded)."""
+        return (self._ensure_ao_buffers(ao), ao_radius) if ao and shade else None
+
+    def _display_lights(self, setup, lights, shadows, shade, ao=None):
         """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
         shadow stage into its row of shadowed_lights, then ONE shading pass.  dd_camcoords is the last light's when
         the shading runs, as the reference's loop leaves it."""
@@ -543,10 +608,16 @@ class Renderer(_Frame, _Band):
                 light_grid = ctx.grid_ptrs(GRID_SPHERICAL)
                 sort_rays(ctx, self)
                 trace_shadows(ctx, self, self, light_grid, self.shadowed_lights[l])
-        if shade:
-            shade_lights(ctx, self, self.cam_pos, lights, shadows)
+        if not shade:
+            return
+        if ao:
+            build_grid(ctx, self, GRID_UNIFORM, self.shards)
+            ao_pass(ctx, self, self.cam_pos, *ao)
+        shade_lights(ctx, self, self.cam_pos, lights, shadows)
+        if ao:
+            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
 
-    def _display_reflect_lights(self, setup, lights, shadows, shade, bounces, reflect_shadows):
+    def _display_reflect_lights(self, setup, lights, shadows, shade, bounces, reflect_shadows, ao=None):
         """_display_lights' camera pass and per-light shadow stages, then the reflection levels once (the uniform grid and
         the reflected rays do not know the light) with every level's hits tested against the eyes of all light cameras in
         one launch, then ONE shading pass.  No host wait is added."""
@@ -574,7 +645,11 @@ class Renderer(_Frame, _Band):
         reflect_rays(ctx, self, self.cam_pos)
         build_grid(ctx, self, GRID_UNIFORM, self.shards)
         trace_reflections(ctx, self, bounces, shadow_lights=eyes if reflect_shadows else None)
+        if ao:
+            ao_pass(ctx, self, self.cam_pos, *ao)
         shade_reflect_lights(ctx, self, self.cam_pos, lights, bounces, shadows, reflect_shadows)
+        if ao:
+            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
 
     def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
@@ -761,9 +836,11 @@ class BandedRenderer(_Frame):
     def contexts(self):
         return [self.aux] + [b.ctx for b in self._per_band]
 
-    def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False):
+    def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
+                ao_radius=None):
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
+        check_ao(ao, ao_radius, True)  # raises with ao > 0: the uniform grid lives on the side context
         if getattr(setup, "lights", None) is not None:
             check_lights(setup.lights, reflect, True)  # raises: one light grid on the side context
         t, aux, main, side = self.torch, self.aux, self.main_stream, self.side_stream

@@ -341,3 +341,14 @@ def mirrors(outdir=None, scale=1.0):
     light_cam = dict(eye=(15.0, 2.0, 9.0), look=(15.0, 2.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
     return _finish(outdir, "mirrors%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_MIRRORS,
                    dict(cameras=cams, light_camera=light_cam, shading_light=(15.0, 2.0, 3.5)))
+
+
+def ao_directions(S):
+    """The S local directions of the ambient-occlusion hemisphere: a deterministic
+    cosine-weighted spiral, r = sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), direction
+    (r cos phi, r sin phi, sqrt(1 - r^2)) with z along the normal.  Computed in float64 and returned as float32 [S, 3]:
+    the library only ever sees these floats as data."""
+    s = np.arange(int(S), dtype=np.float64)
+    r = np.sqrt((s + 0.5) / float(S))
+    phi = s * (np.pi * (3.0 - np.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r)], 1).astype(np.float32)
