@@ -28,7 +28,8 @@ Oracle figures per case (all chunks traced): light-grid references R / distinct 
                       (4096,256) 9 448 717 / 3 777 / 3 785  (4096,2) 1 908 981 / 3 777 / 3 785
                       (2,4096) 814 654 / 3 / 579
 A ray's cell row is the same for nearly every ray of these frames (the reference's getEffective_y), so the number
-of distinct ray cells follows the grid's width alone.  Two consequences for the cases:
+of distinct ray cells follows the grid's width alone; rays in every row are tests/test_shadow_synthetic.py's.  Two
+consequences for the cases:
 * (256,256) gives hall 178 and crash 245 distinct ray cells, below the floor of 256: those two scenes run the 2^16
   cells as (512,128) instead (the same 15-bit direction code; 353 and 487 cells).  Cornell keeps (256,256).
 * (2,4096) is in the sweep BECAUSE nearly all rays share a handful of cells (long runs, many beams per cell), which
