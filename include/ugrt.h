@@ -165,6 +165,13 @@ const int *ugrt_scene_materiallist_index(const ugrt_scene *s);  /* h_materiallis
 const float *ugrt_scene_materiallist(const ugrt_scene *s);      /* h_materiallist [6M] Ka,Kd */
 /* obj_material.reflect of the mtllib (obj_parser.h:53, token "r"), [mtl_count] */
 const float *ugrt_scene_reflectlist(const ugrt_scene *s, int *mtl_count);
+/* How much of a material's colour comes from behind it, [mtl_count]: (float)(1 - obj_material.trans) clamped to [0, 1]
+ * (a NaN: 0).  The MTL token "d" is OBJ's dissolve -- 1 is opaque -- and defaults to 1, so a material without it has
+ * transmit 0.  A scene loaded from a cache reports 0 for every material: the cache format does not hold the list. */
+const float *ugrt_scene_transmitlist(const ugrt_scene *s, int *mtl_count);
+/* (float)obj_material.refract_index of the mtllib (token "Ni", default 1), [mtl_count].  A scene loaded from a cache
+ * reports 1 for every material: the cache format does not hold the list. */
+const float *ugrt_scene_iorlist(const ugrt_scene *s, int *mtl_count);
 /* Binary cache of a loaded scene (the strtok parser takes seconds on 1 M triangles).
  * Little-endian: "UGRTSCN1", counts, then the flat lists exactly as the accessors return them.
  * load_cache replaces the scene's contents; a truncated or foreign file gives UGRT_EIO. */
@@ -532,6 +539,56 @@ int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_list, const u
  * integers.  A zero mask leaves the pixel as it is.  Stage UGRT_ST_SHADE.  num_dirs outside 1..UGRT_MAX_AO_DIRS or a null
  * argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_dirs);
+
+/* ---- device: refraction ---------------------------
+ * Transmitted rays in the bounce chain: a level's ray goes THROUGH a hit whose material has transmit > 0 instead of
+ * being mirrored, and the any-hit walk of section 6.2 does not count such a material's triangles as occluders.  The
+ * levels, ugrt_trace_dda and every shading call are those of sections 6.1-6.5; the shading calls are given
+ * continue[m] = transmit[m] > 0 ? transmit[m] : reflect[m] as their d_reflect.  All arithmetic is fp32 without
+ * contraction, sqrt and / correctly rounded.
+ * The refracted ray of a hit (o, d, t, triangle) of material m: P = o + t*d, n = normalize(e1 x e2), front = d.n <= 0,
+ * n turned so that d.n <= 0 (the frame of ugrt_reflect_rays_next); u = d * (1 / sqrt(d.d)), c = -(u.n);
+ * ior = ior[m] > 0 ? ior[m] : 1 (a NaN or a non-positive index counts as 1); eta = front ? 1 / ior : ior;
+ * k = 1 - (eta*eta) * (1 - c*c).  k < 0 (total internal reflection): the ray of ugrt_reflect_rays_next,
+ * {P + eps*n, d - (2*(d.n))*n}.  Otherwise g = eta*c - sqrt(k) and the ray is {P - eps*n, eta*u + g*n}: it starts on
+ * the far side.  Which side is the front rests on the winding of the scene's closed solids (outwards); it is not
+ * tracked per ray. */
+/* ugrt_reflect_rays with glass: under ugrt_reflect_rays' conditions on the pixel (d_t_value[p] > 0, d_intersect_id[p] >= 0,
+ * material m in range), d_transmit[m] > 0: the refracted ray above from the camera and active 1; else d_reflect[m] > 0:
+ * ugrt_reflect_rays' ray and 1; else six zeros and 0.  A material with both transmits.  With d_transmit all zero the
+ * call writes ugrt_reflect_rays' bytes.  It tells the context what ugrt_reflect_rays tells it (level 1: the
+ * ugrt_trace_dda that follows uses the split-walk history).  Stage UGRT_ST_REFLECT_GEN.  A null argument: UGRT_EINVAL
+ * and nothing is enqueued. */
+int ugrt_refract_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
+		      const int *d_intersect_id, const int *d_mat_idx, const float *d_reflect, const float *d_transmit,
+		      const float *d_ior, int num_materials, const float *d_vertlist, const int *d_trilist, float eps,
+		      float *d_rays, int *d_active);
+/* ugrt_reflect_rays_next with glass, in the same way: for a pixel with d_active[p], d_hit_t[p] > 0, d_hit_id[p] >= 0
+ * and material m in range, d_transmit[m] > 0 gives the refracted ray from the ray's own origin, else d_reflect[m] > 0
+ * the reflected one, else six zeros and 0.  With d_transmit all zero the call writes ugrt_reflect_rays_next's bytes.
+ * It tells the context what ugrt_reflect_rays_next tells it (the ugrt_trace_dda that follows walks without the
+ * split-walk history).  Stage UGRT_ST_REFLECT_GEN.  A null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_refract_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+			   const int *d_hit_id, const int *d_mat_idx, const float *d_reflect, const float *d_transmit,
+			   const float *d_ior, int num_materials, const float *d_vertlist, const int *d_trilist, float eps,
+			   float *d_rays_next, int *d_active_next);
+/* ugrt_trace_dda_any that sees through glass: a triangle f of a visited cell's list occludes iff it passes
+ * ugrt_trace_dda_any's test (exact test, 0 < t < t_max) AND it is not see-through; f is see-through when
+ * m = d_mat_idx[f] is in 0..num_materials-1 and d_transmit[m] > 0.  The two loads happen only behind a geometrically
+ * accepted test.  Everything else -- visited cells, result layout, prepare launch, ticket, bitmap, options, stages,
+ * errors, leaving the split-walk history alone -- is ugrt_trace_dda_any's; with d_transmit all zero the call writes
+ * what ugrt_trace_dda_any writes.  A null d_mat_idx or d_transmit: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_trace_dda_any_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+			    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_rays,
+			    const int *d_active, float t_max, int *d_occluded, const int *d_mat_idx,
+			    const float *d_transmit, int num_materials);
+/* ugrt_trace_dda_any_lights that sees through glass, in the same way: layer l is what ugrt_trace_dda_any_thru(...,
+ * t_max = 1) writes for the rays towards light_pos[l].  With d_transmit all zero the call writes what
+ * ugrt_trace_dda_any_lights writes.  (The hemisphere walk of section 6.5 has no such form: glass does enclose.) */
+int ugrt_trace_dda_any_lights_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				   const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				   const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
+				   int *d_occluded, const int *d_mat_idx, const float *d_transmit, int num_materials);
 
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */

@@ -112,6 +112,8 @@ PROTOTYPES = {
     "ugrt_scene_materiallist_index": (_P, [_P]),
     "ugrt_scene_materiallist": (_P, [_P]),
     "ugrt_scene_reflectlist": (_P, [_P, C.POINTER(C.c_int)]),
+    "ugrt_scene_transmitlist": (_P, [_P, C.POINTER(C.c_int)]),
+    "ugrt_scene_iorlist": (_P, [_P, C.POINTER(C.c_int)]),
     "ugrt_scene_save_cache": (C.c_int, [_P, C.c_char_p]),
     "ugrt_scene_load_cache": (C.c_int, [_P, C.c_char_p]),
     "ugrt_scene_bounds": (C.c_int, [_P, _F3, _F3]),
@@ -167,6 +169,10 @@ PROTOTYPES = {
     "ugrt_ao_rays": (C.c_int, [_P] * 7 + [C.c_float, _P, _P]),
     "ugrt_trace_dda_any_hemi": (C.c_int, [_P] * 8 + [C.c_int, _F3, C.c_float, _P]),
     "ugrt_shade_ao": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ugrt_refract_rays": (C.c_int, [_P] * 9 + [C.c_int, _P, _P, C.c_float, _P, _P]),
+    "ugrt_refract_rays_next": (C.c_int, [_P] * 9 + [C.c_int, _P, _P, C.c_float, _P, _P]),
+    "ugrt_trace_dda_any_thru": (C.c_int, [_P] * 8 + [C.c_float, _P, _P, _P, C.c_int]),
+    "ugrt_trace_dda_any_lights_thru": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

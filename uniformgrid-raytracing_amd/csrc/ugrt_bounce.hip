@@ -68,6 +68,123 @@ extern "C" int ugrt_reflect_rays_next(ugrt_ctx *ctx, const float *d_rays, const 
 	return UGRT_OK;
 }
 
+// Refraction: k_reflect_rays and k_reflect_rays_next with the choice of d_continue_ray -- a hit
+// on a material that transmits sends the refracted ray on, one that only reflects the mirrored ray.  The reflect kernels
+// keep their code; with transmit all zero these write the same bytes.
+__global__ __launch_bounds__(PX_THREADS) void k_refract_rays(const float *__restrict__ cam_pos,
+							      const float *__restrict__ t_list,
+							      const float *__restrict__ dir_list,
+							      const int *__restrict__ id_list, const int *__restrict__ mat_idx,
+							      const float *__restrict__ reflect,
+							      const float *__restrict__ transmit, const float *__restrict__ ior,
+							      int mat_count, const float *__restrict__ verts,
+							      const int *__restrict__ tris, float eps, float *__restrict__ rays,
+							      int *__restrict__ active, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int p = p0 + i;
+	int id = id_list[p];
+	float t = t_list[p];
+	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+	int act = 0;
+	if (t > 0 && id >= 0) {
+		int m = mat_idx[id];
+		if (m >= 0 && m < mat_count && (transmit[m] > 0 || reflect[m] > 0)) {
+			float tri[9], d[3];
+			d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				d[k] = dir_list[p * 3 + k];
+			act = d_continue_ray(cam_pos, d, t, tri, eps, transmit[m], reflect[m], ior[m], out) ? 1 : 0;
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 6; k++)
+		rays[p * 6 + k] = out[k];
+	active[p] = act;
+}
+
+extern "C" int ugrt_refract_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
+				 const int *d_intersect_id, const int *d_mat_idx, const float *d_reflect,
+				 const float *d_transmit, const float *d_ior, int num_materials, const float *d_vertlist,
+				 const int *d_trilist, float eps, float *d_rays, int *d_active)
+{
+	if (!ctx || !d_cam_position || !d_t_value || !d_ray_dir || !d_intersect_id || !d_mat_idx || !d_reflect || !d_transmit ||
+	    !d_ior || !d_vertlist || !d_trilist || !d_rays || !d_active)
+		return ugrt_fail(UGRT_EINVAL, "refract_rays: null argument");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
+	hipLaunchKernelGGL(k_refract_rays, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_cam_position, d_t_value, d_ray_dir, d_intersect_id, d_mat_idx, d_reflect, d_transmit, d_ior,
+			   num_materials, d_vertlist, d_trilist, eps, d_rays, d_active, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
+	UGRT_HIP(hipGetLastError());
+	ctx->dda_deeper_level = false; // level 1, as ugrt_reflect_rays says it
+	return UGRT_OK;
+}
+
+__global__ __launch_bounds__(PX_THREADS) void k_refract_rays_next(const float *__restrict__ rays,
+								   const int *__restrict__ active,
+								   const float *__restrict__ hit_t,
+								   const int *__restrict__ hit_id,
+								   const int *__restrict__ mat_idx,
+								   const float *__restrict__ reflect,
+								   const float *__restrict__ transmit,
+								   const float *__restrict__ ior, int mat_count,
+								   const float *__restrict__ verts, const int *__restrict__ tris,
+								   float eps, float *__restrict__ rays_next,
+								   int *__restrict__ active_next, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int p = p0 + i;
+	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+	int act = 0;
+	if (active[p]) {
+		int id = hit_id[p];
+		float t = hit_t[p];
+		if (t > 0 && id >= 0) {
+			int m = mat_idx[id];
+			if (m >= 0 && m < mat_count && (transmit[m] > 0 || reflect[m] > 0)) {
+				float tri[9], o[3], d[3];
+				d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
+#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					o[k] = rays[p * 6 + k];
+					d[k] = rays[p * 6 + 3 + k];
+				}
+				act = d_continue_ray(o, d, t, tri, eps, transmit[m], reflect[m], ior[m], out) ? 1 : 0;
+			}
+		}
+	}
+#pragma unroll
+	for (int k = 0; k < 6; k++)
+		rays_next[p * 6 + k] = out[k];
+	active_next[p] = act;
+}
+
+extern "C" int ugrt_refract_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
+				      const int *d_hit_id, const int *d_mat_idx, const float *d_reflect,
+				      const float *d_transmit, const float *d_ior, int num_materials, const float *d_vertlist,
+				      const int *d_trilist, float eps, float *d_rays_next, int *d_active_next)
+{
+	if (!ctx || !d_rays || !d_active || !d_hit_t || !d_hit_id || !d_mat_idx || !d_reflect || !d_transmit || !d_ior ||
+	    !d_vertlist || !d_trilist || !d_rays_next || !d_active_next)
+		return ugrt_fail(UGRT_EINVAL, "refract_rays_next: null argument");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
+	hipLaunchKernelGGL(k_refract_rays_next, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
+			   ctx->stream, d_rays, d_active, d_hit_t, d_hit_id, d_mat_idx, d_reflect, d_transmit, d_ior,
+			   num_materials, d_vertlist, d_trilist, eps, d_rays_next, d_active_next, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
+	UGRT_HIP(hipGetLastError());
+	ctx->dda_deeper_level = true; // a level >= 2, as ugrt_reflect_rays_next says it
+	return UGRT_OK;
+}
+
 // Occlusion rays from one level's hits towards the light: the origin is the one the next
 // reflected ray would start from (d_reflect_ray), the direction L - o' is not normalised, so the light lies at t = 1.
 // The hit's material plays no part: a diffuse hit seen in a mirror is shadowed too.

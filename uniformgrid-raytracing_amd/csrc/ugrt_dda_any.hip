@@ -17,8 +17,10 @@
 // ugrt_trace_dda_any_lights is the same kernel over (light, ray group): the walk towards several
 // points from one set of origins, with one prepare launch and one ray list.  ugrt_trace_dda_any_hemi (DESIGN.md section
 // 6.5) is the same kernel over (direction, ray group): S directions of the hemisphere over each stored normal, formed in
-// registers, one bit of a mask word per direction.
+// registers, one bit of a mask word per direction.  ugrt_trace_dda_any_thru and ugrt_trace_dda_any_lights_thru (DESIGN.md
+// section 6.6) are the same kernel with THRU: an accepted test counts only if the triangle's material does not transmit.
 #include "ugrt_dda.h"
+#include <type_traits>
 
 #define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
 
@@ -59,6 +61,22 @@ struct AnyHemi {
 	static constexpr bool lights = false, hemi = true;
 };
 
+// THRU: which triangles a ray passes: f is see-through when m = mat_idx[f] is in range and
+// transmit[m] > 0.  The plain kernels take the empty block: their arguments and their code stay what they were.
+struct ThruArg {
+	const int *mat_idx;
+	const float *transmit;
+	int mat_count;
+};
+struct NoThru {};
+__device__ __forceinline__ bool d_see_through(const ThruArg &a, const u32 *__restrict__ value_list, u32 at)
+{
+	// (the list entry is read again: kept in a register over the exact test it would cost the walk a wave per SIMD)
+	asm volatile("" : "+v"(at));
+	const int m = a.mat_idx[value_list[at]];
+	return m >= 0 && m < a.mat_count && a.transmit[m] > 0;
+}
+
 // D = (x*T + y*B) + z*n over the normal n: a = the axis of the smallest |n[k]| (strict <, 1 against 0, then 2 against the
 // winner: ties go to the lowest k), T = normalize(n x e_a) -- a swizzle with one exact negation --, B = n x T.
 __device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, float z, float *D)
@@ -94,14 +112,15 @@ __device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, flo
 
 // `occluded` of the band was cleared by the prepare kernel (AnyLights: layer 0; the layers behind by the host call): only
 // the flags of occluded rays are written (AnyHemi: `occluded` is the mask words, bit s is OR-ed in by direction s's lane)
-template <bool REC, class Aim>
+template <bool REC, class Aim, bool THRU = false>
 __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__restrict__ value_list,
 							const u32 *__restrict__ span, const u32 *__restrict__ offset,
 							const u32 *__restrict__ bitmap, const float *__restrict__ verts,
 							const int *__restrict__ tris, const float4 *__restrict__ rec,
 							const float *__restrict__ rays, const u32 *__restrict__ list,
 							const u32 *__restrict__ count_p, const typename Aim::Arg aim, int *__restrict__ occluded,
-							u32 RPW, u32 COOP, u32 *__restrict__ ticket)
+							u32 RPW, u32 COOP, u32 *__restrict__ ticket,
+							const std::conditional_t<THRU, ThruArg, NoThru> thru)
 {
 	const int lane = threadIdx.x;
 	const u32 count = *count_p;
@@ -193,6 +212,10 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 						float t9[9], t;
 						d_load_triangle<REC>(rec, verts, tris, value_list[off + r], o[0], o[1], o[2], t9);
 						if (d_mt_core(&t9[0], &t9[3], &t9[6], d, &t) && t > 0.0f && t < t_max) {
+							if constexpr (THRU) { // (the two loads: behind an accepted test only)
+								if (d_see_through(thru, value_list, off + r))
+									continue;
+							}
 							occ = true;
 							break;
 						}
@@ -214,6 +237,10 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 							float t9[9], t;
 							d_load_triangle<REC>(rec, verts, tris, value_list[offl + r], ox, oy, oz, t9);
 							acc = d_mt_core(&t9[0], &t9[3], &t9[6], dl, &t) && t > 0.0f && t < t_max;
+							if constexpr (THRU) {
+								if (acc && d_see_through(thru, value_list, offl + r))
+									acc = false;
+							}
 						}
 						hit = __ballot(acc) != 0ull;
 					}
@@ -238,14 +265,16 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 	}
 }
 
-extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
-				  const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
-				  const float *d_rays, const int *d_active, float t_max, int *d_occluded)
+// both exports: thru null = ugrt_trace_dda_any
+static int trace_dda_any(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
+			 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_rays,
+			 const int *d_active, float t_max, int *d_occluded, const ThruArg *thru)
 {
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_occluded)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any: null argument");
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_occluded ||
+	    (thru && (!thru->mat_idx || !thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
 	if (!(t_max > 0.0f))
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any: t_max must be greater than 0");
+		return ugrt_fail(UGRT_EINVAL, "%s: t_max must be greater than 0", who);
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
@@ -268,24 +297,49 @@ extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, c
 	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays> : k_trace_dda_any<false, AnyRays>), dim3(blocks), dim3(64), 0,
-			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays,
-			   (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+	if (thru)
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays, true> : k_trace_dda_any<false, AnyRays, true>), dim3(blocks),
+				   dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist,
+				   d_trilist, rec, d_rays, (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
+	else
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays> : k_trace_dda_any<false, AnyRays>), dim3(blocks), dim3(64), 0,
+				   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
+				   d_rays, (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
 }
 
-extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
-					 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
-					 const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
-					 int *d_occluded)
+extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				  const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				  const float *d_rays, const int *d_active, float t_max, int *d_occluded)
+{
+	return trace_dda_any(ctx, "trace_dda_any", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active, t_max,
+			     d_occluded, nullptr);
+}
+
+extern "C" int ugrt_trace_dda_any_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				       const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				       const float *d_rays, const int *d_active, float t_max, int *d_occluded,
+				       const int *d_mat_idx, const float *d_transmit, int num_materials)
+{
+	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
+	return trace_dda_any(ctx, "trace_dda_any_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active,
+			     t_max, d_occluded, &thru);
+}
+
+// both exports: thru null = ugrt_trace_dda_any_lights
+static int trace_dda_any_lights(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
+				const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
+				const int *d_oactive, int num_lights, const float *light_pos, int *d_occluded, const ThruArg *thru)
 {
 	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !light_pos ||
-	    !d_occluded)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_lights: null argument");
+	    !d_occluded || (thru && (!thru->mat_idx || !thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
 	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_lights: num_lights %d is not in 1..%d", num_lights, UGRT_MAX_LIGHTS);
+		return ugrt_fail(UGRT_EINVAL, "%s: num_lights %d is not in 1..%d", who, num_lights, UGRT_MAX_LIGHTS);
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
@@ -325,13 +379,38 @@ extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_
 	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights> : k_trace_dda_any<false, AnyLights>), dim3(blocks), dim3(64), 0,
-			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
-			   (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
-			   ctx->d_small + UGRT_DSMALL_TICKET);
+	if (thru)
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights, true> : k_trace_dda_any<false, AnyLights, true>),
+				   dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p,
+				   d_vertlist, d_trilist, rec, d_orays, (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
+	else
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights> : k_trace_dda_any<false, AnyLights>), dim3(blocks), dim3(64),
+				   0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
+				   d_orays, (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
+}
+
+extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					 const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
+					 int *d_occluded)
+{
+	return trace_dda_any_lights(ctx, "trace_dda_any_lights", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
+				    d_oactive, num_lights, light_pos, d_occluded, nullptr);
+}
+
+extern "C" int ugrt_trace_dda_any_lights_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					      const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
+					      int *d_occluded, const int *d_mat_idx, const float *d_transmit, int num_materials)
+{
+	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
+	return trace_dda_any_lights(ctx, "trace_dda_any_lights_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				    d_orays, d_oactive, num_lights, light_pos, d_occluded, &thru);
 }
 
 extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -375,7 +454,8 @@ extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_li
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
 	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyHemi> : k_trace_dda_any<false, AnyHemi>), dim3(blocks), dim3(64), 0,
 			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
-			   (const u32 *)list, (const u32 *)dcount, hemi, (int *)d_mask, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET);
+			   (const u32 *)list, (const u32 *)dcount, hemi, (int *)d_mask, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET,
+			   NoThru());
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;

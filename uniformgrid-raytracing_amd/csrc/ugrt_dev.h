@@ -378,8 +378,9 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 
 // where a ray leaves a hit: hit point P = o + t*d on the staged triangle tri ({., e1, e2}: d_stage_triangle),
 // nn = normalize(e1 x e2) turned against d, dn = d.nn (<= 0).  The text d_reflect_ray and k_ao_rays share (a macro, like
-// D_CROSS: the kernels that had it written out keep their code to the instruction).
-#define D_HIT_FRAME(o, d, t, tri, P, nn, dn)              \
+// D_CROSS: the kernels that had it written out keep their code to the instruction).  D_HIT_FRAME_SIDED also says which
+// side was hit: front = the normal was not turned, d.normalize(e1 x e2) <= 0 (d_refract_ray).
+#define D_HIT_FRAME_SIDED(o, d, t, tri, P, nn, dn, front) \
 	do {                                              \
 		const float *e1_ = &(tri)[3], *e2_ = &(tri)[6]; \
 		_Pragma("unroll") for (int k_ = 0; k_ < 3; k_++) \
@@ -387,12 +388,19 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 		D_CROSS(nn, e1_, e2_);                    \
 		D_NORMALIZE(nn);                          \
 		dn = D_DOT(d, nn);                        \
+		front = !(dn > 0);                        \
 		if (dn > 0) {                             \
 			nn[0] = -nn[0];                   \
 			nn[1] = -nn[1];                   \
 			nn[2] = -nn[2];                   \
 			dn = -dn;                         \
 		}                                         \
+	} while (0)
+#define D_HIT_FRAME(o, d, t, tri, P, nn, dn)                        \
+	do {                                                        \
+		bool front_;                                        \
+		D_HIT_FRAME_SIDED(o, d, t, tri, P, nn, dn, front_); \
+		(void)front_;                                       \
 	} while (0)
 
 // the reflection bounce's next ray: out = {P + eps*n, d - 2(d.n)n} of D_HIT_FRAME.
@@ -407,6 +415,51 @@ __device__ __forceinline__ void d_reflect_ray(const float *o, const float *d, fl
 		out[k] = P[k] + eps * nn[k];
 		out[3 + k] = d[k] - (2.0f * dn) * nn[k];
 	}
+}
+
+// the refraction's next ray: through the hit into the far side by Snell's law, eta = 1/ior into
+// the solid (front) and ior out of it; past the critical angle (k < 0) d_reflect_ray's ray, operation for operation.
+__device__ __forceinline__ void d_refract_ray(const float *o, const float *d, float t, const float *tri, float eps,
+					      float transmit_m, float ior_m, float *out)
+{
+	(void)transmit_m; // (the weight of the next level: the shading's business)
+	float nn[3], P[3], dn;
+	bool front;
+	D_HIT_FRAME_SIDED(o, d, t, tri, P, nn, dn, front);
+	float u[3] = { d[0], d[1], d[2] };
+	D_NORMALIZE(u);
+	const float c = -D_DOT(u, nn);
+	const float ior = ior_m > 0 ? ior_m : 1.0f;
+	const float eta = front ? 1.0f / ior : ior;
+	const float k = 1.0f - (eta * eta) * (1.0f - c * c);
+	if (k < 0) {
+#pragma unroll
+		for (int q = 0; q < 3; q++) {
+			out[q] = P[q] + eps * nn[q];
+			out[3 + q] = d[q] - (2.0f * dn) * nn[q];
+		}
+		return;
+	}
+	const float g = eta * c - __builtin_sqrtf(k);
+#pragma unroll
+	for (int q = 0; q < 3; q++) {
+		out[q] = P[q] - eps * nn[q];
+		out[3 + q] = eta * u[q] + g * nn[q];
+	}
+}
+
+// a level's next ray where glass is known (k_refract_rays, k_refract_rays_next): a material that transmits is gone
+// through, one that only reflects mirrors; false: the level ends here and out is left as it is
+__device__ __forceinline__ bool d_continue_ray(const float *o, const float *d, float t, const float *tri, float eps,
+					       float transmit_m, float reflect_m, float ior_m, float *out)
+{
+	if (transmit_m > 0)
+		d_refract_ray(o, d, t, tri, eps, transmit_m, ior_m, out);
+	else if (reflect_m > 0)
+		d_reflect_ray(o, d, t, tri, eps, out);
+	else
+		return false;
+	return true;
 }
 
 __device__ __forceinline__ unsigned char d_to_u8(float c)

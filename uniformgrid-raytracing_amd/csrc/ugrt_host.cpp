@@ -217,6 +217,8 @@ struct ugrt_scene {
 	std::vector<int> matidx;        // h_materiallist_index
 	std::vector<float> materiallist; // h_materiallist (6 per material)
 	std::vector<float> reflect;     // obj_material.reflect
+	std::vector<float> transmit;    // 1 - obj_material.trans (the dissolve d: 1 = opaque), clamped to [0, 1]
+	std::vector<float> ior;         // obj_material.refract_index
 	int num_materials = 0;
 	float bbmin[3] = { 9999.9f, 9999.9f, 9999.9f };
 	float bbmax[3] = { -9999.9f, -9999.9f, -9999.9f };
@@ -314,6 +316,13 @@ extern "C" int ugrt_scene_load_model(ugrt_scene *s, const char *path)
 	s->reflect.resize(o.mtl.size());
 	for (size_t i = 0; i < o.mtl.size(); i++)
 		s->reflect[i] = (float)o.mtl[i].reflect;
+	s->transmit.resize(o.mtl.size());
+	s->ior.resize(o.mtl.size());
+	for (size_t i = 0; i < o.mtl.size(); i++) {
+		const float tr = (float)(1 - o.mtl[i].trans);
+		s->transmit[i] = tr > 0.0f ? (tr < 1.0f ? tr : 1.0f) : 0.0f; // (a NaN counts as opaque)
+		s->ior[i] = (float)o.mtl[i].refract_index;
+	}
 	return UGRT_OK;
 }
 
@@ -412,6 +421,9 @@ extern "C" int ugrt_scene_load_cache(ugrt_scene *s, const char *path)
 	if (!ok)
 		return ugrt_fail(UGRT_EIO, "scene_load_cache: %s is not a valid ugrt scene cache", path);
 	t.num_materials = nm;
+	// the cache format knows no glass: a cached scene is opaque
+	t.transmit.assign(t.reflect.size(), 0.0f);
+	t.ior.assign(t.reflect.size(), 1.0f);
 	*s = t;
 	return UGRT_OK;
 }
@@ -439,6 +451,22 @@ extern "C" const float *ugrt_scene_reflectlist(const ugrt_scene *s, int *n)
 	if (n)
 		*n = (int)s->reflect.size();
 	return s->reflect.data();
+}
+extern "C" const float *ugrt_scene_transmitlist(const ugrt_scene *s, int *n)
+{
+	if (!s)
+		return nullptr;
+	if (n)
+		*n = (int)s->transmit.size();
+	return s->transmit.data();
+}
+extern "C" const float *ugrt_scene_iorlist(const ugrt_scene *s, int *n)
+{
+	if (!s)
+		return nullptr;
+	if (n)
+		*n = (int)s->ior.size();
+	return s->ior.data();
 }
 extern "C" int ugrt_scene_bounds(const ugrt_scene *s, float bbmin[3], float bbmax[3])
 {

@@ -337,6 +337,37 @@ class Context:
         """Each byte b of a pixel becomes (b * open) // num_dirs, open = num_dirs - popcount(mask & low num_dirs bits)."""
         check(lib.ugrt_shade_ao(self._h, _ptr(img), _ptr(mask), int(num_dirs)))
 
+    # -- refraction (DESIGN.md section 6.6) -------------------------------------
+    def refract_rays(self, cam_pos, t, ray_dir, ids, mat_idx, reflect, transmit, ior, num_materials, verts, faces, eps,
+                     rays, active):
+        """reflect_rays where a material with transmit > 0 sends the refracted ray on instead (index ior)."""
+        check(lib.ugrt_refract_rays(self._h, _ptr(cam_pos), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(mat_idx),
+                                    _ptr(reflect), _ptr(transmit), _ptr(ior), num_materials, _ptr(verts), _ptr(faces),
+                                    eps, _ptr(rays), _ptr(active)))
+
+    def refract_rays_next(self, rays, active, hit_t, hit_id, mat_idx, reflect, transmit, ior, num_materials, verts,
+                          faces, eps, rays_next, active_next):
+        """reflect_rays_next where a material with transmit > 0 sends the refracted ray on instead."""
+        check(lib.ugrt_refract_rays_next(self._h, _ptr(rays), _ptr(active), _ptr(hit_t), _ptr(hit_id), _ptr(mat_idx),
+                                         _ptr(reflect), _ptr(transmit), _ptr(ior), num_materials, _ptr(verts),
+                                         _ptr(faces), eps, _ptr(rays_next), _ptr(active_next)))
+
+    def trace_dda_any_thru(self, value, span, offset, verts, faces, rays, active, t_max, occluded, mat_idx, transmit,
+                           num_materials):
+        """trace_dda_any in which a triangle whose material has transmit > 0 does not occlude."""
+        check(lib.ugrt_trace_dda_any_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                          _ptr(rays), _ptr(active), t_max, _ptr(occluded), _ptr(mat_idx),
+                                          _ptr(transmit), num_materials))
+
+    def trace_dda_any_lights_thru(self, value, span, offset, verts, faces, orays, oactive, light_pos, occluded, mat_idx,
+                                  transmit, num_materials):
+        """trace_dda_any_lights in which a triangle whose material has transmit > 0 does not occlude."""
+        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
+        n = 0 if light_pos is None else len(light_pos)
+        check(lib.ugrt_trace_dda_any_lights_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts),
+                                                 _ptr(faces), _ptr(orays), _ptr(oactive), n, pos, _ptr(occluded),
+                                                 _ptr(mat_idx), _ptr(transmit), num_materials))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

@@ -75,6 +75,20 @@ class Model:
         p = lib.ugrt_scene_reflectlist(self._h, C.byref(n))
         return _view(p, n.value, np.float32)
 
+    @property
+    def h_transmitlist(self):
+        """1 - d of the MTL (d: the dissolve, 1 = opaque), clamped to [0, 1]; all 0 after load_cache."""
+        n = C.c_int()
+        p = lib.ugrt_scene_transmitlist(self._h, C.byref(n))
+        return _view(p, n.value, np.float32)
+
+    @property
+    def h_iorlist(self):
+        """Ni of the MTL (default 1); all 1 after load_cache."""
+        n = C.c_int()
+        p = lib.ugrt_scene_iorlist(self._h, C.byref(n))
+        return _view(p, n.value, np.float32)
+
     def bounds(self):
         mn, mx = (C.c_float * 3)(), (C.c_float * 3)()
         check(lib.ugrt_scene_bounds(self._h, mn, mx))

@@ -21,7 +21,9 @@ occluded levels.  With ``FrameSetup.lights`` the per-lig
 per light and one shading pass averages the lights (one-stream frame, no reflections); with
 ``reflect_lights=True`` as well, the reflections are rendered under all of them.  With ``ao=S`` every
 one-stream frame ends with ambient occlusion: S hemisphere rays per primary hit through the uniform grid, and a last
-pass that scales the image by the share of open rays.
+pass that scales the image by the share of open rays.  With ``refract=True`` a level's ray goes
+through a hit whose material transmits instead of being mirrored, and the reflected hits' shadow walk sees through such
+materials.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -51,6 +53,15 @@ def check_reflect_shadows(reflect_shadows, reflect):
     if reflect_shadows and not reflect:
         raise ValueError("reflect_shadows=True needs reflect=True: it shadows the reflected hits")
     return bool(reflect_shadows)
+
+
+def check_refract(refract, reflect):
+    """A bool, and only with reflect, or ValueError (before anything is enqueued)."""
+    if not isinstance(refract, (bool, np.bool_)):
+        raise ValueError("refract must be a bool, not %r" % (refract,))
+    if refract and not reflect:
+        raise ValueError("refract=True needs reflect=True: the transmitted rays are levels of the bounce chain")
+    return bool(refract)
 
 
 _CAMERA_KEYS = ("eye", "look", "up", "near", "far")
@@ -194,17 +205,32 @@ def shade_lights(c, f, cam_pos, lights, shadows):
                    [pos for _, pos in lights], f.shadowed_lights if shadows else None)
 
 
+def refracts(f):
+    """This frame's display(..., refract=) as the stages read it (a frame that never heard of it: False)."""
+    return getattr(f, "refract", False)
+
+
+def level_weights(f):
+    """What the shading calls are given as d_reflect: how much of a level's colour comes from the next level.  In a
+    refract frame that is a glass material's transmit (f.d_continue), otherwise its reflect."""
+    return f.d_continue if refracts(f) else f.d_reflect
+
+
 def shade_reflect_lights(c, f, cam_pos, lights, bounces, shadows, reflect_shadows):
     """The reflection levels blended under every light, its shadows and its occluded levels, averaged, in one pass
     (DESIGN.md section 6.4)."""
-    c.shade_reflect_lights(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.d_reflect,
-                           f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels, f.active_levels, f.hit_t_levels,
-                           f.hit_id_levels, [pos for _, pos in lights], f.shadowed_lights if shadows else None,
-                           f.occluded_lights if reflect_shadows else None)
+    c.shade_reflect_lights(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                           level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels, f.active_levels,
+                           f.hit_t_levels, f.hit_id_levels, [pos for _, pos in lights],
+                           f.shadowed_lights if shadows else None, f.occluded_lights if reflect_shadows else None)
 
 
 def reflect_rays(c, f, cam_pos):
-    """Level 1's secondary rays from the primary hits."""
+    """Level 1's secondary rays from the primary hits (a refract frame: through glass, mirrored elsewhere)."""
+    if refracts(f):
+        c.refract_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_matidx, f.d_reflect, f.d_transmit, f.d_ior,
+                       f.num_materials, f.d_verts, f.d_faces, f.reflect_eps, f.rays, f.active)
+        return
     c.reflect_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
                    f.d_faces, f.reflect_eps, f.rays, f.active)
 
@@ -216,26 +242,41 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
     occlusion rays towards that point and the any-hit walk up to it (t < 1) into f.occluded_levels.
     shadow_lights (reflect_lights with reflect_shadows: the eyes of the L light cameras): the occlusion rays ONCE per
     level (towards the first eye; only their origins are used) and one any-hit launch towards all L eyes into level j's
-    [L, N] layers of f.occluded_lights."""
+    [L, N] layers of f.occluded_lights.
+    A refract frame (f.refract) generates the levels with the refract calls and walks the occlusion rays with the any-hit
+    calls that see through glass."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     rays, active, hit_t, hit_id = f.rays, f.active, f.hit_t, f.hit_id
     for j in range(bounces):
         if j:
             nrays, nactive = f.rays_levels[j], f.active_levels[j]
-            c.reflect_rays_next(rays, active, hit_t, hit_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
-                                f.d_faces, f.reflect_eps, nrays, nactive)
+            if refracts(f):
+                c.refract_rays_next(rays, active, hit_t, hit_id, f.d_matidx, f.d_reflect, f.d_transmit, f.d_ior,
+                                    f.num_materials, f.d_verts, f.d_faces, f.reflect_eps, nrays, nactive)
+            else:
+                c.reflect_rays_next(rays, active, hit_t, hit_id, f.d_matidx, f.d_reflect, f.num_materials, f.d_verts,
+                                    f.d_faces, f.reflect_eps, nrays, nactive)
             rays, active, hit_t, hit_id = nrays, nactive, f.hit_t_levels[j], f.hit_id_levels[j]
         c.trace_dda(uvalue, uspan, uoffset, f.d_verts, f.d_faces, rays, active, hit_t, hit_id)
         if shadow_light is not None:
             c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_light, f.reflect_eps,
                              f.occlusion_rays, f.occlusion_active)
-            c.trace_dda_any(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active, 1.0,
-                            f.occluded_levels[j])
+            if refracts(f):
+                c.trace_dda_any_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active,
+                                     1.0, f.occluded_levels[j], f.d_matidx, f.d_transmit, f.num_materials)
+            else:
+                c.trace_dda_any(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active, 1.0,
+                                f.occluded_levels[j])
         if shadow_lights is not None:
             c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_lights[0], f.reflect_eps,
                              f.occlusion_rays, f.occlusion_active)
-            c.trace_dda_any_lights(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active,
-                                   shadow_lights, f.occluded_lights[j])
+            if refracts(f):
+                c.trace_dda_any_lights_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays,
+                                            f.occlusion_active, shadow_lights, f.occluded_lights[j], f.d_matidx,
+                                            f.d_transmit, f.num_materials)
+            else:
+                c.trace_dda_any_lights(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays,
+                                       f.occlusion_active, shadow_lights, f.occluded_lights[j])
 
 
 def ao_pass(c, f, cam_pos, dirs, radius):
@@ -252,14 +293,14 @@ def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_sha
     depth shading with the occluded levels darkened, at every depth), then add_shadows."""
     if reflect and reflect_shadows:
         c.shade_reflect_depth_occluded(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
-                                       f.d_reflect, f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
+                                       level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
                                        f.active_levels, f.hit_t_levels, f.hit_id_levels, f.occluded_levels)
     elif reflect and bounces == 1:
-        c.shade_reflect(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.d_reflect,
-                        f.num_materials, f.d_verts, f.d_faces, f.rays, f.active, f.hit_t, f.hit_id)
+        c.shade_reflect(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+                        level_weights(f), f.num_materials, f.d_verts, f.d_faces, f.rays, f.active, f.hit_t, f.hit_id)
     elif reflect:
         c.shade_reflect_depth(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
-                              f.d_reflect, f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
+                              level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
                               f.active_levels, f.hit_t_levels, f.hit_id_levels)
     elif frame_cnt < 2:
         c.shade_simple(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
@@ -299,7 +340,7 @@ class _Frame:
     """The scene on the device and the arrays of a whole frame, which every context that renders rows of it writes
     (pixel ids are global)."""
 
-    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps):
+    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps, transmit=None, ior=None):
         t = ctx.torch
         self.F = int(len(faces))
         self.num_materials = int(len(mat_list) // 6 if np.ndim(mat_list) == 1 else len(mat_list))
@@ -309,6 +350,14 @@ class _Frame:
         self.d_matlist = ctx.upload(np.asarray(mat_list, np.float32).reshape(-1))
         refl = np.zeros(self.num_materials, np.float32) if reflect is None else np.asarray(reflect, np.float32)
         self.d_reflect = ctx.upload(refl)
+        # refraction: how much of a material's colour comes from behind it, its index, and the
+        # weight of the next level in a refract frame -- a glass material's transmit, otherwise its reflect
+        tr = np.zeros(self.num_materials, np.float32) if transmit is None else np.asarray(transmit, np.float32)
+        ni = np.ones(self.num_materials, np.float32) if ior is None else np.asarray(ior, np.float32)
+        self.d_transmit = ctx.upload(tr)
+        self.d_ior = ctx.upload(ni)
+        self.d_continue = ctx.upload(np.where(tr > 0, tr, refl).astype(np.float32))
+        self.refract = False  # this frame's display(..., refract=): read by the stages
         v = np.asarray(verts, np.float32).reshape(-1, 3)
         self.bbmin, self.bbmax = v.min(0), v.max(0)
         N = ctx.width * ctx.height
@@ -446,9 +495,11 @@ class _Band:
 
 
 class Renderer(_Frame, _Band):
-    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, reflect_eps=1e-3, overlap=False,
-                 shards=None, helper_thread=True, aux_stream=None, batch_builds=False):
-        """overlap=True: the light grid and the uniform grid (which do not depend on the camera pass) are built
+    def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, transmit=None, ior=None, reflect_eps=1e-3,
+                 overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False):
+        """transmit, ior: per material, how much of its colour comes from behind it (0: opaque, the default) and its index
+        of refraction (default 1), for display(..., refract=True).
+        overlap=True: the light grid and the uniform grid (which do not depend on the camera pass) are built
         by a second context on a second HIP stream while the main stream builds the perspective grid and
         traces the primary rays; streams are joined with events before the grids are consumed.  Same results.
         A grid build blocks its caller once (the read-back of total_refs), so the second context is driven by
@@ -466,7 +517,7 @@ class Renderer(_Frame, _Band):
         self._inline = overlap and not helper_thread
         if overlap:
             self._make_side_context(ctx, aux_stream, helper_thread)
-        _Frame.__init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps)
+        _Frame.__init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps, transmit, ior)
         _Band.__init__(self, ctx)
         self.orig = None
 
@@ -531,7 +582,7 @@ class Renderer(_Frame, _Band):
             self._worker = None
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
-                reflect_lights=False, ao=0, ao_radius=None):
+                reflect_lights=False, ao=0, ao_radius=None, refract=False):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -543,7 +594,13 @@ class Renderer(_Frame, _Band):
         reflect_shadows; occluded_lights holds the flags [D, L, W*H]), one shading pass.
         ao (one-stream renderer, every frame above; 0: off): ambient occlusion with ao = 1..32 hemisphere rays
         (scenes.ao_directions) of length ao_radius per primary hit; ao_mask holds the occluded directions' bits and the
-        image is scaled by the share of open rays behind the frame's own shading."""
+        image is scaled by the share of open rays behind the frame's own shading.
+        refract (needs reflect=True; every frame that takes reflect): a level's ray goes through a hit whose material
+        has transmit > 0 (Snell's law with the material's ior; total internal reflection mirrors) and is mirrored where
+        the material only reflects; the shading weighs the next level with transmit there; with reflect_shadows the
+        any-hit walk does not count glass as an occluder.  The primary shadow stage still does: a glass ball casts a
+        full shadow."""
+        self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
@@ -803,8 +860,8 @@ class BandedRenderer(_Frame):
     No call waits for the device (option async_build on every context); one host thread enqueues the stages band by
     band."""
 
-    def __init__(self, Context, W, H, verts, faces, matidx, mat_list, reflect=None, bands=2, device=0, light_grid=(128, 128),
-                 uniform_dims=(128, 128, 64), flags=0):
+    def __init__(self, Context, W, H, verts, faces, matidx, mat_list, reflect=None, transmit=None, ior=None, bands=2, device=0,
+                 light_grid=(128, 128), uniform_dims=(128, 128, 64), flags=0):
         from . import parallel
 
         assert bands >= 1
@@ -827,7 +884,7 @@ class BandedRenderer(_Frame):
                 self._per_band.append(_Band(cx))
             self.streams.append(st)
         # the scene and the frame's arrays once, on the main stream (band 0's)
-        _Frame.__init__(self, self._per_band[0].ctx, verts, faces, matidx, mat_list, reflect, 1e-3)
+        _Frame.__init__(self, self._per_band[0].ctx, verts, faces, matidx, mat_list, reflect, 1e-3, transmit, ior)
         for c in self.contexts():
             c.set_option("async_build", 1)
         # (as in the two-stream frame: the bounce's persistent waves leave room for the bands' short kernels)
@@ -837,7 +894,8 @@ class BandedRenderer(_Frame):
         return [self.aux] + [b.ctx for b in self._per_band]
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
-                ao_radius=None):
+                ao_radius=None, refract=False):
+        self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         check_ao(ao, ao_radius, True)  # raises with ao > 0: the uniform grid lives on the side context

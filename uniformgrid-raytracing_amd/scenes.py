@@ -16,6 +16,9 @@ parse the same text, so the float32 vertex arrays are identical.
   mirrors()  -- a corridor between two facing mirror walls over a reflective
                 floor, boxes and an icosphere between them: reflections of
                 many levels (Renderer.display(..., bounces=D))
+  glass()    -- a small room with a glass icosphere, a glass slab in front of
+                two boxes and a mirror panel: rays that go through solids
+                (Renderer.display(..., reflect=True, refract=True))
 """
 import os
 
@@ -172,14 +175,16 @@ CORNELL_QUADS = [
 ]
 
 
-def write_scene(outdir, name, verts, faces, matidx, materials):
-    """Write <name>.obj, <name>.mtl, <name>.mat; returns their paths."""
+def write_scene(outdir, name, verts, faces, matidx, materials, glass=None):
+    """Write <name>.obj, <name>.mtl, <name>.mat; returns their paths.  glass: {material index: (d, Ni)} -- the MTL
+    carries these materials' dissolve and index of refraction, every other material is written as "d 1" without Ni."""
     os.makedirs(outdir, exist_ok=True)
     obj, mtl, mat = (os.path.join(outdir, name + e) for e in (".obj", ".mtl", ".mat"))
     with open(mtl, "w") as fp:
-        for nm, ka, kd, refl in materials:
+        for k, (nm, ka, kd, refl) in enumerate(materials):
+            d_ni = "d 1\n" if not glass or k not in glass else "d %.6f\nNi %.6f\n" % tuple(glass[k])
             fp.write("newmtl %s\nKa %.6f %.6f %.6f\nKd %.6f %.6f %.6f\nKs 1.000000 1.000000 1.000000\nNs 0\n"
-                     "d 1\nr %.6f\nillum 2\n\n" % ((nm,) + tuple(ka) + tuple(kd) + (refl,)))
+                     "%sr %.6f\nillum 2\n\n" % ((nm,) + tuple(ka) + tuple(kd) + (d_ni, refl)))
     with open(mat, "w") as fp:
         for nm, ka, kd, refl in materials:
             fp.write("newmtl %s Ka %.6f %.6f %.6f Kd %.6f %.6f %.6f Ks 1 1 1 Ns 0 d 1 r %.6f map NA\n"
@@ -202,7 +207,8 @@ def _finish(outdir, name, mesh, materials, extra):
     info = dict(name=name, num_faces=len(faces), num_vertices=len(verts), materials=materials)
     info.update(extra)
     if outdir is not None:
-        info["obj"], info["mtl"], info["mat"] = write_scene(outdir, name, verts, faces, matidx, materials)
+        info["obj"], info["mtl"], info["mat"] = write_scene(outdir, name, verts, faces, matidx, materials,
+                                                            extra.get("glass"))
     info["verts"] = verts.astype(np.float32)  # generation values; the loaders parse the 6-decimal text
     info["faces"] = faces
     info["matidx"] = matidx
@@ -341,6 +347,67 @@ def mirrors(outdir=None, scale=1.0):
     light_cam = dict(eye=(15.0, 2.0, 9.0), look=(15.0, 2.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
     return _finish(outdir, "mirrors%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_MIRRORS,
                    dict(cameras=cams, light_camera=light_cam, shading_light=(15.0, 2.0, 3.5)))
+
+
+MATERIALS_GLASS = [
+    # name, Ka, Kd, reflect
+    ("g0_floor", (0.2, 0.2, 0.2), (0.62, 0.60, 0.55), 0.0),
+    ("g1_back_wall", (0.2, 0.2, 0.2), (0.30, 0.40, 0.80), 0.0),
+    ("g2_right_wall", (0.2, 0.2, 0.2), (0.80, 0.25, 0.20), 0.0),
+    ("g3_left_wall", (0.2, 0.2, 0.2), (0.25, 0.70, 0.30), 0.0),
+    ("g4_glass_ball", (0.2, 0.2, 0.2), (0.85, 0.92, 0.95), 0.0),
+    ("g5_glass_slab", (0.2, 0.2, 0.2), (0.75, 0.90, 0.85), 0.0),
+    ("g6_box", (0.2, 0.2, 0.2), (0.90, 0.75, 0.15), 0.0),
+    ("g7_box", (0.2, 0.2, 0.2), (0.70, 0.25, 0.75), 0.0),
+    ("g8_mirror", (0.2, 0.2, 0.2), (0.70, 0.80, 0.90), 0.8),
+]
+# material index -> (d, Ni) of the MTL: d is OBJ's dissolve (1 = opaque), so the ball transmits 0.85 and the slab 0.8
+GLASS_OF = {4: (0.15, 1.5), 5: (0.2, 1.33)}
+
+
+def _wind_outwards(verts, faces):
+    """The faces of a closed convex solid with every normal e1 x e2 pointing away from the solid's centroid."""
+    verts, faces = np.asarray(verts, np.float64), np.array(faces, np.int64)
+    c = verts[np.unique(faces)].mean(0)
+    a, b, d = verts[faces[:, 0]], verts[faces[:, 1]], verts[faces[:, 2]]
+    inward = np.einsum("ij,ij->i", np.cross(b - a, d - a), (a + b + d) / 3.0 - c) < 0
+    faces[inward] = faces[inward][:, [0, 2, 1]]
+    return verts, faces
+
+
+def glass(outdir=None, scale=1.0):
+    """Room [0,10]x[0,8]x[0,5] without a ceiling and without the wall x = 0 (behind the camera: see add_room): a matt
+    floor, a blue back wall, a red and a green side wall.  In it a glass icosphere (d 0.15, Ni 1.5), a glass slab with
+    all six faces (d 0.2, Ni 1.33) standing in front of two coloured boxes, and a mirror panel (r 0.8) before the back
+    wall.  The glass solids are closed and wound outwards (refraction takes the side a ray enters from off the
+    winding: DESIGN.md section 6.6).  ~10 000 triangles at scale 1."""
+    mesh = Mesh()
+    s = max(0.05, scale) ** 0.5
+    n = max(2, int(20 * s))
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 0, faces="z")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 1, faces="X")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 2, faces="y")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 3, faces="Y")
+    level = max(1, min(7, int(round(4 + np.log(max(scale, 1e-3)) / np.log(4)))))  # (grows with the scale above 1 too)
+    sv, sf = icosphere(level)
+    mesh.add(*_wind_outwards(sv * 1.1 + np.array([5.5, 2.4, 1.35]), sf), 4)
+    slab, nb = Mesh(), max(1, int(8 * s))
+    add_box(slab, (4.6, 4.3, 0.02), (5.1, 7.1, 2.8), nb, 5)
+    sv, sf, _ = slab.arrays()
+    mesh.add(*_wind_outwards(sv, sf), 5)
+    nb = max(1, int(6 * s))
+    add_box(mesh, (6.6, 4.5, 0.0), (7.4, 5.3, 1.5), nb, 6, faces="xXyYZ")
+    add_box(mesh, (6.9, 5.9, 0.0), (7.7, 6.7, 2.1), nb, 7, faces="xXyYZ")
+    mesh.add(*grid_quad((9.9, 0.8, 0.5), (0, 3.0, 0), (0, 0, 3.0), max(1, int(8 * s)), max(1, int(8 * s))), 8)
+    cams = {"ref": dict(eye=(0.6, 3.9, 2.0), look=(6.0, 4.3, 1.2), up=(0, 0, 1), near=0.1, far=100.0)}
+    light_cam = dict(eye=(4.0, 4.0, 9.0), look=(4.0, 4.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
+    info = _finish(outdir, "glass%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_GLASS,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(4.0, 4.0, 4.5), glass=GLASS_OF))
+    d_ni = [GLASS_OF.get(k, (1.0, 1.0)) for k in range(len(MATERIALS_GLASS))]
+    # what the loader makes of the MTL's 6-decimal text: transmit = (float)(1 - d), ior = (float)Ni
+    info["transmit"] = np.array([1.0 - float("%.6f" % d) for d, _ in d_ni], dtype=np.float32)
+    info["ior"] = np.array([float("%.6f" % ni) for _, ni in d_ni], dtype=np.float32)
+    return info
 
 
 def ao_directions(S):
