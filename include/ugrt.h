@@ -590,6 +590,45 @@ int ugrt_trace_dda_any_lights_thru(ugrt_ctx *ctx, const unsigned *d_value_list, 
 				   const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
 				   int *d_occluded, const int *d_mat_idx, const float *d_transmit, int num_materials);
 
+/* ---- device: area lights ---------------------------
+ * Soft shadows: num_samples shadow rays per primary hit towards num_samples points of a light's disk, carried by one
+ * any-hit walk of section 6.2 through the uniform grid, one mask word per pixel, and a last integer pass that turns the
+ * share of lit samples into a penumbra.  Per frame: ugrt_ao_rays (the origins) + ugrt_trace_dda_any_area before the
+ * shading call that rewrites the ids, ugrt_shade_area behind the shading, in the place of ugrt_shade_add_shadows.  All
+ * arithmetic is fp32 without contraction. */
+#define UGRT_MAX_AREA_SAMPLES 32
+/* The any-hit walk towards num_samples (1..UGRT_MAX_AREA_SAMPLES) points from each stored origin: for an active pixel
+ * p of the band, bit s of d_mask[p] is exactly what ugrt_trace_dda_any(..., t_max = 1) writes for the ray
+ * {o, sample_pos[s] - o}; o = floats 0..2 of d_orays[6 * p] (what ugrt_ao_rays writes; floats 3..5 are not read), the
+ * subtraction per component in fp32 as ugrt_occlusion_rays forms it: the sample lies at t = 1.  sample_pos is host
+ * memory ([3 * num_samples], world positions, passed on by value).  Bits >= num_samples are 0, inactive pixels of the
+ * band get 0, pixels outside the band are not written; for num_samples <= UGRT_MAX_LIGHTS bit s equals layer s of
+ * ugrt_trace_dda_any_lights on the same origins.  The index space is (pixel group, sample): the num_samples rays of a
+ * pixel sit in neighbouring lanes of one wave, which writes the pixel's word whole, with one store.  One prepare launch
+ * and one ray list serve the call; it clears the band's words.  Options "any_rays_per_wave" (the lanes of a wave that
+ * are given rays; unset: 64), "any_coop" and "dda_blocks" shape the launch and change no result.  Stages
+ * UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of ugrt_trace_dda and what
+ * ugrt_reflect_rays_next told it alone.  num_samples out of range or a null argument: UGRT_EINVAL and nothing is
+ * enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_trace_dda_any_area(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+			    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+			    const float *d_orays, const int *d_oactive, int num_samples, const float *sample_pos,
+			    unsigned *d_mask);
+/* ugrt_trace_dda_any_area that sees through glass: the rule of ugrt_trace_dda_any_thru and nothing else (a triangle
+ * whose material is in range and has transmit > 0 does not occlude; the two loads happen only behind a geometrically
+ * accepted test).  With d_transmit all zero the call writes ugrt_trace_dda_any_area's words.  A null d_mat_idx or
+ * d_transmit: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				 const float *d_orays, const int *d_oactive, int num_samples, const float *sample_pos,
+				 unsigned *d_mask, const int *d_mat_idx, const float *d_transmit, int num_materials);
+/* The penumbra, for the context's band: lit = num_samples - popcount(d_mask[p] & the low num_samples bits), and each of
+ * the pixel's three bytes b becomes (b * (num_samples + 2 * lit)) / (3 * num_samples) in unsigned 32-bit integers.  A
+ * zero mask leaves the pixel as it is, a full one gives b / 3, the byte of ugrt_shade_add_shadows (num_samples = 1 is
+ * ugrt_shade_add_shadows with the flag in bit 0).  Stage UGRT_ST_SHADE.  num_samples outside
+ * 1..UGRT_MAX_AREA_SAMPLES or a null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_shade_area(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_samples);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

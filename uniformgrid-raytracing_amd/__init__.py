@@ -56,6 +56,7 @@ GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM = 0, 1, 2
 MAX_REFLECT_DEPTH = 8  # UGRT_MAX_REFLECT_DEPTH
 MAX_LIGHTS = 8  # UGRT_MAX_LIGHTS
 MAX_AO_DIRS = 32  # UGRT_MAX_AO_DIRS
+MAX_AREA_SAMPLES = 32  # UGRT_MAX_AREA_SAMPLES
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -173,6 +174,9 @@ PROTOTYPES = {
     "ugrt_refract_rays_next": (C.c_int, [_P] * 9 + [C.c_int, _P, _P, C.c_float, _P, _P]),
     "ugrt_trace_dda_any_thru": (C.c_int, [_P] * 8 + [C.c_float, _P, _P, _P, C.c_int]),
     "ugrt_trace_dda_any_lights_thru": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P, _P, _P, C.c_int]),
+    "ugrt_trace_dda_any_area": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P]),
+    "ugrt_trace_dda_any_area_thru": (C.c_int, [_P] * 8 + [C.c_int, _F3, _P, _P, _P, C.c_int]),
+    "ugrt_shade_area": (C.c_int, [_P, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

@@ -19,6 +19,8 @@
 // 6.5) is the same kernel over (direction, ray group): S directions of the hemisphere over each stored normal, formed in
 // registers, one bit of a mask word per direction.  ugrt_trace_dda_any_thru and ugrt_trace_dda_any_lights_thru (DESIGN.md
 // section 6.6) are the same kernel with THRU: an accepted test counts only if the triangle's material does not transmit.
+// ugrt_trace_dda_any_area and its _thru form are the same kernel over (pixel group, sample): the S
+// rays of a pixel towards S points of a light's disk in neighbouring lanes of one wave, one mask word per pixel.
 #include "ugrt_dda.h"
 #include <type_traits>
 
@@ -37,7 +39,7 @@ int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *
 // light l's flags lie at l * level.
 struct AnyRays {
 	typedef float Arg; // t_max
-	static constexpr bool lights = false, hemi = false;
+	static constexpr bool lights = false, hemi = false, area = false;
 };
 struct AnyLights {
 	struct Arg {
@@ -45,7 +47,7 @@ struct AnyLights {
 		int count;
 		size_t level; // W*H
 	};
-	static constexpr bool lights = true, hemi = false;
+	static constexpr bool lights = true, hemi = false, area = false;
 };
 // AnyHemi: from the stored origins along num_dirs directions of the hemisphere over the stored normal
 // (ugrt_trace_dda_any_hemi), up to `radius`.  The index space is (direction, ray group),
@@ -58,8 +60,38 @@ struct AnyHemi {
 		int count;
 		float radius;
 	};
-	static constexpr bool lights = false, hemi = true;
+	static constexpr bool lights = false, hemi = true, area = false;
 };
+// AnyArea: from the stored origins towards `count` = S points (ugrt_trace_dda_any_area); the sample
+// lies at t = 1.  The index space is (pixel group, sample), pixel-major: a group is PPW = max(1, L / S) slots of the ray
+// list (the kernel's RPW argument carries PPW), lane l < PPW * S walks slot lgrp * PPW + l / S towards sample l % S and
+// the lanes behind idle.  The S rays of a pixel share the origin, the entry cell and most cells behind it, and they sit
+// side by side: bit s of the pixel's word is one bit of the wave's ballot, and the pixel's first lane stores the word.
+// The sample is per lane here, so the by-value block cannot be read with scalar loads where it is used: lane 0 copies
+// it to LDS once per wave (uniform indices: scalar loads), and a lane reads its three floats from there per group.
+struct AnyArea {
+	struct Arg {
+		float pos[3 * UGRT_MAX_AREA_SAMPLES]; // by value: uniform over the launch, read from the kernarg segment
+		int count;
+	};
+	static constexpr bool lights = false, hemi = false, area = true;
+};
+// Which slot of its group (pix) and which sample (smp) a lane serves: lane / S and lane % S, the quotient by a
+// multiplication that is exact for lane < 64 and S <= 32.  They are formed again where they are used, before and behind
+// the walk (the lane id is made opaque), so the walk carries no register for them.
+__device__ __forceinline__ void d_area_lane(int lane, u32 S, u32 &pix, u32 &smp)
+{
+	u32 l = (u32)lane;
+	asm volatile("" : "+v"(l));
+	pix = (l * ((65536u + S - 1u) / S)) >> 16;
+	smp = l - pix * S;
+}
+// (function-scope LDS: only the kernels that call this carry it)
+__device__ __forceinline__ float *d_area_lds()
+{
+	__shared__ float s_pos[3 * UGRT_MAX_AREA_SAMPLES];
+	return s_pos;
+}
 
 // THRU: which triangles a ray passes: f is see-through when m = mat_idx[f] is in range and
 // transmit[m] > 0.  The plain kernels take the empty block: their arguments and their code stay what they were.
@@ -111,7 +143,8 @@ __device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, flo
 }
 
 // `occluded` of the band was cleared by the prepare kernel (AnyLights: layer 0; the layers behind by the host call): only
-// the flags of occluded rays are written (AnyHemi: `occluded` is the mask words, bit s is OR-ed in by direction s's lane)
+// the flags of occluded rays are written (AnyHemi: `occluded` is the mask words, bit s is OR-ed in by direction s's lane;
+// AnyArea: the mask words, a non-zero word is stored whole by its pixel's first lane)
 template <bool REC, class Aim, bool THRU = false>
 __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__restrict__ value_list,
 							const u32 *__restrict__ span, const u32 *__restrict__ offset,
@@ -130,8 +163,21 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 		t_max = 1.0f;
 	else if constexpr (Aim::hemi)
 		t_max = aim.radius;
+	else if constexpr (Aim::area)
+		t_max = 1.0f;
 	else
 		t_max = aim;
+	// AnyArea: the samples in LDS
+	if constexpr (Aim::area) {
+		const u32 S = (u32)aim.count;
+		float *s_pos = d_area_lds();
+		for (u32 i = 0; i < 3u * S; i++) {
+			const float v = aim.pos[i]; // (uniform index)
+			if (lane == 0)
+				s_pos[i] = v;
+		}
+		__syncthreads();
+	}
 	// AnyLights: the ray count is the device's, so is the number of groups per light (no ray: no group, no division)
 	u32 per_light = 0u, groups = 0u;
 	if constexpr (layered) {
@@ -145,8 +191,15 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 			light = grp / per_light;
 			lgrp = grp - light * per_light;
 		}
-		const u32 slot = lgrp * RPW + (u32)lane;
+		u32 slot = lgrp * RPW + (u32)lane;
 		bool inb = (u32)lane < RPW && slot < count;
+		u32 asmp = 0u;
+		if constexpr (Aim::area) { // (RPW is the pixels per wave)
+			u32 apix;
+			d_area_lane(lane, (u32)aim.count, apix, asmp);
+			slot = lgrp * RPW + apix;
+			inb = apix < RPW && slot < count;
+		}
 		const int p = inb ? (int)list[slot] : 0;
 		inb = inb && p != -1; // (padding: k_dda_prepare)
 		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
@@ -158,6 +211,8 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 				o[k] = rays[p * 6 + k];
 				if constexpr (Aim::lights)
 					d[k] = aim.pos[3u * light + (u32)k] - o[k];
+				else if constexpr (Aim::area)
+					d[k] = d_area_lds()[3u * asmp + (u32)k] - o[k];
 				else
 					d[k] = rays[p * 6 + 3 + k];
 			}
@@ -251,7 +306,16 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 			}
 			walking = walking && planning; // (planning: the walk goes on behind this window)
 		}
-		if (occ) {
+		if constexpr (Aim::area) {
+			// the pixel's S flags are S neighbouring bits of the ballot (idle and out-of-range lanes hold occ = false)
+			const u32 S = (u32)aim.count;
+			u32 apix, asmp;
+			d_area_lane(lane, S, apix, asmp);
+			const unsigned long long flags = __ballot(occ);
+			const u32 word = (u32)(flags >> ((apix * S) & 63u)) & (S == 32u ? 0xFFFFFFFFu : (1u << S) - 1u);
+			if (inb && asmp == 0u && word != 0u)
+				((u32 *)occluded)[p] = word;
+		} else if (occ) {
 			if constexpr (Aim::lights)
 				(occluded + (size_t)light * aim.level)[p] = 1; // (the layer's base is uniform)
 			else if constexpr (Aim::hemi)
@@ -459,4 +523,75 @@ extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_li
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
+}
+
+// both exports: thru null = ugrt_trace_dda_any_area
+static int trace_dda_any_area(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
+			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
+			      const int *d_oactive, int num_samples, const float *sample_pos, unsigned *d_mask, const ThruArg *thru)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !sample_pos ||
+	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
+	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	if (!G.valid)
+		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const DGrid g = ugrt_dgrid_of(G);
+	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	AnyArea::Arg area = {};
+	for (int k = 0; k < 3 * num_samples; k++)
+		area.pos[k] = sample_pos[k];
+	area.count = num_samples;
+	// launch shape: of a wave's lanes L = "any_rays_per_wave" (unset: all 64) are given rays, PPW pixels' S samples each
+	const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
+	const u32 PPW = L / (u32)num_samples > 0u ? L / (u32)num_samples : 1u;
+	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
+	// ONE prepare launch and one ray list, taken as ugrt_trace_dda_any takes them (the turn of the ray counters, the
+	// ticket, the bitmap); it clears the band's mask words, and the walk stores the non-zero ones
+	u32 *list, *dcount;
+	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
+	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, (int *)d_mask, d_span, true, nullptr, &list, &dcount);
+	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
+	if (rc)
+		return rc;
+	// persistent single-wave workgroups over the pixel groups; "dda_blocks" caps them as it caps ugrt_trace_dda's
+	int blocks = launch_blocks_for((u32)ctx->npix / PPW + 1u);
+	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
+		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
+	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
+	if (thru)
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyArea, true> : k_trace_dda_any<false, AnyArea, true>), dim3(blocks),
+				   dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist,
+				   d_trilist, rec, d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
+	else
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyArea> : k_trace_dda_any<false, AnyArea>), dim3(blocks), dim3(64), 0,
+				   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
+				   d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
+				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
+	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+extern "C" int ugrt_trace_dda_any_area(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				       const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				       const float *d_orays, const int *d_oactive, int num_samples, const float *sample_pos,
+				       unsigned *d_mask)
+{
+	return trace_dda_any_area(ctx, "trace_dda_any_area", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
+				  d_oactive, num_samples, sample_pos, d_mask, nullptr);
+}
+
+extern "C" int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					    const float *d_orays, const int *d_oactive, int num_samples, const float *sample_pos,
+					    unsigned *d_mask, const int *d_mat_idx, const float *d_transmit, int num_materials)
+{
+	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
+	return trace_dda_any_area(ctx, "trace_dda_any_area_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
+				  d_oactive, num_samples, sample_pos, d_mask, &thru);
 }

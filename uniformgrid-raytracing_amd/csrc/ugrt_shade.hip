@@ -422,6 +422,41 @@ extern "C" int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned
 	return UGRT_OK;
 }
 
+// Area lights (not in the reference): the pass in the place of k_add_shadows.  bit s of mask =
+// the shadow ray towards sample s of the light's disk is occluded; a byte goes from b (every sample lit) to b / 3 (none).
+__global__ __launch_bounds__(PX_THREADS) void k_shade_area(unsigned char *__restrict__ d_img, const u32 *__restrict__ mask,
+							    u32 num_samples, u32 low_bits, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	const u32 m = mask[pixelID] & low_bits;
+	if (m != 0u) {
+		const u32 lit = num_samples - (u32)__popc(m);
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			d_img[pixelID * 3 + k] =
+				(unsigned char)(((u32)d_img[pixelID * 3 + k] * (num_samples + 2u * lit)) / (3u * num_samples));
+	}
+}
+
+extern "C" int ugrt_shade_area(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_samples)
+{
+	if (!ctx || !d_img || !d_mask)
+		return ugrt_fail(UGRT_EINVAL, "shade_area: null argument");
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "shade_area: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AREA_SAMPLES);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const u32 low_bits = num_samples == 32 ? 0xFFFFFFFFu : (1u << num_samples) - 1u;
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_area, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_img, d_mask, (u32)num_samples, low_bits, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // several lights (the reference's loop over h_numLights, main.cu:148-203, runs with one and
 // its shading kernels index light 0): k_shade<false> and k_add_shadows once per light and the mean of the bytes, in

@@ -368,6 +368,28 @@ class Context:
                                                  _ptr(faces), _ptr(orays), _ptr(oactive), n, pos, _ptr(occluded),
                                                  _ptr(mat_idx), _ptr(transmit), num_materials))
 
+    # -- area lights -------------------------------------
+    def trace_dda_any_area(self, value, span, offset, verts, faces, orays, oactive, samples, mask):
+        """Bit s of mask[p] = trace_dda_any's flag (t_max 1) of the ray from orays' origin of p towards samples[s];
+        samples: host floats [S, 3], world positions (scenes.area_samples); mask: uint32 words (an int32 tensor serves)."""
+        flat = None if samples is None else _f3(np.asarray(samples, np.float32).reshape(-1))
+        n = 0 if samples is None else len(flat) // 3
+        check(lib.ugrt_trace_dda_any_area(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                          _ptr(orays), _ptr(oactive), n, flat, _ptr(mask)))
+
+    def trace_dda_any_area_thru(self, value, span, offset, verts, faces, orays, oactive, samples, mask, mat_idx, transmit,
+                                num_materials):
+        """trace_dda_any_area in which a triangle whose material has transmit > 0 does not occlude."""
+        flat = None if samples is None else _f3(np.asarray(samples, np.float32).reshape(-1))
+        n = 0 if samples is None else len(flat) // 3
+        check(lib.ugrt_trace_dda_any_area_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                               _ptr(orays), _ptr(oactive), n, flat, _ptr(mask), _ptr(mat_idx),
+                                               _ptr(transmit), num_materials))
+
+    def shade_area(self, img, mask, num_samples):
+        """Each byte b of a pixel becomes (b * (S + 2 * lit)) // (3 * S), lit = S - popcount(mask & low S bits)."""
+        check(lib.ugrt_shade_area(self._h, _ptr(img), _ptr(mask), int(num_samples)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

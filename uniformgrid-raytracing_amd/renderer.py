@@ -23,7 +23,9 @@ per light and one shading pass averages the lights (one-stream frame, no reflect
 one-stream frame ends with ambient occlusion: S hemisphere rays per primary hit through the uniform grid, and a last
 pass that scales the image by the share of open rays.  With ``refract=True`` a level's ray goes
 through a hit whose material transmits instead of being mirrored, and the reflected hits' shadow walk sees through such
-materials.
+materials.  With ``area=S`` the one-stream single-light frame casts soft shadows: S shadow rays
+per primary hit towards a disk around the light through the uniform grid in the place of the light-space shadow stage,
+and a last pass that darkens the image by the share of occluded samples.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -33,7 +35,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -131,6 +133,29 @@ def check_ao(ao, ao_radius, two_streams=False):
         raise ValueError("ao needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
                          "side context")
     return int(ao), float(np.float32(ao_radius))
+
+
+def check_area(area, area_radius, shadows=True, lights=None, two_streams=False):
+    """area: an integer 0..MAX_AREA_SAMPLES (0: off, and nothing else is looked at); area > 0 needs a number
+    area_radius > 0, shadows=True, a single-light frame (lights: setup.lights) and the one-stream Renderer (two_streams:
+    the two-stream and banded frames keep the uniform grid on a side context), or ValueError (before anything is
+    enqueued); DESIGN.md section 6.7.  Returns (area, radius or None)."""
+    if isinstance(area, (bool, np.bool_)) or not isinstance(area, (int, np.integer)) or not 0 <= area <= MAX_AREA_SAMPLES:
+        raise ValueError("area must be an integer in 0..%d, not %r" % (MAX_AREA_SAMPLES, area))
+    if area == 0:
+        return 0, None
+    if isinstance(area_radius, (bool, np.bool_)) or not isinstance(area_radius, (int, float, np.integer, np.floating)):
+        raise ValueError("area=%d needs area_radius, a number greater than 0, not %r" % (area, area_radius))
+    if not float(np.float32(area_radius)) > 0.0:
+        raise ValueError("area_radius must be greater than 0, not %r" % (area_radius,))
+    if not shadows:
+        raise ValueError("area needs shadows=True: the area light's penumbra takes the place of the hard shadows")
+    if lights is not None:
+        raise ValueError("area needs a single-light frame: area lights under setup.lights are not built")
+    if two_streams:
+        raise ValueError("area needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on "
+                         "a side context")
+    return int(area), float(np.float32(area_radius))
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -288,6 +313,20 @@ def ao_pass(c, f, cam_pos, dirs, radius):
     c.trace_dda_any_hemi(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, dirs, radius, f.ao_mask)
 
 
+def area_pass(c, f, cam_pos, samples, thru=None):
+    """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
+    buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
+    f.area_mask.  thru (a refract frame: (mat_idx, transmit, num_materials)): the walk that sees through glass.  Runs
+    behind the uniform grid's build and before the shading call that rewrites the ids."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    if thru is None:
+        c.trace_dda_any_area(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples, f.area_mask)
+    else:
+        c.trace_dda_any_area_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples,
+                                  f.area_mask, *thru)
+
+
 def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
     depth shading with the occluded levels darkened, at every depth), then add_shadows."""
@@ -384,6 +423,8 @@ class _Frame:
         # (_ensure_ao_buffers); the direction sets asked for so far, by their size
         self.ao_rays = self.ao_active = self.ao_mask = None
         self._ao_dirs = {}
+        # area: the mask of occluded samples of the light's disk (_ensure_area_buffers; the origins share ao_rays)
+        self.area_mask = None
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -391,15 +432,26 @@ class _Frame:
         """ao_rays [6 W*H], ao_active [W*H] and ao_mask [W*H] (uint32 words in an int32 tensor), allocated on first use;
         returns the ao directions of scenes.ao_directions."""
         t, N, dev = self.torch, self.N, self.image.device
-        if self.ao_mask is None:
+        if self.ao_rays is None:
             self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
             self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+        if self.ao_mask is None:
             self.ao_mask = t.zeros(N, dtype=t.int32, device=dev)
         if ao not in self._ao_dirs:
             from .scenes import ao_directions
 
             self._ao_dirs[ao] = ao_directions(ao)
         return self._ao_dirs[ao]
+
+    def _ensure_area_buffers(self):
+        """area_mask [W*H] (uint32 words in an int32 tensor) and the origins' buffers ao_rays / ao_active, allocated on
+        first use."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.ao_rays is None:
+            self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+        if self.area_mask is None:
+            self.area_mask = t.zeros(N, dtype=t.int32, device=dev)
 
     def _ensure_light_buffers(self, num_lights):
         """shadowed_lights [L, W*H]: light l's is_shadowed, allocated once for the most lights asked for."""
@@ -582,7 +634,7 @@ class Renderer(_Frame, _Band):
             self._worker = None
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
-                reflect_lights=False, ao=0, ao_radius=None, refract=False):
+                reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -599,7 +651,13 @@ class Renderer(_Frame, _Band):
         has transmit > 0 (Snell's law with the material's ior; total internal reflection mirrors) and is mirrored where
         the material only reflects; the shading weighs the next level with transmit there; with reflect_shadows the
         any-hit walk does not count glass as an occluder.  The primary shadow stage still does: a glass ball casts a
-        full shadow."""
+        full shadow.
+        area (one-stream renderer, single-light frames, needs shadows=True; 0: off): the light is a disk of radius
+        area_radius around the light camera's eye, perpendicular to its view; area = 1..32 shadow rays per primary hit
+        towards scenes.area_samples' points of it walk the uniform grid in the place of the light-space shadow stage
+        (is_shadowed is left alone), area_mask holds the occluded samples' bits and the image goes from b (every sample
+        lit) to b / 3 (none); with refract the walk sees through glass."""
+        area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
@@ -622,7 +680,7 @@ class Renderer(_Frame, _Band):
         camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         use_light_camera(ctx, lcam)
-        if shadows:
+        if shadows and not area:
             map_rays(ctx, self, self)
             build_grid(ctx, self, GRID_SPHERICAL, self.shards)
             light_grid = ctx.grid_ptrs(GRID_SPHERICAL)
@@ -634,11 +692,16 @@ class Renderer(_Frame, _Band):
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
-        elif ao:
+        elif ao or area:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
+        if area:
+            area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup),
+                      (self.d_matidx, self.d_transmit, self.num_materials) if self.refract else None)
         if ao:
             ao_pass(ctx, self, self.cam_pos, *ao)
-        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
+        if area:
+            ctx.shade_area(self.image, self.area_mask, area)
         if ao:
             ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
 
@@ -646,6 +709,15 @@ class Renderer(_Frame, _Band):
         """(directions, radius) for ao_pass and shade_ao, with the buffers in place; None: the frame has no ambient
         occlusion (ao == 0, or nothing is shaded)."""
         return (self._ensure_ao_buffers(ao), ao_radius) if ao and shade else None
+
+    def _area_stage(self, area, area_radius, setup):
+        """The sample points for area_pass, with the buffers in place: the disk of area_radius around the light camera's
+        eye (the point the hard shadows are cast from), perpendicular to its look - eye."""
+        from .scenes import area_samples
+
+        self._ensure_area_buffers()
+        eye = np.asarray(setup.light_camera["eye"], np.float64)
+        return area_samples(area, eye, np.asarray(setup.light_camera["look"], np.float64) - eye, area_radius)
 
     def _display_lights(self, setup, lights, shadows, shade, ao=None):
         """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
@@ -894,7 +966,8 @@ class BandedRenderer(_Frame):
         return [self.aux] + [b.ctx for b in self._per_band]
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
-                ao_radius=None, refract=False):
+                ao_radius=None, refract=False, area=0, area_radius=None):
+        check_area(area, area_radius, shadows, getattr(setup, "lights", None), True)  # raises with area > 0, as ao does
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)

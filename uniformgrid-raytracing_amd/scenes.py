@@ -419,3 +419,24 @@ def ao_directions(S):
     r = np.sqrt((s + 0.5) / float(S))
     phi = s * (np.pi * (3.0 - np.sqrt(5.0)))
     return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r)], 1).astype(np.float32)
+
+
+def area_samples(S, centre, axis, radius):
+    """The S points of an area light's disk: radius `radius` around `centre`, perpendicular to
+    `axis`.  With a = axis / |axis|, k the index of the smallest |a[k]| (ties go to the lowest k), T = normalize(a x e_k)
+    and B = a x T: r = radius * sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), point
+    centre + r cos phi * T + r sin phi * B.  Computed in float64 and returned as float32 [S, 3]: the library only ever
+    sees these floats as data."""
+    c = np.asarray(centre, np.float64).reshape(3)
+    a = np.asarray(axis, np.float64).reshape(3)
+    a = a / np.sqrt((a * a).sum())
+    k = int(np.argmin(np.abs(a)))  # (the first of equal minima)
+    e = np.zeros(3)
+    e[k] = 1.0
+    T = np.cross(a, e)
+    T = T / np.sqrt((T * T).sum())
+    B = np.cross(a, T)
+    s = np.arange(int(S), dtype=np.float64)
+    r = float(radius) * np.sqrt((s + 0.5) / float(S))
+    phi = s * (np.pi * (3.0 - np.sqrt(5.0)))
+    return (c + (r * np.cos(phi))[:, None] * T + (r * np.sin(phi))[:, None] * B).astype(np.float32)
