@@ -261,6 +261,16 @@ int ugrt_grid_build_spherical(ugrt_ctx *ctx, const int *d_facelist, const float 
 /* uniform world-space grid for the reflection bounce (README.md:1; no reference code) */
 int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces,
 			    const float bbmin[3], const float bbmax[3]);
+/* The grid's arrays.  The merged lists exist after this call: a build of the PERSPECTIVE grid that has wide
+ * triangles -- triangles whose cell range is the whole band; every cell holds them -- stops behind its spans and
+ * offsets (no z slabs, at most 4096 wide triangles; every other build merges at once) and puts off the merge of the
+ * sorted narrow references with the wide ids, which only writes the same few hundred ids into every cell.  This call
+ * enqueues that merge if it is still pending (it does not wait), and so does ugrt_trace_primary when it is handed this
+ * grid's arrays by pointers kept from an earlier call; a frame that traces through ugrt_trace_primary_grid never runs
+ * it.  What is handed out is element for element what a build that merges at once writes.  The merge goes onto the
+ * context's stream as it is when it is asked for; ugrt_ctx_set_stream waits for the old stream before it switches, so
+ * a merge on the new stream still runs behind the build it completes.  With profiling on, its time is booked under
+ * the build's bounds stage, whenever it runs. */
 int ugrt_grid_get_info(ugrt_ctx *ctx, int which, ugrt_grid_info *out);
 /* With slabs > 1 the arrays of ugrt_grid_info hold num_cells = cells * slabs entries, cell-major
  * (key = cell * slabs + slab, grid_kernel.cu:322).  This call synchronises the stream. */
@@ -324,6 +334,16 @@ int ugrt_scan_pair(ugrt_ctx *ctx, const unsigned *d_in_a, unsigned *d_out_a, con
 int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
 		       const unsigned *d_offset, float *d_normal, float *d_t_value, float *d_ray_dir,
 		       int *d_shadowed, int *d_intersect_id, const float *d_vertlist, const int *d_trilist);
+/* The same trace through the context's current perspective grid (ugrt_grid_build_perspective must have run), without
+ * asking for its lists: while the build's merge is put off (ugrt_grid_get_info) the tracer reads a cell's run of the
+ * sorted narrow references and then the one list of wide triangle ids, and breaks ties between equal distances by
+ * triangle id -- inside a cell the ids ascend, so that is the reference's "first in the list wins".  Every output is
+ * bit for bit that of ugrt_trace_primary on the merged arrays.  With no merge pending (no wide triangle, z slabs, the
+ * lists have been asked for) the call IS ugrt_trace_primary on the grid's arrays.  ugrt_ctx_get_state
+ * "primary_deferred_merges" counts the builds that put their merge off, "primary_completed_merges" those of them whose
+ * merge was carried out after all, "primary_merge_pending" is 1 while one is put off.  No reference counterpart. */
+int ugrt_trace_primary_grid(ugrt_ctx *ctx, float *d_normal, float *d_t_value, float *d_ray_dir, int *d_shadowed,
+			    int *d_intersect_id, const float *d_vertlist, const int *d_trilist);
 /* getEffectiveRayGridMapping(...), per_frame_funcs.h:97 -> mapSort_Effective_kernel.
  * d_map holds 2n entries, n = pixels of this context's band. */
 int ugrt_map_rays_to_light(ugrt_ctx *ctx, const float *d_t_value, const float *d_ray_dir, unsigned *d_map,

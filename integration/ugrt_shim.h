@@ -99,6 +99,12 @@ public:
 	{
 		UGRT_CHECK(ugrt_trace_primary(g_ctx, value, span, offset, normal, t, dir, shadowed, id, verts, tris));
 	}
+	// no reference counterpart: the same trace through the grid buildGrid left, without its merged lists (ugrt.h:
+	// ugrt_trace_primary_grid; a frame loop that calls this instead of trace never reads d_triangle_value_list)
+	void traceGrid(float *normal, float *t, float *dir, int *shadowed, int *id, float *verts, int *tris)
+	{
+		UGRT_CHECK(ugrt_trace_primary_grid(g_ctx, normal, t, dir, shadowed, id, verts, tris));
+	}
 };
 
 class Shader { // shader.h:14-31

@@ -148,6 +148,7 @@ PROTOTYPES = {
     "ugrt_scan": (C.c_int, [_P, _P, _P, C.c_size_t, C.c_int]),
     "ugrt_scan_pair": (C.c_int, [_P, _P, _P, _P, _P, C.c_size_t, C.c_int]),
     "ugrt_trace_primary": (C.c_int, [_P] * 11),
+    "ugrt_trace_primary_grid": (C.c_int, [_P] * 8),
     "ugrt_map_rays_to_light": (C.c_int, [_P, _P, _P, _P, _P, C.c_float, C.c_float]),
     "ugrt_sort_rays": (C.c_int, [_P, _P, _P, C.c_uint, C.POINTER(C.c_uint)]),
     "ugrt_sort_rays_chunks": (C.c_int, [_P, C.POINTER(C.c_uint)]),

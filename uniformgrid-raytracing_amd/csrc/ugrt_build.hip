@@ -777,6 +777,15 @@ static int plan_async(ugrt_ctx *ctx, BuildPlan &p)
 
 static inline u32 build_parts(const BuildPlan &p) { return (p.Rn + BUILD_THREADS - 1) / BUILD_THREADS; }
 
+// The screen grid's merge is put off: its wide triangles are the same few hundred ids in every cell of the band, the
+// frame's own tracer (ugrt_trace_primary_grid) reads them from their one list, and the merged lists are written when
+// somebody asks for them (ugrt_grid_complete).  Only where the rank kernel orders the wide ids (up to 4096 of them) and
+// a cell is one list (no z slabs); every other build merges at once.
+static inline bool build_defers_merge(const ugrt_ctx *ctx, const BuildPlan &p)
+{
+	return p.G == &ctx->grid[UGRT_GRID_PERSPECTIVE] && !p.no_wide && p.W <= 4096u && ctx->cfg.slabs == 1;
+}
+
 // (the launches for the narrow references are skipped when there are none: only a waiting build can know that, the launch
 // size of an asynchronous one is never zero)
 static int build_fill(ugrt_ctx *ctx, const BuildPlan &p)
@@ -831,7 +840,7 @@ static int build_sort(ugrt_ctx *ctx, const BuildPlan *b, int n)
 	for (int i = 0; i < n; i++) {
 		const BuildPlan &p = b[i];
 		u32 *wl = (u32 *)p.G->wide.p, *wsorted = wl + p.F;
-		if (p.no_wide)
+		if (p.no_wide || build_defers_merge(ctx, p))
 			continue;
 		if (p.W > 4096u) {
 			// many wide triangles (a tiny grid, and a waiting build): radix sort of the ids, the values are not used
@@ -847,6 +856,48 @@ static int build_sort(ugrt_ctx *ctx, const BuildPlan *b, int n)
 	return UGRT_OK;
 }
 
+// the two merge kernels of a build with wide triangles: the merged lists go to key[0] / val[0].  `report_tail`: the
+// build's report ends here (an asynchronous build that merges at once)
+static void build_merge(ugrt_ctx *ctx, const BuildPlan &p, u32 *report_tail)
+{
+	Grid &G = *p.G;
+	const u32 C = p.C;
+	hipStream_t st = ctx->stream;
+	u32 *k0 = (u32 *)G.key[0].p, *k1 = (u32 *)G.key[1].p, *v0 = (u32 *)G.val[0].p, *v1 = (u32 *)G.val[1].p;
+	u32 *wsorted = (u32 *)G.wide.p + p.F;
+	u32 *cstart = (u32 *)G.span.p + C, *used = cstart + C;
+	const WideBox wb = { p.W, (u32)p.ny, (u32)p.nz, (u32)p.ylo, (u32)p.yhi, p.rw };
+	if (p.Rn)
+		hipLaunchKernelGGL(k_merge_narrow, dim3(build_parts(p)), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, (const u32 *)v1, p.Rn,
+				   (const u32 *)cstart, (const u32 *)G.offset.p, (const u32 *)wsorted, wb, k0, v0);
+	u32 blocks = C < 256u * 32u ? C : 256u * 32u;
+	hipLaunchKernelGGL(k_merge_wide, dim3(blocks), dim3(64), 0, st, (const u32 *)v1, (const u32 *)cstart,
+			   (const u32 *)G.span.p, (const u32 *)G.offset.p, (const u32 *)wsorted, C, wb, k0, v0, report_tail,
+			   (const u32 *)used, (const u32 *)p.status);
+}
+
+// The merge a screen-grid build put off (build_defers_merge), on the context's stream: the order of the wide ids, then
+// the two merge kernels.  They read what the build left -- the sorted narrow references, the run starts, spans and
+// offsets, the wide ids and, for an asynchronous build, the counts on the device -- none of which changes before the
+// next build of the grid.  Does nothing when no merge is pending.  (The stream may have been changed since the build:
+// ugrt_ctx_set_stream waits for the old stream first, so the build's kernels have finished by then.)
+int ugrt_grid_complete(ugrt_ctx *ctx, Grid &G)
+{
+	if (!G.valid || !G.merge_pending)
+		return UGRT_OK;
+	const BuildPlan &p = G.merge_plan;
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_BUILD_BOUNDS);
+	hipLaunchKernelGGL(k_wide_rank, dim3((p.W + BUILD_THREADS - 1) / BUILD_THREADS), dim3(BUILD_THREADS), 0, ctx->stream,
+			   (const u32 *)G.wide.p, p.W, (u32 *)G.wide.p + p.F, (const u32 *)p.rw);
+	build_merge(ctx, p, nullptr);
+	ugrt_prof_end(ctx, UGRT_ST_BUILD_BOUNDS);
+	UGRT_HIP(hipGetLastError());
+	G.merge_pending = false;
+	ctx->merges_completed++;
+	return UGRT_OK;
+}
+
 static int build_finish(ugrt_ctx *ctx, const BuildPlan &p)
 {
 	Grid &G = *p.G;
@@ -854,11 +905,11 @@ static int build_finish(ugrt_ctx *ctx, const BuildPlan &p)
 	hipStream_t st = ctx->stream;
 	int rc;
 	u32 *k0 = (u32 *)G.key[0].p, *k1 = (u32 *)G.key[1].p, *v0 = (u32 *)G.val[0].p, *v1 = (u32 *)G.val[1].p;
-	u32 *wsorted = (u32 *)G.wide.p + p.F;
 	u32 *cstart = (u32 *)G.span.p + C, *used = cstart + C;
 	u32 *report_tail = p.report ? p.report + 2 : nullptr;
 	const WideBox wb = { p.W, (u32)p.ny, (u32)p.nz, (u32)p.ylo, (u32)p.yhi, p.rw };
 	const u32 nparts = build_parts(p);
+	const bool defer = build_defers_merge(ctx, p);
 	ugrt_prof_begin(ctx, UGRT_ST_BUILD_BOUNDS);
 	if (p.Rn)
 		hipLaunchKernelGGL(k_bounds, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, p.Rn, cstart, (u32 *)G.span.p,
@@ -866,10 +917,10 @@ static int build_finish(ugrt_ctx *ctx, const BuildPlan &p)
 	else
 		UGRT_HIP(hipMemsetAsync(G.span.p, 0, (size_t)C * 8 + 4, st)); // (otherwise cleared by k_fill)
 	// spans + offsets in one kernel (an empty build: the cleared words are the spans); an asynchronous build without
-	// wide triangles ends its report there (with them: k_merge_wide)
+	// wide triangles, or one whose merge is put off, ends its report there (one that merges at once: k_merge_wide)
 	{
 		SpanLoad sl = { (const u32 *)cstart, (u32 *)G.span.p, used, wb };
-		SpanTail tl = { p.no_wide ? report_tail : (u32 *)nullptr, (const u32 *)used, (const u32 *)p.status, wide_counter(G, p.F) };
+		SpanTail tl = { (p.no_wide || defer) ? report_tail : (u32 *)nullptr, (const u32 *)used, (const u32 *)p.status, wide_counter(G, p.F) };
 		if ((rc = ugrt_scan_launch<false>(ctx, sl, (u32 *)G.offset.p, (size_t)C, tl)))
 			return rc;
 		G.wide_zeroed = wide_counter(G, p.F);
@@ -878,14 +929,14 @@ static int build_finish(ugrt_ctx *ctx, const BuildPlan &p)
 		G.keys = k1;
 		G.vals = v1;
 	} else {
-		// the merged lists go to key[0]/val[0]
-		if (p.Rn)
-			hipLaunchKernelGGL(k_merge_narrow, dim3(nparts), dim3(BUILD_THREADS), 0, st, (const u32 *)k1, (const u32 *)v1, p.Rn,
-					   (const u32 *)cstart, (const u32 *)G.offset.p, (const u32 *)wsorted, wb, k0, v0);
-		u32 blocks = C < 256u * 32u ? C : 256u * 32u;
-		hipLaunchKernelGGL(k_merge_wide, dim3(blocks), dim3(64), 0, st, (const u32 *)v1, (const u32 *)cstart,
-				   (const u32 *)G.span.p, (const u32 *)G.offset.p, (const u32 *)wsorted, C, wb, k0, v0, report_tail,
-				   (const u32 *)used, (const u32 *)p.status);
+		// the merged lists go to key[0]/val[0]: now, or when they are asked for (spans and offsets are final either way)
+		if (defer) {
+			G.merge_plan = p;
+			G.merge_pending = true;
+			ctx->merges_deferred++;
+		} else {
+			build_merge(ctx, p, report_tail);
+		}
 		G.keys = k0;
 		G.vals = v0;
 	}
@@ -957,6 +1008,7 @@ static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, in
 		G.async_pending = false;
 	}
 	G.valid = false;
+	G.merge_pending = false; // (a merge nobody asked for is dropped with the grid it belonged to)
 	G.C = C;
 	G.F = F;
 	ugrt_prof_begin(ctx, UGRT_ST_BUILD_SCAN);

@@ -213,6 +213,12 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = ctx->rs_atomic_rank < 0 ? -1 : (ctx->rs_atomic_rank == 1 && ctx->opt[UGRT_OPT_SORT_RANK] != 0 ? 1 : 0);
 	else if (strcmp(key, "shadow_key_bits") == 0)
 		*value = (long long)ctx->shadow_key_bits;
+	else if (strcmp(key, "primary_deferred_merges") == 0)
+		*value = (long long)ctx->merges_deferred;
+	else if (strcmp(key, "primary_completed_merges") == 0)
+		*value = (long long)ctx->merges_completed;
+	else if (strcmp(key, "primary_merge_pending") == 0)
+		*value = ctx->grid[UGRT_GRID_PERSPECTIVE].valid && ctx->grid[UGRT_GRID_PERSPECTIVE].merge_pending ? 1 : 0;
 	else if (strcmp(key, "recip_mismatches") == 0) {
 		// exhaustive: every float through the tracers' short reciprocal against the division (ugrt_dev.h d_recip_det)
 		unsigned long long bad = 0;
@@ -350,6 +356,9 @@ extern "C" int ugrt_grid_get_info(ugrt_ctx *ctx, int which, ugrt_grid_info *out)
 	Grid &G = ctx->grid[which];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "grid_get_info: grid %d has not been built", which);
+	// the lists are handed out: a screen grid whose merge was put off is merged now (enqueued, no wait)
+	if (int rc = ugrt_grid_complete(ctx, G))
+		return rc;
 	// pointers and total_refs are known on the host since the build; cells_used is fetched lazily and
 	// is final after the next ugrt_ctx_synchronize (the reference only prints it, frustum_grid.h:338)
 	out->d_triangle_value_list = G.vals;

@@ -61,6 +61,23 @@ struct DevBuf {
 	size_t cap = 0;
 };
 
+struct Grid;
+// What the stages of a grid build (ugrt_build.hip: build_fill, build_sort, build_finish) need.  A waiting build has
+// read the counts back and holds them exactly; an asynchronous build holds the sizes its launches and buffers were
+// made for and `rw`, where its kernels find the counts.  The context keeps the plans of an open batch.
+struct BuildPlan {
+	Grid *G;
+	int F, ny, nz, ylo, yhi;
+	u32 C;
+	unsigned long long active; // cells that hold every wide triangle
+	u32 Rn, W, R;              // narrow references, wide triangles, all references: the counts, or (rw) their caps
+	u32 *rw;                   // {narrow references, wide triangles} on the device; nullptr = the host knows them
+	u32 *report, *status;      // asynchronous build: its four report words (UGRT_PIN_REPORT), the device's status word
+	bool no_wide;              // no wide triangle (or: built for none), the sorted references are the final lists
+	bool own_sort;             // the built-in radix sort, not the library's
+	bool prehist;              // the fill counts the first digit of the keys for the sort (ugrt_rs_hist.h)
+};
+
 struct Grid {
 	DevBuf rng, sizes, scan;          // per triangle
 	DevBuf parts;                     // fill: triangle of the first reference of every workgroup
@@ -80,6 +97,11 @@ struct Grid {
 	float ug[12] = { 0 }; // uniform grid: lo[3], cell[3], inv cell[3]
 	bool valid = false;
 	const u32 *wide_zeroed = nullptr; // the wide-triangle counter the last build's scan left at zero (build_prologue)
+	// Screen grid only: the build stopped behind its spans and offsets.  The sorted narrow references (val[1], run starts
+	// behind the spans), the wide ids (wide) and `merge_plan` stay as they are until the next build of the grid;
+	// ugrt_grid_complete (ugrt_build.hip) writes the merged lists into key[0] / val[0] when somebody asks for them.
+	bool merge_pending = false;
+	BuildPlan merge_plan = {};
 };
 
 // layout of ugrt_ctx::d_small (u32 words of device scratch)
@@ -116,22 +138,6 @@ struct Grid {
 #define UGRT_PRIMARY_STATS 16
 static_assert(UGRT_DSMALL_DDA + 2 * UGRT_DDA_STATS <= UGRT_DSMALL_RW, "the DDA's counters run into the build counts");
 static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
-
-// What the stages of a grid build (ugrt_build.hip: build_fill, build_sort, build_finish) need.  A waiting build has
-// read the counts back and holds them exactly; an asynchronous build holds the sizes its launches and buffers were
-// made for and `rw`, where its kernels find the counts.  The context keeps the plans of an open batch.
-struct BuildPlan {
-	Grid *G;
-	int F, ny, nz, ylo, yhi;
-	u32 C;
-	unsigned long long active; // cells that hold every wide triangle
-	u32 Rn, W, R;              // narrow references, wide triangles, all references: the counts, or (rw) their caps
-	u32 *rw;                   // {narrow references, wide triangles} on the device; nullptr = the host knows them
-	u32 *report, *status;      // asynchronous build: its four report words (UGRT_PIN_REPORT), the device's status word
-	bool no_wide;              // no wide triangle (or: built for none), the sorted references are the final lists
-	bool own_sort;             // the built-in radix sort, not the library's
-	bool prehist;              // the fill counts the first digit of the keys for the sort (ugrt_rs_hist.h)
-};
 
 struct ProfPair {
 	hipEvent_t a, b;
@@ -206,6 +212,9 @@ struct ugrt_ctx {
 	unsigned long long stats[8] = { 0 };
 	unsigned long long dda_stats[UGRT_DDA_STATS] = { 0 }; // ugrt_stats_dda
 	unsigned long long primary_stats[UGRT_PRIMARY_STATS] = { 0 }; // ugrt_stats_primary
+	// screen-grid builds that put their merge off, and those of them whose merge was carried out later after all
+	// (ugrt_ctx_get_state "primary_deferred_merges", "primary_completed_merges")
+	unsigned long long merges_deferred = 0, merges_completed = 0;
 };
 
 #define UGRT_HIP(call)                                                                            \
@@ -227,6 +236,8 @@ static inline const float4 *ugrt_trirec_of(const ugrt_ctx *ctx, const float *d_v
 // NUM_SLABS > 1: span/offset over all slabs of each of the C light cells (ugrt_build.hip)
 int ugrt_slab_union(ugrt_ctx *ctx, const u32 *d_span, const u32 *d_offset, u32 C, u32 slabs, const u32 **uspan,
 		    const u32 **uoffset);
+// carries out the merge a screen-grid build put off (Grid::merge_pending); does nothing when none is pending
+int ugrt_grid_complete(ugrt_ctx *ctx, Grid &G);
 float *ugrt_ctx_tex(ugrt_ctx *ctx); // device copy of the 5x5x4 direction table
 // status words the asynchronous calls have reported so far (each report carries the device's word as it stood then)
 static inline u32 ugrt_reported_status(const ugrt_ctx *ctx)

@@ -26,6 +26,18 @@ struct WItem {
 	u32 multi; // primary: bit 0 = the cell is split across items; bits 1..15 its row, bits 16..31 its column of cells
 };
 
+// The context's own screen grid while its merge is put off (ugrt_build.hip: build_defers_merge): the references of a
+// cell are its run of the sorted NARROW references followed by the wide triangles, which are the same for every cell
+// of the band and are read from their one list.  span[] already counts both.
+struct WideSrc {
+	const u32 *nvals;  // sorted narrow references
+	const u32 *cstart; // per cell: where its run starts in nvals (meaningless for a cell without a run)
+	const u32 *span;   // per cell: narrow run + W
+	const u32 *wl;     // the W wide triangle ids, in no particular order
+	const u32 *rw;     // asynchronous build: {narrow references, wide triangles} on the device; nullptr: W below
+	u32 W;
+};
+
 // ---------------------------------------------------------------------------
 // work lists
 // ---------------------------------------------------------------------------
@@ -48,7 +60,10 @@ struct WlPrimaryLoad {
 		}
 	}
 };
-struct WlPrimaryStore {
+// (REL: the context's own grid through a WideSrc -- the items of a cell count from the start of the cell's stream, not
+// of the value list)
+template <bool REL>
+struct WlPrimaryStoreT {
 	static constexpr bool active = true;
 	const u32 *span, *offset;
 	u32 nby, gy_lo, rows, SEG;
@@ -61,7 +76,7 @@ struct WlPrimaryStore {
 				break;
 			const u32 cx = i / rows, cy = gy_lo + (i % rows);
 			const u32 cell = cx * nby + cy;
-			const u32 sp = span[cell], off = offset[cell], cnt = v[k];
+			const u32 sp = span[cell], off = REL ? 0u : offset[cell], cnt = v[k];
 			const u32 first = incl[k] - cnt;
 			for (u32 s = 0; s < cnt; s++) {
 				WItem w;
@@ -76,6 +91,8 @@ struct WlPrimaryStore {
 	}
 };
 
+typedef WlPrimaryStoreT<false> WlPrimaryStore;
+
 // ---------------------------------------------------------------------------
 // primary rays: rckernel_alpha, trace_kernel.cu:84-270 (NUM_SLABS = 1)
 // ---------------------------------------------------------------------------
@@ -88,8 +105,8 @@ struct PrimaryOut {
 };
 
 // trace_kernel.cu:56-82 isWithin + :230-267 epilogue for one pixel.
-// `ref` = index into value_list of the nearest accepted triangle, ~0u = none.
-template <bool REC>
+// `ref` = index into value_list of the nearest accepted triangle (WIDE: the triangle itself), ~0u = none.
+template <bool REC, bool WIDE = false>
 __device__ __forceinline__ void d_finish_pixel(const CamBlock &cam, const PrimaryOut &o, int pixelID,
 					       const float *dir, float oldt, u32 ref,
 					       const u32 *__restrict__ value_list, const float *__restrict__ verts,
@@ -107,7 +124,7 @@ __device__ __forceinline__ void d_finish_pixel(const CamBlock &cam, const Primar
 		ok = ugrt_floor2i(hz * 1.0f) == 0;
 	}
 	if (ok) {
-		u32 face = value_list[ref];
+		u32 face = WIDE ? ref : value_list[ref];
 		float tri[9];
 		// the record holds the same two edge subtractions (one 48-B gather instead of three indices + nine floats)
 		d_load_triangle<REC>(rec, verts, tris, face, 0.0f, 0.0f, 0.0f, tri);
@@ -168,7 +185,13 @@ enum { PS_ITEMS, PS_BATCHES, PS_BATCHES_KEPT, PS_REFS, PS_TILE_SURVIVORS, PS_SUR
        PS_ROUNDS_DIV, PS_ROUNDS_V, PS_ROUNDS_T, PS_LANE_TESTS, PS_HITS, PS_PRUNABLE, PS_PRUNED, PS_END };
 static_assert(PS_END <= UGRT_PRIMARY_STATS, "primary work counters");
 
-template <bool REC, bool COUNT>
+// WIDE: the references come from a WideSrc, and the word that breaks ties between equal t's is the TRIANGLE ID instead
+// of the position in the cell's list.  Inside one cell of a grid built here the ids are unique and strictly ascending
+// (the fill writes a cell's references in id order, the sort is stable, duplicates are dropped, the merge keeps the
+// order), so "the first of the list wins" and "the smaller id wins" are the same rule -- and a minimum over ids does
+// not care in which order the stream delivers them, which is what lets the wide triangles come last and unordered.
+// The position-keyed instantiations stay for lists a caller supplies, which need not be ascending.
+template <bool REC, bool WIDE, bool COUNT>
 __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const float *__restrict__ tex,
 						       const WItem *__restrict__ items,
 						       const u32 *__restrict__ nitems_p,
@@ -176,7 +199,7 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 						       const float *__restrict__ verts, const int *__restrict__ tris,
 						       const float4 *__restrict__ rec, PrimaryOut out,
 						       u64 *__restrict__ best, int p0, unsigned long long *__restrict__ counters,
-						       u32 ORDER, u32 CHUNK, u32 SLICES)
+						       u32 ORDER, u32 CHUNK, u32 SLICES, WideSrc ws)
 {
 	__shared__ __attribute__((aligned(16))) float lds[SURV_CAP * TRI_STRIDE];
 	__shared__ unsigned short jobs[JOB_CAP]; // survivor slot | lane offset of the quadrant << 7
@@ -225,11 +248,26 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 		// item's last reference instead of being masked: loads under a divergent branch make the compiler
 		// wait for everything outstanding at the join.)
 		const u32 last = w.count ? w.count - 1u : 0u;
-		u32 id_next = 0;
+		// WIDE: reference i of the item is number w.begin + i of the cell's stream: narrow run, then the wide list (ONE
+		// load from a selected address: see above about loads under divergent branches)
+		u32 ns = 0;
+		const u32 *np = nullptr;
+		if (WIDE) {
+			const u32 Wn = ws.rw ? ws.rw[1] : ws.W, sp = ws.span[w.cell];
+			ns = sp > Wn ? sp - Wn : 0u;
+			np = ws.nvals + ws.cstart[w.cell];
+		}
+		auto fetch = [&](u32 i) -> u32 {
+			if (!WIDE)
+				return value_list[w.begin + i];
+			const u32 s = w.begin + i;
+			return *(s < ns ? np + s : ws.wl + (s - ns));
+		};
+		u32 id_next = 0, id_rec = 0; // id_rec: the triangle whose record is in ra, rb, rcx
 		float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra;
 		float rcx = 0.f;
 		if (REC && w.count)
-			id_next = value_list[w.begin + min((u32)lane, last)];
+			id_next = fetch(min((u32)lane, last));
 		const int bx = (int)(w.multi >> 16), by = (int)((w.multi >> 1) & 0x7FFFu);
 		const int col = bx * 8 + (lane & 7), row = by * 8 + (lane >> 3);
 		const int pixelID = row * cam.W + col;
@@ -239,7 +277,9 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 			ra = rec[id_next * 3u + 0u];
 			rb = rec[id_next * 3u + 1u];
 			rcx = reinterpret_cast<const float *>(rec)[id_next * 12u + 8u];
-			id_next = value_list[w.begin + min(64u + (u32)lane, last)];
+			if (WIDE)
+				id_rec = id_next;
+			id_next = fetch(min(64u + (u32)lane, last));
 		}
 		// direction boxes: reduce inside the quadrants (lane bits 0,1,3,4), then across them (bits 2,5);
 		// centre and half width are formed per lane and read from one lane of each quadrant, so that
@@ -278,20 +318,26 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 				bool keep = false;
 				float t9[9];
 				CullTri ct;
+				u32 tie = w.begin + b + (u32)lane; // what breaks ties: the position in the list (WIDE: the triangle id)
 				if (REC) {
 					// (the same subtractions d_load_triangle makes)
 					t9[0] = ex - ra.x, t9[1] = ey - ra.y, t9[2] = ez - ra.z;
 					t9[3] = ra.w, t9[4] = rb.x, t9[5] = rb.y, t9[6] = rb.z, t9[7] = rb.w, t9[8] = rcx;
+					if (WIDE)
+						tie = id_rec, id_rec = id_next;
 					ra = rec[id_next * 3u + 0u];
 					rb = rec[id_next * 3u + 1u];
 					rcx = reinterpret_cast<const float *>(rec)[id_next * 12u + 8u];
-					id_next = value_list[w.begin + min(b + 128u + (u32)lane, last)];
+					id_next = fetch(min(b + 128u + (u32)lane, last));
 					if ((u32)lane < cnt) {
 						ct = d_cull_prep(&t9[0], &t9[3], &t9[6]);
 						keep = !d_cull_cr(ct, tb);
 					}
 				} else if ((u32)lane < cnt) {
-					d_load_triangle<REC>(rec, verts, tris, value_list[w.begin + b + lane], ex, ey, ez, t9);
+					const u32 face = fetch(b + (u32)lane);
+					if (WIDE)
+						tie = face;
+					d_load_triangle<REC>(rec, verts, tris, face, ex, ey, ez, t9);
 					ct = d_cull_prep(&t9[0], &t9[3], &t9[6]);
 					keep = !d_cull_cr(ct, tb);
 				}
@@ -311,7 +357,7 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 						float4 *dst = reinterpret_cast<float4 *>(&lds[slot * TRI_STRIDE]);
 						dst[0] = make_float4(t9[0], t9[1], t9[2], t9[3]);
 						dst[1] = make_float4(t9[4], t9[5], t9[6], t9[7]);
-						dst[2] = make_float4(t9[8], __uint_as_float(w.begin + b + lane), 0.0f, 0.0f);
+						dst[2] = make_float4(t9[8], __uint_as_float(tie), 0.0f, 0.0f);
 					}
 					nsurv += (u32)__popcll(mask);
 				}
@@ -472,7 +518,7 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 		const unsigned long long mine = s_best[lane];
 		if (!(w.multi & 1u)) {
 			const bool hit = mine != ~0ull;
-			d_finish_pixel<REC>(cam, out, pixelID, dir, hit ? __uint_as_float((u32)(mine >> 32)) : 99999999.9f,
+			d_finish_pixel<REC, WIDE>(cam, out, pixelID, dir, hit ? __uint_as_float((u32)(mine >> 32)) : 99999999.9f,
 					    hit ? (u32)mine : 0xFFFFFFFFu, value_list, verts, tris, rec);
 		} else if (mine != ~0ull) {
 			atomicMin(reinterpret_cast<unsigned long long *>(&best[pixelID - p0]), mine);
@@ -592,8 +638,8 @@ __global__ __launch_bounds__(64) void k_trace_primary_slabs(CamBlock cam, const 
 	}
 }
 
-// pixels of split cells: take the merged (t, ref), finish, re-arm the slot
-template <bool REC>
+// pixels of split cells: take the merged (t, ref), finish, re-arm the slot (WIDE: ref is the triangle itself)
+template <bool REC, bool WIDE>
 __global__ __launch_bounds__(256) void k_resolve_primary(CamBlock cam, const float *__restrict__ tex,
 							  const u32 *__restrict__ span,
 							  const u32 *__restrict__ value_list,
@@ -617,7 +663,7 @@ __global__ __launch_bounds__(256) void k_resolve_primary(CamBlock cam, const flo
 	float oldt = (b == ~0ull) ? 99999999.9f : __uint_as_float((u32)(b >> 32));
 	if (b == ~0ull)
 		ref = 0xFFFFFFFFu;
-	d_finish_pixel<REC>(cam, out, pixelID, dir, oldt, ref, value_list, verts, tris, rec);
+	d_finish_pixel<REC, WIDE>(cam, out, pixelID, dir, oldt, ref, value_list, verts, tris, rec);
 }
 
 // total refs behind a span/offset pair: known for the context's own grids,
@@ -637,14 +683,25 @@ static int refs_of(ugrt_ctx *ctx, const u32 *d_span, const u32 *d_offset, u32 C,
 	return UGRT_OK;
 }
 
-// FrustumTracer::trace, frustum_tracer.h:35-58
-extern "C" int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
-				  const unsigned *d_offset, float *d_normal, float *d_t_value, float *d_ray_dir,
-				  int *d_shadowed, int *d_intersect_id, const float *d_vertlist, const int *d_trilist)
+// the two kernels of a trace, in their position-keyed or id-keyed (WideSrc) instantiations
+typedef void (*TraceKernel)(CamBlock, const float *, const WItem *, const u32 *, const u32 *, const float *, const int *,
+			    const float4 *, PrimaryOut, u64 *, int, unsigned long long *, u32, u32, u32, WideSrc);
+typedef void (*ResolveKernel)(CamBlock, const float *, const u32 *, const u32 *, const float *, const int *, const float4 *,
+			      PrimaryOut, u64 *, int, int, u32);
+template <bool WIDE>
+static TraceKernel trace_kernel_of(bool use_rec, bool counting)
 {
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_normal || !d_t_value || !d_ray_dir || !d_shadowed ||
-	    !d_intersect_id || !d_vertlist || !d_trilist)
-		return ugrt_fail(UGRT_EINVAL, "trace_primary: null argument");
+	return counting ? (use_rec ? k_trace_primary<true, WIDE, true> : k_trace_primary<false, WIDE, true>)
+			: (use_rec ? k_trace_primary<true, WIDE, false> : k_trace_primary<false, WIDE, false>);
+}
+
+// FrustumTracer::trace, frustum_tracer.h:35-58.  wide: null = the references are value_list[offset[c] ...]; otherwise
+// the context's own screen grid with its merge put off (d_value_list is then not read)
+static int trace_primary_run(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+			     const unsigned *d_offset, float *d_normal, float *d_t_value, float *d_ray_dir,
+			     int *d_shadowed, int *d_intersect_id, const float *d_vertlist, const int *d_trilist,
+			     const WideSrc *wide)
+{
 	UGRT_HIP(hipSetDevice(ctx->device));
 	hipStream_t st = ctx->stream;
 	const int rows = ctx->cfg.row_end - ctx->cfg.row_begin;
@@ -681,11 +738,14 @@ extern "C" int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, c
 		return rc;
 	u32 *incl = (u32 *)ctx->wscan.p;
 	WItem *items = (WItem *)ctx->witems.p;
+	const WideSrc ws = wide ? *wide : WideSrc{ nullptr, nullptr, nullptr, nullptr, nullptr, 0u };
 	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
 	{
 		const WlPrimaryLoad load = { d_span, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG };
 		const WlPrimaryStore store = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items };
-		if ((rc = ugrt_scan_launch<true>(ctx, load, incl, ncell, ScanTailNone(), store)))
+		const WlPrimaryStoreT<true> store_rel = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items };
+		if ((rc = wide ? ugrt_scan_launch<true>(ctx, load, incl, ncell, ScanTailNone(), store_rel)
+			       : ugrt_scan_launch<true>(ctx, load, incl, ncell, ScanTailNone(), store)))
 			return rc;
 	}
 	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
@@ -717,26 +777,64 @@ extern "C" int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, c
 	const u32 p_order = ctx->opt[UGRT_OPT_PRIMARY_ORDER] == 0 ? 0u : 1u;
 	u32 p_chunk = ctx->opt[UGRT_OPT_PRIMARY_CHUNK] > 0 ? (u32)ctx->opt[UGRT_OPT_PRIMARY_CHUNK] : (p_order ? 32u : 64u);
 	p_chunk = p_chunk > 64u ? 64u : (p_chunk < 4u ? 4u : p_chunk);
-	const auto kernel = counting ? (use_rec ? k_trace_primary<true, true> : k_trace_primary<false, true>)
-				     : (use_rec ? k_trace_primary<true, false> : k_trace_primary<false, false>);
+	const TraceKernel kernel = wide ? trace_kernel_of<true>(use_rec, counting) : trace_kernel_of<false>(use_rec, counting);
 	if (counting)
 		UGRT_HIP(hipMemsetAsync(pc, 0, UGRT_PRIMARY_STATS * 8, st));
 	hipLaunchKernelGGL(kernel, dim3(pwaves), dim3(64), 0, st, ctx->cam, tex, (const WItem *)items,
 			   (const u32 *)(incl + (ncell - 1)), d_value_list, d_vertlist, d_trilist, rec, out, (u64 *)ctx->best.p,
 			   ctx->p0, pc, p_order, p_chunk,
-			   p_slices ? 1u : (p_run ? ((p_run_log2 + 1u) << 1) | (ctx->opt[UGRT_OPT_PRIMARY_CENTRE] != 0 ? 1u : 0u) : 0u));
+			   p_slices ? 1u : (p_run ? ((p_run_log2 + 1u) << 1) | (ctx->opt[UGRT_OPT_PRIMARY_CENTRE] != 0 ? 1u : 0u) : 0u), ws);
 	if (counting)
 		UGRT_HIP(hipMemcpyAsync(ctx->primary_stats, pc, UGRT_PRIMARY_STATS * 8, hipMemcpyDeviceToHost, st));
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_PRIMARY);
 	UGRT_HIP(hipGetLastError());
 	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	hipLaunchKernelGGL(use_rec ? k_resolve_primary<true> : k_resolve_primary<false>, dim3((ctx->npix + 255) / 256),
+	const ResolveKernel resolve = wide ? (use_rec ? k_resolve_primary<true, true> : k_resolve_primary<false, true>)
+					   : (use_rec ? k_resolve_primary<true, false> : k_resolve_primary<false, false>);
+	hipLaunchKernelGGL(resolve, dim3((ctx->npix + 255) / 256),
 			   dim3(256), 0, st, ctx->cam, tex, d_span, d_value_list, d_vertlist, d_trilist, rec, out,
 			   (u64 *)ctx->best.p, ctx->p0, ctx->npix, SEG);
 	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
 	UGRT_HIP(hipGetLastError());
 	ctx->stats[0] = cap; // upper bound of primary work items
 	return UGRT_OK;
+}
+
+extern "C" int ugrt_trace_primary(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				  const unsigned *d_offset, float *d_normal, float *d_t_value, float *d_ray_dir,
+				  int *d_shadowed, int *d_intersect_id, const float *d_vertlist, const int *d_trilist)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_normal || !d_t_value || !d_ray_dir || !d_shadowed ||
+	    !d_intersect_id || !d_vertlist || !d_trilist)
+		return ugrt_fail(UGRT_EINVAL, "trace_primary: null argument");
+	// the context's own screen-grid arrays (pointers kept from an earlier ugrt_grid_get_info: the buffers rarely move)
+	// while the merge of the last build is put off: the value list is about to be read, so it is written first
+	Grid &G = ctx->grid[UGRT_GRID_PERSPECTIVE];
+	if (G.valid && G.merge_pending && d_value_list == (const unsigned *)G.vals && d_span == (const unsigned *)G.span.p &&
+	    d_offset == (const unsigned *)G.offset.p)
+		if (int rc = ugrt_grid_complete(ctx, G))
+			return rc;
+	return trace_primary_run(ctx, d_value_list, d_span, d_offset, d_normal, d_t_value, d_ray_dir, d_shadowed,
+				 d_intersect_id, d_vertlist, d_trilist, nullptr);
+}
+
+// The same trace through the context's current screen grid, without asking for its lists: while the merge of the last
+// ugrt_grid_build_perspective is put off, the tracer reads the sorted narrow references and the one list of wide
+// triangles, and the merged lists are never written.  Otherwise (no wide triangle, z slabs, a merge that has been
+// carried out) this is ugrt_trace_primary on the grid's arrays.
+extern "C" int ugrt_trace_primary_grid(ugrt_ctx *ctx, float *d_normal, float *d_t_value, float *d_ray_dir,
+				       int *d_shadowed, int *d_intersect_id, const float *d_vertlist, const int *d_trilist)
+{
+	if (!ctx || !d_normal || !d_t_value || !d_ray_dir || !d_shadowed || !d_intersect_id || !d_vertlist || !d_trilist)
+		return ugrt_fail(UGRT_EINVAL, "trace_primary_grid: null argument");
+	Grid &G = ctx->grid[UGRT_GRID_PERSPECTIVE];
+	if (!G.valid)
+		return ugrt_fail(UGRT_EINVAL, "trace_primary_grid: the perspective grid has not been built");
+	const WideSrc ws = { (const u32 *)G.val[1].p, (const u32 *)G.span.p + G.C, (const u32 *)G.span.p, (const u32 *)G.wide.p,
+			     (const u32 *)G.merge_plan.rw, G.merge_plan.W };
+	return trace_primary_run(ctx, (const unsigned *)G.vals, (const unsigned *)G.span.p, (const unsigned *)G.offset.p, d_normal,
+				 d_t_value, d_ray_dir, d_shadowed, d_intersect_id, d_vertlist, d_trilist,
+				 (G.merge_pending && ctx->cfg.slabs == 1) ? &ws : nullptr);
 }
 
 // work counters of the primary tracer's last counting launch (UGRT_FLAG_COUNT_WORK), in the order of the PS_* enum

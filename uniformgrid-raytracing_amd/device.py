@@ -149,7 +149,8 @@ class Context:
 
     def get_state(self, key):
         """Counters and findings of the context: "radix_launches", "sort_rank_atomic", "shadow_key_bits" (key bits the
-        last shadow pass sorted its rays on), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
+        last shadow pass sorted its rays on), "primary_deferred_merges" / "primary_completed_merges" /
+        "primary_merge_pending" (screen-grid builds that put their merge off, those merged later after all, one pending), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
         on the device), "f2i_mismatches" (the same for the device's float -> integer conversions), "lane_reduce_mismatches"
         (the tracers' DPP / permlane-swap reductions against __shfl_xor)."""
         v = C.c_longlong(0)
@@ -188,8 +189,20 @@ class Context:
 
     # -- tracing -----------------------------------------------------------
     def trace_primary(self, value, span, offset, normal, t, ray_dir, shadowed, ids, verts, faces):
+        """FrustumTracer::trace on the given lists; value, span and offset all None: through the context's current
+        perspective grid (trace_primary_grid), which is how a frame traces the grid it has just built."""
+        if value is None and span is None and offset is None:
+            return self.trace_primary_grid(normal, t, ray_dir, shadowed, ids, verts, faces)
+        if value is None or span is None or offset is None:
+            raise ValueError("trace_primary: give value, span and offset, or None for all three (the context's own grid)")
         check(lib.ugrt_trace_primary(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(normal), _ptr(t),
                                      _ptr(ray_dir), _ptr(shadowed), _ptr(ids), _ptr(verts), _ptr(faces)))
+
+    def trace_primary_grid(self, normal, t, ray_dir, shadowed, ids, verts, faces):
+        """trace_primary through the context's current perspective grid, without asking for its lists: a build whose
+        merge of the wide triangles is put off (see ugrt.h) is traced from the narrow runs and the one wide list."""
+        check(lib.ugrt_trace_primary_grid(self._h, _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(shadowed), _ptr(ids),
+                                          _ptr(verts), _ptr(faces)))
 
     def map_rays_to_light(self, t, ray_dir, d_map, cam_pos, xM, yM):
         check(lib.ugrt_map_rays_to_light(self._h, _ptr(t), _ptr(ray_dir), _ptr(d_map), _ptr(cam_pos), xM, yM))

@@ -35,7 +35,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_PERSPECTIVE, GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -169,8 +169,9 @@ def camera_pass(c, f, b, setup, cam):
     b._upload_cam_pos(cam.worldori)
     c.upload_camera(cam.camcoords)
     c.grid_build_perspective(f.d_faces, f.d_verts, f.F)
-    value, span, offset, _ = c.grid_ptrs(GRID_PERSPECTIVE)
-    c.trace_primary(value, span, offset, f.normal, f.t, f.dir, f.is_shadowed, f.intersect_id, f.d_verts, f.d_faces)
+    # (no lists: the trace goes through the grid as the build left it, ugrt_trace_primary_grid; asking for the grid's
+    # lists would make the build merge its wide triangles into every cell first)
+    c.trace_primary(None, None, None, f.normal, f.t, f.dir, f.is_shadowed, f.intersect_id, f.d_verts, f.d_faces)
 
 
 def use_light_camera(c, lcam):
