@@ -649,6 +649,52 @@ int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_value_list, co
  * 1..UGRT_MAX_AREA_SAMPLES or a null argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_shade_area(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_samples);
 
+/* ---- device: interleaved sample sets and the edge-aware gather ----
+ * Neighbouring pixels aim at different sample sets of the light's disk, and a small gather over pixels of the same
+ * surface averages their masks: with a 4x4 tile of sets and a 5x5 gather a pixel sees 16 * num_samples points of the
+ * light for num_samples rays and one image pass.  Per frame: ugrt_trace_dda_any_area_sets in the place of
+ * ugrt_trace_dda_any_area, ugrt_filter_visibility + ugrt_shade_area_vis in the place of ugrt_shade_area.  All arithmetic
+ * is fp32 without contraction or unsigned 32-bit integer. */
+#define UGRT_MAX_AREA_SET_TILE 4     /* set_w, set_h */
+#define UGRT_MAX_AREA_SET_POINTS 512 /* set_w * set_h * num_samples */
+#define UGRT_MAX_FILTER_RADIUS 8
+/* ugrt_trace_dda_any_area with one sample set per pixel of a set_w x set_h tile: pixel p of the band has the full-image
+ * coordinates x = p % width, y = p / width and the set k(p) = (y % set_h) * set_w + (x % set_w); bit s of d_mask[p] is
+ * exactly what ugrt_trace_dda_any(..., t_max = 1) writes for the ray {o, d_sample_pos[3 * (k(p) * num_samples + s) ..] - o}.
+ * d_sample_pos is DEVICE memory, [set_w * set_h][num_samples][3] floats (the by-value argument block cannot hold it);
+ * every workgroup copies it to LDS once.  Everything else -- bits >= num_samples, inactive pixels, pixels outside the
+ * band, the prepare launch, the ticket, the bitmap, the options, the stages, leaving the split-walk history alone -- is
+ * ugrt_trace_dda_any_area's, and with set_w = set_h = 1 the call writes that call's words.  set_w or set_h outside
+ * 1..UGRT_MAX_AREA_SET_TILE, num_samples outside 1..UGRT_MAX_AREA_SAMPLES, set_w * set_h * num_samples >
+ * UGRT_MAX_AREA_SET_POINTS or a null argument: UGRT_EINVAL (the message names the argument) and nothing is enqueued. */
+int ugrt_trace_dda_any_area_sets(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				 const float *d_orays, const int *d_oactive, int num_samples, int set_w, int set_h,
+				 const float *d_sample_pos, unsigned *d_mask);
+/* ugrt_trace_dda_any_area_sets that sees through glass: the rule of ugrt_trace_dda_any_thru and nothing else. */
+int ugrt_trace_dda_any_area_sets_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				      const float *d_orays, const int *d_oactive, int num_samples, int set_w, int set_h,
+				      const float *d_sample_pos, unsigned *d_mask, const int *d_mat_idx,
+				      const float *d_transmit, int num_materials);
+/* The gather over mask words.  d_orays / d_oactive are what ugrt_ao_rays wrote ({o, n} per pixel); radius R is
+ * 0..UGRT_MAX_FILTER_RADIUS, num_bits S 1..32, d_vis unsigned [2 * width * height].  For an active pixel p = (x, y) of
+ * the band the sums run over q = (x + dx, y + dy), |dx|, |dy| <= R, q inside the image, inside the band's rows and
+ * active; q counts when it is p itself, or when (n_p0*n_q0 + n_p1*n_q1) + n_p2*n_q2 >= normal_cos and
+ * |(d0*n_p0 + d1*n_p1) + d2*n_p2| <= plane_tol with d = o_q - o_p per component (a comparison with a NaN rejects q).
+ * With w = (R + 1 - |dx|) * (R + 1 - |dy|) and open_q = S - popcount(d_mask[q] & the low S bits):
+ * d_vis[2p] = sum of w * open_q, d_vis[2p + 1] = sum of w (at most 32 * 6561 and 6561).  Inactive pixels of the band
+ * get (0, 0), pixels outside the band are not written.  Stage UGRT_ST_SHADE.  radius or num_bits out of range, a
+ * plane_tol that is negative or a NaN, or a null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_filter_visibility(ugrt_ctx *ctx, const unsigned *d_mask, int num_bits, const float *d_orays,
+			   const int *d_oactive, int radius, float normal_cos, float plane_tol, unsigned *d_vis);
+/* The penumbra from the gathered sums, for the context's band: with num = d_vis[2p] and den = d_vis[2p + 1] != 0 each
+ * of the pixel's three bytes b becomes (b * (num_samples * den + 2 * num)) / (3 * num_samples * den) in unsigned 32-bit
+ * integers (the largest product is 255 * 3 * 32 * 6561); den = 0 leaves the pixel as it is.  Behind a gather of
+ * radius 0 the bytes are ugrt_shade_area's.  Stage UGRT_ST_SHADE.  num_samples outside 1..UGRT_MAX_AREA_SAMPLES or a
+ * null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_samples);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

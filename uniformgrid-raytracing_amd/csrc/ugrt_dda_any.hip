@@ -21,6 +21,8 @@
 // section 6.6) are the same kernel with THRU: an accepted test counts only if the triangle's material does not transmit.
 // ugrt_trace_dda_any_area and its _thru form are the same kernel over (pixel group, sample): the S
 // rays of a pixel towards S points of a light's disk in neighbouring lanes of one wave, one mask word per pixel.
+// ugrt_trace_dda_any_area_sets and its _thru form are that walk with one sample set per pixel of a
+// set_w x set_h tile of the image: the sets lie in device memory, a workgroup copies them to LDS once.
 #include "ugrt_dda.h"
 #include <type_traits>
 
@@ -39,7 +41,7 @@ int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *
 // light l's flags lie at l * level.
 struct AnyRays {
 	typedef float Arg; // t_max
-	static constexpr bool lights = false, hemi = false, area = false;
+	static constexpr bool lights = false, hemi = false, area = false, sets = false;
 };
 struct AnyLights {
 	struct Arg {
@@ -47,7 +49,7 @@ struct AnyLights {
 		int count;
 		size_t level; // W*H
 	};
-	static constexpr bool lights = true, hemi = false, area = false;
+	static constexpr bool lights = true, hemi = false, area = false, sets = false;
 };
 // AnyHemi: from the stored origins along num_dirs directions of the hemisphere over the stored normal
 // (ugrt_trace_dda_any_hemi), up to `radius`.  The index space is (direction, ray group),
@@ -60,7 +62,7 @@ struct AnyHemi {
 		int count;
 		float radius;
 	};
-	static constexpr bool lights = false, hemi = true, area = false;
+	static constexpr bool lights = false, hemi = true, area = false, sets = false;
 };
 // AnyArea: from the stored origins towards `count` = S points (ugrt_trace_dda_any_area); the sample
 // lies at t = 1.  The index space is (pixel group, sample), pixel-major: a group is PPW = max(1, L / S) slots of the ray
@@ -74,8 +76,24 @@ struct AnyArea {
 		float pos[3 * UGRT_MAX_AREA_SAMPLES]; // by value: uniform over the launch, read from the kernarg segment
 		int count;
 	};
-	static constexpr bool lights = false, hemi = false, area = true;
+	static constexpr bool lights = false, hemi = false, area = true, sets = false;
 };
+// AnyAreaSets: AnyArea with a sample set per pixel (ugrt_trace_dda_any_area_sets): pixel p = (x, y)
+// of the full image aims at set k(p) = (y % set_h) * set_w + (x % set_w) of `pos`, device memory [set_w * set_h][S][3].
+// The table is too large for the by-value block (6 KB at 16 sets of 32): every workgroup copies it to dynamic LDS once,
+// with the whole wave's loads, and a lane reads its three floats at 3 * (k(p) * S + sample).  k(p) is formed from the
+// pixel id behind the list's load and used there only: it costs the walk no register.
+struct AnyAreaSets {
+	struct Arg {
+		const float *pos;
+		int count;          // S
+		u32 set_w, set_h;   // 1..4 each
+		u32 width;          // of the full image
+	};
+	static constexpr bool lights = false, hemi = false, area = true, sets = true;
+};
+// (dynamic LDS, its base 16-byte aligned; AnyAreaSets is the only aim that has any)
+extern __shared__ __attribute__((aligned(16))) float s_sets_pos[];
 // Which slot of its group (pix) and which sample (smp) a lane serves: lane / S and lane % S, the quotient by a
 // multiplication that is exact for lane < 64 and S <= 32.  They are formed again where they are used, before and behind
 // the walk (the lane id is made opaque), so the walk carries no register for them.
@@ -168,7 +186,19 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 	else
 		t_max = aim;
 	// AnyArea: the samples in LDS
-	if constexpr (Aim::area) {
+	if constexpr (Aim::sets) {
+		// 3 * K * S floats: float4 per lane while four are left (a 16-byte aligned table), then single floats
+		const u32 total = 3u * (u32)aim.count * aim.set_w * aim.set_h;
+		u32 done = 0u;
+		if (((size_t)aim.pos & 15u) == 0u) {
+			for (u32 i = 4u * (u32)lane; i + 4u <= total; i += 256u)
+				*(float4 *)(s_sets_pos + i) = *(const float4 *)(aim.pos + i);
+			done = total & ~3u;
+		}
+		for (u32 i = done + (u32)lane; i < total; i += 64u)
+			s_sets_pos[i] = aim.pos[i];
+		__syncthreads();
+	} else if constexpr (Aim::area) {
 		const u32 S = (u32)aim.count;
 		float *s_pos = d_area_lds();
 		for (u32 i = 0; i < 3u * S; i++) {
@@ -202,6 +232,13 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 		}
 		const int p = inb ? (int)list[slot] : 0;
 		inb = inb && p != -1; // (padding: k_dda_prepare)
+		if constexpr (Aim::sets) { // the lane's sample becomes its index into the table: set k(p), sample asmp
+			// (the divisors are made opaque here: their reciprocals are formed per group, not kept over the walk)
+			u32 width = aim.width, set_w = aim.set_w, set_h = aim.set_h;
+			asm volatile("" : "+s"(width), "+s"(set_w), "+s"(set_h));
+			const u32 y = (u32)p / width, x = (u32)p - y * width;
+			asmp += ((y % set_h) * set_w + x % set_w) * (u32)aim.count;
+		}
 		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
 		int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
 		bool walking = false, occ = false;
@@ -211,6 +248,8 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 				o[k] = rays[p * 6 + k];
 				if constexpr (Aim::lights)
 					d[k] = aim.pos[3u * light + (u32)k] - o[k];
+				else if constexpr (Aim::sets)
+					d[k] = s_sets_pos[3u * asmp + (u32)k] - o[k];
 				else if constexpr (Aim::area)
 					d[k] = d_area_lds()[3u * asmp + (u32)k] - o[k];
 				else
@@ -525,29 +564,22 @@ extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_li
 	return UGRT_OK;
 }
 
-// both exports: thru null = ugrt_trace_dda_any_area
-static int trace_dda_any_area(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
-			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
-			      const int *d_oactive, int num_samples, const float *sample_pos, unsigned *d_mask, const ThruArg *thru)
+// the area walks: the prepare launch and the kernel over (pixel group, sample) for Aim = AnyArea or AnyAreaSets, with
+// `lds` bytes of dynamic LDS
+template <class Aim>
+static int area_walk(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+		     const float *d_vertlist, const int *d_trilist, const float *d_orays, const int *d_oactive,
+		     const typename Aim::Arg &area, size_t lds, unsigned *d_mask, const ThruArg *thru)
 {
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !sample_pos ||
-	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
-		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
-	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
-		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
 	UGRT_HIP(hipSetDevice(ctx->device));
 	const DGrid g = ugrt_dgrid_of(G);
 	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
-	AnyArea::Arg area = {};
-	for (int k = 0; k < 3 * num_samples; k++)
-		area.pos[k] = sample_pos[k];
-	area.count = num_samples;
 	// launch shape: of a wave's lanes L = "any_rays_per_wave" (unset: all 64) are given rays, PPW pixels' S samples each
 	const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
-	const u32 PPW = L / (u32)num_samples > 0u ? L / (u32)num_samples : 1u;
+	const u32 PPW = L / (u32)area.count > 0u ? L / (u32)area.count : 1u;
 	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
 	// ONE prepare launch and one ray list, taken as ugrt_trace_dda_any takes them (the turn of the ray counters, the
 	// ticket, the bitmap); it clears the band's mask words, and the walk stores the non-zero ones
@@ -563,18 +595,66 @@ static int trace_dda_any_area(ugrt_ctx *ctx, const char *who, const unsigned *d_
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
 	if (thru)
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyArea, true> : k_trace_dda_any<false, AnyArea, true>), dim3(blocks),
-				   dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist,
-				   d_trilist, rec, d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, Aim, true> : k_trace_dda_any<false, Aim, true>), dim3(blocks), dim3(64),
+				   lds, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist,
+				   rec, d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
 				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
 	else
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyArea> : k_trace_dda_any<false, AnyArea>), dim3(blocks), dim3(64), 0,
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, Aim> : k_trace_dda_any<false, Aim>), dim3(blocks), dim3(64), lds,
 				   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
 				   d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
 				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
+}
+
+// both exports: thru null = ugrt_trace_dda_any_area
+static int trace_dda_any_area(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
+			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
+			      const int *d_oactive, int num_samples, const float *sample_pos, unsigned *d_mask, const ThruArg *thru)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !sample_pos ||
+	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
+	AnyArea::Arg area = {};
+	for (int k = 0; k < 3 * num_samples; k++)
+		area.pos[k] = sample_pos[k];
+	area.count = num_samples;
+	return area_walk<AnyArea>(ctx, d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays, d_oactive, area, 0, d_mask,
+				  thru);
+}
+
+// both exports: thru null = ugrt_trace_dda_any_area_sets
+static int trace_dda_any_area_sets(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
+				   const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
+				   const int *d_oactive, int num_samples, int set_w, int set_h, const float *d_sample_pos,
+				   unsigned *d_mask, const ThruArg *thru)
+{
+	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !d_sample_pos ||
+	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
+	if (set_w < 1 || set_w > UGRT_MAX_AREA_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w %d is not in 1..%d", who, set_w, UGRT_MAX_AREA_SET_TILE);
+	if (set_h < 1 || set_h > UGRT_MAX_AREA_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_h %d is not in 1..%d", who, set_h, UGRT_MAX_AREA_SET_TILE);
+	if (set_w * set_h * num_samples > UGRT_MAX_AREA_SET_POINTS)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w * set_h * num_samples = %d is more than %d", who, set_w * set_h * num_samples,
+				 UGRT_MAX_AREA_SET_POINTS);
+	AnyAreaSets::Arg area = {};
+	area.pos = d_sample_pos;
+	area.count = num_samples;
+	area.set_w = (u32)set_w;
+	area.set_h = (u32)set_h;
+	area.width = (u32)ctx->cfg.width;
+	// the table's bytes, rounded up to the 16 of the copy's float4 stores (at most 6 KB)
+	const size_t lds = ((size_t)12 * (size_t)(set_w * set_h * num_samples) + 15u) & ~(size_t)15u;
+	return area_walk<AnyAreaSets>(ctx, d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays, d_oactive, area, lds,
+				      d_mask, thru);
 }
 
 extern "C" int ugrt_trace_dda_any_area(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -594,4 +674,24 @@ extern "C" int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_val
 	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
 	return trace_dda_any_area(ctx, "trace_dda_any_area_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
 				  d_oactive, num_samples, sample_pos, d_mask, &thru);
+}
+
+extern "C" int ugrt_trace_dda_any_area_sets(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					    const float *d_orays, const int *d_oactive, int num_samples, int set_w, int set_h,
+					    const float *d_sample_pos, unsigned *d_mask)
+{
+	return trace_dda_any_area_sets(ctx, "trace_dda_any_area_sets", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				       d_orays, d_oactive, num_samples, set_w, set_h, d_sample_pos, d_mask, nullptr);
+}
+
+extern "C" int ugrt_trace_dda_any_area_sets_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+						 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+						 const float *d_orays, const int *d_oactive, int num_samples, int set_w, int set_h,
+						 const float *d_sample_pos, unsigned *d_mask, const int *d_mat_idx,
+						 const float *d_transmit, int num_materials)
+{
+	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
+	return trace_dda_any_area_sets(ctx, "trace_dda_any_area_sets_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				       d_orays, d_oactive, num_samples, set_w, set_h, d_sample_pos, d_mask, &thru);
 }

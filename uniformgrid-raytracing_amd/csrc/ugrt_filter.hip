@@ -1,0 +1,151 @@
+// ugrt_filter.hip -- the edge-aware gather over mask words and the shading behind it (not in the reference; DESIGN.md
+// section 6.8).  Interleaved sample sets (ugrt_trace_dda_any_area_sets) give neighbouring pixels different S points of
+// the light; the gather sums the open bits of the pixels around p that lie on p's surface, with a tent weight, and
+// ugrt_shade_area_vis turns the two sums into ugrt_shade_area's byte.
+#include "ugrt_dev.h"
+
+#define PX_THREADS 256
+#define FV_TW 32 // tile: FV_TH / 8 pixels per lane of a 256-lane workgroup, a wave = two rows of 32
+#ifndef FV_TH
+#define FV_TH 8 // (a multiple of 8; make EXTRA=-DFV_TH=16 builds the taller tile that DESIGN.md section 6.8 measures)
+#endif
+static_assert(FV_TH % 8 == 0 && FV_TH >= 8 && FV_TH <= 32, "tile height" /* 63 KB of LDS at radius 8 */);
+#define FV_ACTIVE 0x80000000u
+
+// (dynamic LDS, its base 16-byte aligned: seven planes of LW * LH words, each a multiple of 16 bytes)
+extern __shared__ __attribute__((aligned(16))) u32 s_fv[];
+
+// The tile and its halo of R are staged once as structure-of-arrays: o[3], n[3] and one word = open | FV_ACTIVE (0 for a
+// pixel outside the image, outside the band's rows or inactive: it is never accepted, and its floats are zeros).  A
+// staged row is LW = FV_TW + 2R words; the 32 lanes of a half-wave read 32 consecutive words of one row for every
+// (dx, dy), which is conflict-free for ds_read_b32 at any row stride.  The loops over (dx, dy) are uniform in R, every
+// index lies inside the staged rectangle for every lane (pixels of the tile past the image's edge included), so no lane
+// is masked off before the stores.
+__global__ __launch_bounds__(PX_THREADS) void k_filter_visibility(const u32 *__restrict__ mask, const float *__restrict__ orays,
+								   const int *__restrict__ oactive, u32 S, u32 low_bits, int R,
+								   float normal_cos, float plane_tol, int W, int row0, int row1,
+								   u32 *__restrict__ vis)
+{
+	const int LW = FV_TW + 2 * R, LH = FV_TH + 2 * R;
+	const int plane = (LW * LH + 3) & ~3;
+	u32 *s_word = s_fv;
+	float *s_o0 = (float *)(s_fv + plane), *s_o1 = (float *)(s_fv + 2 * plane), *s_o2 = (float *)(s_fv + 3 * plane);
+	float *s_n0 = (float *)(s_fv + 4 * plane), *s_n1 = (float *)(s_fv + 5 * plane), *s_n2 = (float *)(s_fv + 6 * plane);
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int x0 = (int)blockIdx.x * FV_TW, y0 = row0 + (int)blockIdx.y * FV_TH;
+	// staging: a wave per row (LW <= 48 lanes of it)
+	for (int ly = wave; ly < LH; ly += PX_THREADS / 64) {
+		const int lx = lane, gx = x0 - R + lx, gy = y0 - R + ly;
+		if (lx < LW) {
+			u32 word = 0u;
+			float v[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
+			if (gx >= 0 && gx < W && gy >= row0 && gy < row1) {
+				const size_t q = (size_t)gy * (size_t)W + (size_t)gx;
+				if (oactive[q] != 0) {
+					word = (S - (u32)__popc(mask[q] & low_bits)) | FV_ACTIVE;
+#pragma unroll
+					for (int k = 0; k < 6; k++)
+						v[k] = orays[q * 6 + k];
+				}
+			}
+			const int at = ly * LW + lx;
+			s_word[at] = word;
+			s_o0[at] = v[0];
+			s_o1[at] = v[1];
+			s_o2[at] = v[2];
+			s_n0[at] = v[3];
+			s_n1[at] = v[4];
+			s_n2[at] = v[5];
+		}
+	}
+	__syncthreads();
+	const int tx = tid & (FV_TW - 1);
+	for (int ty = tid / FV_TW; ty < FV_TH; ty += PX_THREADS / FV_TW) {
+		const int c = (ty + R) * LW + tx + R;
+		const u32 wp = s_word[c];
+		const float op0 = s_o0[c], op1 = s_o1[c], op2 = s_o2[c], np0 = s_n0[c], np1 = s_n1[c], np2 = s_n2[c];
+		u32 num = 0u, den = 0u;
+		for (int dy = -R; dy <= R; dy++) {
+			const u32 wy = (u32)(R + 1 - (dy < 0 ? -dy : dy));
+			for (int dx = -R; dx <= R; dx++) {
+				const int at = c + dy * LW + dx;
+				const u32 wq = s_word[at];
+				const float d0 = s_o0[at] - op0, d1 = s_o1[at] - op1, d2 = s_o2[at] - op2;
+				const float cosine = (np0 * s_n0[at] + np1 * s_n1[at]) + np2 * s_n2[at];
+				const float dist = (d0 * np0 + d1 * np1) + d2 * np2;
+				const bool same = (dx == 0 && dy == 0) || (cosine >= normal_cos && __builtin_fabsf(dist) <= plane_tol);
+				if ((wq & FV_ACTIVE) != 0u && same) {
+					const u32 w = wy * (u32)(R + 1 - (dx < 0 ? -dx : dx));
+					num += w * (wq & ~FV_ACTIVE);
+					den += w;
+				}
+			}
+		}
+		const int px = x0 + tx, py = y0 + ty;
+		if (px < W && py < row1) {
+			const size_t p = (size_t)py * (size_t)W + (size_t)px;
+			const bool act = (wp & FV_ACTIVE) != 0u;
+			vis[2 * p] = act ? num : 0u;
+			vis[2 * p + 1] = act ? den : 0u;
+		}
+	}
+}
+
+extern "C" int ugrt_filter_visibility(ugrt_ctx *ctx, const unsigned *d_mask, int num_bits, const float *d_orays,
+				      const int *d_oactive, int radius, float normal_cos, float plane_tol, unsigned *d_vis)
+{
+	if (!ctx || !d_mask || !d_orays || !d_oactive || !d_vis)
+		return ugrt_fail(UGRT_EINVAL, "filter_visibility: null argument");
+	if (num_bits < 1 || num_bits > 32)
+		return ugrt_fail(UGRT_EINVAL, "filter_visibility: num_bits %d is not in 1..32", num_bits);
+	if (radius < 0 || radius > UGRT_MAX_FILTER_RADIUS)
+		return ugrt_fail(UGRT_EINVAL, "filter_visibility: radius %d is not in 0..%d", radius, UGRT_MAX_FILTER_RADIUS);
+	if (!(plane_tol >= 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "filter_visibility: plane_tol must be 0 or greater");
+	UGRT_HIP(hipSetDevice(ctx->device));
+	const int W = ctx->cfg.width, row0 = ctx->p0 / W, rows = ctx->npix / W;
+	if (rows < 1)
+		return UGRT_OK;
+	const u32 low_bits = num_bits == 32 ? 0xFFFFFFFFu : (1u << num_bits) - 1u;
+	const int LW = FV_TW + 2 * radius, LH = FV_TH + 2 * radius;
+	const size_t lds = (size_t)7 * (size_t)((LW * LH + 3) & ~3) * sizeof(u32); // 31.5 KB at radius 8 with FV_TH 8
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_filter_visibility, dim3((W + FV_TW - 1) / FV_TW, (rows + FV_TH - 1) / FV_TH), dim3(PX_THREADS), lds,
+			   ctx->stream, d_mask, d_orays, d_oactive, (u32)num_bits, low_bits, radius, normal_cos, plane_tol, W, row0,
+			   row0 + rows, d_vis);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
+// the pass in the place of k_shade_area: num / den is the gathered share of open samples
+__global__ __launch_bounds__(PX_THREADS) void k_shade_area_vis(unsigned char *__restrict__ d_img, const u32 *__restrict__ vis,
+								u32 num_samples, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t pixelID = (size_t)(p0 + i);
+	const u32 num = vis[2 * pixelID], den = vis[2 * pixelID + 1];
+	if (den != 0u) {
+		const u32 a = num_samples * den + 2u * num, b = 3u * num_samples * den;
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			d_img[pixelID * 3 + k] = (unsigned char)(((u32)d_img[pixelID * 3 + k] * a) / b);
+	}
+}
+
+extern "C" int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_samples)
+{
+	if (!ctx || !d_img || !d_vis)
+		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: null argument");
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AREA_SAMPLES);
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
+	hipLaunchKernelGGL(k_shade_area_vis, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
+			   d_img, d_vis, (u32)num_samples, ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, UGRT_ST_SHADE);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}

@@ -403,6 +403,36 @@ class Context:
         """Each byte b of a pixel becomes (b * (S + 2 * lit)) // (3 * S), lit = S - popcount(mask & low S bits)."""
         check(lib.ugrt_shade_area(self._h, _ptr(img), _ptr(mask), int(num_samples)))
 
+    # -- interleaved sample sets and the gather (DESIGN.md section 6.8) ----------
+    def trace_dda_any_area_sets(self, value, span, offset, verts, faces, orays, oactive, num_samples, set_w, set_h,
+                                sample_pos, mask):
+        """trace_dda_any_area with a sample set per pixel of a set_w x set_h tile: pixel (x, y) of the full image aims at
+        set (y % set_h) * set_w + x % set_w of sample_pos, a DEVICE tensor of floats [set_w * set_h, num_samples, 3]
+        (scenes.area_sample_sets, uploaded)."""
+        check(lib.ugrt_trace_dda_any_area_sets(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                               _ptr(orays), _ptr(oactive), int(num_samples), int(set_w), int(set_h),
+                                               _ptr(sample_pos), _ptr(mask)))
+
+    def trace_dda_any_area_sets_thru(self, value, span, offset, verts, faces, orays, oactive, num_samples, set_w, set_h,
+                                     sample_pos, mask, mat_idx, transmit, num_materials):
+        """trace_dda_any_area_sets in which a triangle whose material has transmit > 0 does not occlude."""
+        check(lib.ugrt_trace_dda_any_area_sets_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts),
+                                                    _ptr(faces), _ptr(orays), _ptr(oactive), int(num_samples), int(set_w),
+                                                    int(set_h), _ptr(sample_pos), _ptr(mask), _ptr(mat_idx),
+                                                    _ptr(transmit), num_materials))
+
+    def filter_visibility(self, mask, num_bits, orays, oactive, radius, normal_cos, plane_tol, vis):
+        """The edge-aware gather: vis[2p] = sum of w * open_q and vis[2p + 1] = sum of w over the active pixels q within
+        `radius` of p (inside the image and the band) whose normal and plane agree with p's (orays / oactive: what ao_rays
+        wrote), w = (R + 1 - |dx|) * (R + 1 - |dy|), open_q = num_bits - popcount(mask[q] & low num_bits bits); vis:
+        uint32 words [2 * W * H] (an int32 tensor serves)."""
+        check(lib.ugrt_filter_visibility(self._h, _ptr(mask), int(num_bits), _ptr(orays), _ptr(oactive), int(radius),
+                                         normal_cos, plane_tol, _ptr(vis)))
+
+    def shade_area_vis(self, img, vis, num_samples):
+        """Each byte b of a pixel with den = vis[2p + 1] != 0 becomes (b * (S * den + 2 * vis[2p])) // (3 * S * den)."""
+        check(lib.ugrt_shade_area_vis(self._h, _ptr(img), _ptr(vis), int(num_samples)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

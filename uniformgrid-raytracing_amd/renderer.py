@@ -25,7 +25,9 @@ pass that scales the image by the share of open rays.  W
 through a hit whose material transmits instead of being mirrored, and the reflected hits' shadow walk sees through such
 materials.  With ``area=S`` the one-stream single-light frame casts soft shadows: S shadow rays
 per primary hit towards a disk around the light through the uniform grid in the place of the light-space shadow stage,
-and a last pass that darkens the image by the share of occluded samples.
+and a last pass that darkens the image by the share of occluded samples; with ``area_sets``
+the pixels of a tile aim at different sets of S points, and with ``area_filter`` a gather over the pixels of the same
+surface averages their shares before that pass.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -35,7 +37,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -156,6 +158,42 @@ def check_area(area, area_radius, shadows=True, lights=None, two_streams=False):
         raise ValueError("area needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on "
                          "a side context")
     return int(area), float(np.float32(area_radius))
+
+
+AREA_SET_TILES = {1: (1, 1), 4: (2, 2), 16: (4, 4)}  # area_sets -> (set_w, set_h)
+
+
+def default_filter_plane(bbmin, bbmax):
+    """area_filter_plane=None: 1 % of the scene's largest extent, as a float32."""
+    return float(np.float32(0.01 * float((np.asarray(bbmax, np.float32) - np.asarray(bbmin, np.float32)).max())))
+
+
+def check_area_filter(area, area_sets=1, area_filter=0, area_filter_cos=0.9, area_filter_plane=None):
+    """The interleaved sample sets and the gather of an area light, checked in check_area's
+    manner behind it (area: what check_area returned).  area_sets: 1, 4 or 16 (tiles of 1 x 1, 2 x 2, 4 x 4 pixels);
+    area_filter: an integer radius 0..MAX_FILTER_RADIUS (0: no gather); a value of either that is not its default needs
+    area > 0.  area_filter_cos: a number (no NaN); area_filter_plane: None (default_filter_plane) or a number >= 0; the
+    two are looked at with area_filter > 0 only.  ValueError before anything is enqueued.  Returns
+    (area_sets, area_filter, cos or None, plane or None)."""
+    if isinstance(area_sets, (bool, np.bool_)) or not isinstance(area_sets, (int, np.integer)) or int(area_sets) not in AREA_SET_TILES:
+        raise ValueError("area_sets must be 1, 4 or 16, not %r" % (area_sets,))
+    if isinstance(area_filter, (bool, np.bool_)) or not isinstance(area_filter, (int, np.integer)) \
+            or not 0 <= area_filter <= MAX_FILTER_RADIUS:
+        raise ValueError("area_filter must be an integer in 0..%d, not %r" % (MAX_FILTER_RADIUS, area_filter))
+    if not area and (area_sets != 1 or area_filter != 0):
+        raise ValueError("area_sets and area_filter need area > 0: they shape the area light's samples and penumbra")
+    if not area_filter:
+        return int(area_sets), 0, None, None
+    number = (int, float, np.integer, np.floating)
+    if isinstance(area_filter_cos, (bool, np.bool_)) or not isinstance(area_filter_cos, number) \
+            or np.isnan(np.float32(area_filter_cos)):
+        raise ValueError("area_filter_cos must be a number, not %r" % (area_filter_cos,))
+    if area_filter_plane is not None:
+        if isinstance(area_filter_plane, (bool, np.bool_)) or not isinstance(area_filter_plane, number) \
+                or not float(np.float32(area_filter_plane)) >= 0.0:
+            raise ValueError("area_filter_plane must be None or a number not below 0, not %r" % (area_filter_plane,))
+        area_filter_plane = float(np.float32(area_filter_plane))
+    return int(area_sets), int(area_filter), float(np.float32(area_filter_cos)), area_filter_plane
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -314,14 +352,20 @@ def ao_pass(c, f, cam_pos, dirs, radius):
     c.trace_dda_any_hemi(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, dirs, radius, f.ao_mask)
 
 
-def area_pass(c, f, cam_pos, samples, thru=None):
+def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
     """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
-    f.area_mask.  thru (a refract frame: (mat_idx, transmit, num_materials)): the walk that sees through glass.  Runs
-    behind the uniform grid's build and before the shading call that rewrites the ids."""
+    f.area_mask.  thru (a refract frame: (mat_idx, transmit, num_materials)): the walk that sees through glass.  sets
+    ((num_samples, set_w, set_h)): `samples` is the device table of a set per pixel of the tile,
+    and the walk is the one over sample sets.  Runs behind the uniform grid's build and before the shading call that
+    rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
-    if thru is None:
+    if sets is not None:
+        walk = c.trace_dda_any_area_sets if thru is None else c.trace_dda_any_area_sets_thru
+        walk(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, sets[0], sets[1], sets[2], samples,
+             f.area_mask, *(thru or ()))
+    elif thru is None:
         c.trace_dda_any_area(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples, f.area_mask)
     else:
         c.trace_dda_any_area_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples,
@@ -426,6 +470,9 @@ class _Frame:
         self._ao_dirs = {}
         # area: the mask of occluded samples of the light's disk (_ensure_area_buffers; the origins share ao_rays)
         self.area_mask = None
+        # area_filter: the gather's two sums per pixel (_ensure_area_filter_buffers); area_sets: the uploaded tables
+        self.area_vis = None
+        self._area_set_tables = {}
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -453,6 +500,11 @@ class _Frame:
             self.ao_active = t.empty(N, dtype=t.int32, device=dev)
         if self.area_mask is None:
             self.area_mask = t.zeros(N, dtype=t.int32, device=dev)
+
+    def _ensure_area_filter_buffers(self):
+        """area_vis [2 W*H] (uint32 words in an int32 tensor), allocated on first use."""
+        if self.area_vis is None:
+            self.area_vis = self.torch.zeros(2 * self.N, dtype=self.torch.int32, device=self.image.device)
 
     def _ensure_light_buffers(self, num_lights):
         """shadowed_lights [L, W*H]: light l's is_shadowed, allocated once for the most lights asked for."""
@@ -635,7 +687,8 @@ class Renderer(_Frame, _Band):
             self._worker = None
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
-                reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None):
+                reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1,
+                area_filter=0, area_filter_cos=0.9, area_filter_plane=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -657,8 +710,15 @@ class Renderer(_Frame, _Band):
         area_radius around the light camera's eye, perpendicular to its view; area = 1..32 shadow rays per primary hit
         towards scenes.area_samples' points of it walk the uniform grid in the place of the light-space shadow stage
         (is_shadowed is left alone), area_mask holds the occluded samples' bits and the image goes from b (every sample
-        lit) to b / 3 (none); with refract the walk sees through glass."""
+        lit) to b / 3 (none); with refract the walk sees through glass.
+        area_sets (needs area > 0; 1, 4 or 16): the pixels of a 1 x 1, 2 x 2 or 4 x 4 tile aim at different sets of `area`
+        points (scenes.area_sample_sets; the table is uploaded once per (area, area_sets, area_radius, light)).
+        area_filter (needs area > 0; 0: off): a gather of radius 1..8 over the pixels of the same surface -- normals within
+        area_filter_cos, planes within area_filter_plane (None: 1 % of the scene's largest extent) -- averages the masks
+        before the penumbra is shaded; area_vis holds its sums."""
         area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
+        area_sets, area_filter, area_filter_cos, area_filter_plane = check_area_filter(area, area_sets, area_filter,
+                                                                                       area_filter_cos, area_filter_plane)
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
@@ -696,12 +756,22 @@ class Renderer(_Frame, _Band):
         elif ao or area:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         if area:
-            area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup),
-                      (self.d_matidx, self.d_transmit, self.num_materials) if self.refract else None)
+            thru = (self.d_matidx, self.d_transmit, self.num_materials) if self.refract else None
+            if area_sets > 1:
+                area_pass(ctx, self, self.cam_pos, self._area_sets_stage(area, area_sets, area_radius, setup), thru,
+                          (area,) + AREA_SET_TILES[area_sets])
+            else:
+                area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru)
         if ao:
             ao_pass(ctx, self, self.cam_pos, *ao)
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
-        if area:
+        if area and area_filter:
+            self._ensure_area_filter_buffers()
+            plane = default_filter_plane(self.bbmin, self.bbmax) if area_filter_plane is None else area_filter_plane
+            ctx.filter_visibility(self.area_mask, area, self.ao_rays, self.ao_active, area_filter, area_filter_cos, plane,
+                                  self.area_vis)
+            ctx.shade_area_vis(self.image, self.area_vis, area)
+        elif area:
             ctx.shade_area(self.image, self.area_mask, area)
         if ao:
             ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
@@ -719,6 +789,22 @@ class Renderer(_Frame, _Band):
         self._ensure_area_buffers()
         eye = np.asarray(setup.light_camera["eye"], np.float64)
         return area_samples(area, eye, np.asarray(setup.light_camera["look"], np.float64) - eye, area_radius)
+
+    def _area_sets_stage(self, area, area_sets, area_radius, setup):
+        """The device table of sample sets for area_pass, with the buffers in place: scenes.area_sample_sets of
+        _area_stage's disk, uploaded once per (area, area_sets, area_radius, light) and kept."""
+        from .scenes import area_sample_sets
+
+        self._ensure_area_buffers()
+        eye, look = tuple(map(float, setup.light_camera["eye"])), tuple(map(float, setup.light_camera["look"]))
+        key = (area, area_sets, area_radius, eye, look)
+        if key not in self._area_set_tables:
+            table = area_sample_sets(area, area_sets, np.float64(eye), np.float64(look) - np.float64(eye), area_radius)
+            self._area_set_tables[key] = self._upload_area_sets(table)
+        return self._area_set_tables[key]
+
+    def _upload_area_sets(self, table):
+        return self.ctx.upload(table.reshape(-1))
 
     def _display_lights(self, setup, lights, shadows, shade, ao=None):
         """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
@@ -967,8 +1053,10 @@ class BandedRenderer(_Frame):
         return [self.aux] + [b.ctx for b in self._per_band]
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
-                ao_radius=None, refract=False, area=0, area_radius=None):
+                ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
+                area_filter_plane=None):
         check_area(area, area_radius, shadows, getattr(setup, "lights", None), True)  # raises with area > 0, as ao does
+        check_area_filter(0, area_sets, area_filter, area_filter_cos, area_filter_plane)  # raises unless at the defaults
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)

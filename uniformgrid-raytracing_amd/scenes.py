@@ -421,12 +421,11 @@ def ao_directions(S):
     return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r)], 1).astype(np.float32)
 
 
-def area_samples(S, centre, axis, radius):
-    """The S points of an area light's disk (DESIGN.md section 6.7): radius `radius` around `centre`, perpendicular to
-    `axis`.  With a = axis / |axis|, k the index of the smallest |a[k]| (ties go to the lowest k), T = normalize(a x e_k)
-    and B = a x T: r = radius * sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), point
-    centre + r cos phi * T + r sin phi * B.  Computed in float64 and returned as float32 [S, 3]: the library only ever
-    sees these floats as data."""
+AREA_SET_RANK = {1: (0,), 4: (0, 2, 3, 1), 16: (0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5)}  # 4 x 4: Bayer
+
+
+def _disk_points(S, centre, axis, radius, turn):
+    """area_samples' points with `turn` added to every angle."""
     c = np.asarray(centre, np.float64).reshape(3)
     a = np.asarray(axis, np.float64).reshape(3)
     a = a / np.sqrt((a * a).sum())
@@ -438,5 +437,25 @@ def area_samples(S, centre, axis, radius):
     B = np.cross(a, T)
     s = np.arange(int(S), dtype=np.float64)
     r = float(radius) * np.sqrt((s + 0.5) / float(S))
-    phi = s * (np.pi * (3.0 - np.sqrt(5.0)))
+    phi = s * (np.pi * (3.0 - np.sqrt(5.0))) + turn
     return (c + (r * np.cos(phi))[:, None] * T + (r * np.sin(phi))[:, None] * B).astype(np.float32)
+
+
+def area_sample_sets(S, sets, centre, axis, radius):
+    """The interleaved sample sets of an area light's disk: sets = 1, 4 or 16 for a tile of
+    1 x 1, 2 x 2 or 4 x 4 pixels; set k (row-major in the tile) is area_samples' formula with
+    phi = s * pi * (3 - sqrt(5)) + 2 pi * rank[k] / sets, rank = AREA_SET_RANK[sets]: neighbouring pixels' spirals are
+    turned against each other by as much as the tile allows.  Computed in float64 and returned as float32 [sets, S, 3];
+    set 0 is area_samples bit for bit."""
+    if sets not in AREA_SET_RANK:
+        raise ValueError("sets must be 1, 4 or 16, not %r" % (sets,))
+    return np.stack([_disk_points(S, centre, axis, radius, 2.0 * np.pi * rank / float(sets)) for rank in AREA_SET_RANK[sets]])
+
+
+def area_samples(S, centre, axis, radius):
+    """The S points of an area light's disk (DESIGN.md section 6.7): radius `radius` around `centre`, perpendicular to
+    `axis`.  With a = axis / |axis|, k the index of the smallest |a[k]| (ties go to the lowest k), T = normalize(a x e_k)
+    and B = a x T: r = radius * sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), point
+    centre + r cos phi * T + r sin phi * B.  Computed in float64 and returned as float32 [S, 3]: the library only ever
+    sees these floats as data."""
+    return _disk_points(S, centre, axis, radius, 0.0)  # (phi + 0.0 is phi: the floats are what they were)
