@@ -528,6 +528,97 @@ def test_synthetic_launch_shapes(ugrt, O, REFS, SYN, torch):
             ctx.set_option(key, bad)
 
 
+PROF_STAGES = ("worklist", "trace_dda", "reflect_gen")
+
+
+def _secondary_calls(ctx, torch, SYN, dv, df, grid, sentinel=-7):
+    """One call of each of the nine any-hit exports and of each of the six ray generators on the synthetic scene, as
+    (name, function) pairs; every call writes into buffers of its own.  3 lights, 4 hemisphere directions, 5 samples and
+    a 2 x 2 tile of sample sets: more than one layer to clear, and a sample table in LDS.  Returns the pairs and the
+    lights call's flags [3, N]."""
+    N, nf = 4096, len(SYN["faces"])
+    i32, f32 = torch.int32, torch.float32
+    rng = np.random.RandomState(11)
+    rays, act = ctx.upload(SYN["rays"]), ctx.upload(np.ones(N, np.int32))
+    mat_idx = torch.zeros(nf, dtype=i32, device=ctx.device)
+    reflect, transmit, ior = (ctx.upload(np.asarray([v], np.float32)) for v in (0.5, 0.5, 1.5))
+    lights = [(4.0, 4.0, 3.9), (1.5, 6.5, 3.9), (6.5, 1.5, 3.95)]  # above the wide triangles: they shadow what lies below
+    dirs = [(0.0, 0.0, 1.0), (0.6, 0.0, 0.8), (0.0, 0.6, 0.8), (-0.6, 0.0, 0.8)]
+    samples = rng.uniform([1, 1, 3.5], [7, 7, 3.9], (5, 3)).astype(np.float32)
+    sets = ctx.upload(rng.uniform([1, 1, 3.5], [7, 7, 3.9], (4, 5, 3)).astype(np.float32).reshape(-1))
+    flags = lambda n=N: torch.full((n,), sentinel, dtype=i32, device=ctx.device)
+    occ_lights = flags(3 * N)
+    g, thru = (grid[0], grid[1], grid[2], dv, df, rays, act), (mat_idx, transmit, 1)
+    any_hit = [
+        ("trace_dda_any", lambda o=flags(): ctx.trace_dda_any(*g, 1.0, o)),
+        ("trace_dda_any_thru", lambda o=flags(): ctx.trace_dda_any_thru(*g, 1.0, o, *thru)),
+        ("trace_dda_any_lights", lambda: ctx.trace_dda_any_lights(*g, lights, occ_lights)),
+        ("trace_dda_any_lights_thru", lambda o=flags(3 * N): ctx.trace_dda_any_lights_thru(*g, lights, o, *thru)),
+        ("trace_dda_any_hemi", lambda o=flags(): ctx.trace_dda_any_hemi(*g, dirs, 2.0, o)),
+        ("trace_dda_any_area", lambda o=flags(): ctx.trace_dda_any_area(*g, samples, o)),
+        ("trace_dda_any_area_thru", lambda o=flags(): ctx.trace_dda_any_area_thru(*g, samples, o, *thru)),
+        ("trace_dda_any_area_sets", lambda o=flags(): ctx.trace_dda_any_area_sets(*g, 5, 2, 2, sets, o)),
+        ("trace_dda_any_area_sets_thru", lambda o=flags(): ctx.trace_dda_any_area_sets_thru(*g, 5, 2, 2, sets, o, *thru)),
+    ]
+    # the generators' inputs: hits of random triangles (or none) at t = 1/2 along the synthetic rays, seen from a camera
+    cam = ctx.upload(np.asarray([4.0, 4.0, -2.0], np.float32))
+    ids = ctx.upload(rng.randint(-1, nf, N).astype(np.int32))
+    t = torch.full((N,), 0.5, dtype=f32, device=ctx.device)
+    pdir = ctx.upload(np.ascontiguousarray(SYN["rays"].reshape(N, 6)[:, 3:]).reshape(-1))
+    out = lambda: (torch.empty(6 * N, dtype=f32, device=ctx.device), torch.empty(N, dtype=i32, device=ctx.device))
+    generators = [
+        ("reflect_rays", lambda o=out(): ctx.reflect_rays(cam, t, pdir, ids, mat_idx, reflect, 1, dv, df, 1e-3, *o)),
+        ("reflect_rays_next", lambda o=out(): ctx.reflect_rays_next(rays, act, t, ids, mat_idx, reflect, 1, dv, df, 1e-3, *o)),
+        ("refract_rays", lambda o=out(): ctx.refract_rays(cam, t, pdir, ids, mat_idx, reflect, transmit, ior, 1, dv, df, 1e-3, *o)),
+        ("refract_rays_next", lambda o=out(): ctx.refract_rays_next(rays, act, t, ids, mat_idx, reflect, transmit, ior, 1, dv, df,
+                                                                   1e-3, *o)),
+        ("occlusion_rays", lambda o=out(): ctx.occlusion_rays(rays, act, t, ids, dv, df, lights[0], 1e-3, *o)),
+        ("ao_rays", lambda o=out(): ctx.ao_rays(cam, t, pdir, ids, dv, df, 1e-3, *o)),
+    ]
+    return any_hit, generators, occ_lights
+
+
+@pytest.mark.gpu
+def test_secondary_calls_open_their_profiler_brackets_once(ugrt, SYN, torch):
+    """The stage profiler's launch counts around the any-hit walk's host path and the generators' launcher: each of the
+    nine any-hit exports adds one `worklist` and one `trace_dda` launch and no `reflect_gen`, each of the six generators
+    one `reflect_gen` and nothing else, and with profiling off none of them adds anything.  The lights call of a band
+    context (its layers are not contiguous: one clear per layer) gives the full frame's flags on its rows and leaves the
+    other rows alone."""
+    N = 4096
+    ctx, dv, df, grid = _syn_context(ugrt, SYN)
+    any_hit, generators, occ_lights = _secondary_calls(ctx, torch, SYN, dv, df, grid)
+    counts = lambda: {k: v[1] for k, v in ctx.prof_get().items() if k in PROF_STAGES}
+    ctx.prof_enable(True, stages=PROF_STAGES)
+    ctx.prof_reset()
+    assert counts() == dict.fromkeys(PROF_STAGES, 0)
+    for calls, adds in ((any_hit, {"worklist": 1, "trace_dda": 1, "reflect_gen": 0}),
+                        (generators, {"worklist": 0, "trace_dda": 0, "reflect_gen": 1})):
+        for name, call in calls:
+            before = counts()
+            call()
+            assert counts() == {k: before[k] + adds[k] for k in PROF_STAGES}, name
+    assert counts() == {"worklist": 9, "trace_dda": 9, "reflect_gen": 6}
+    ctx.prof_enable(False)
+    before = ctx.prof_get()
+    for name, call in any_hit + generators:
+        call()
+    assert ctx.prof_get() == before
+    # the band: rows 2..4 of 8
+    full = occ_lights.cpu().numpy().reshape(3, N)
+    assert set(np.unique(full)) == {0, 1} and all(0 < int(full[l].sum()) < N for l in range(3))
+    band, bv, bf, bgrid = _syn_context(ugrt, SYN, rows=(2, 5))
+    p0, n = band.p0, band.npix
+    assert (p0, n) == (1024, 1536)
+    band.prof_enable(True, stages=PROF_STAGES)
+    band_any, _, band_lights = _secondary_calls(band, torch, SYN, bv, bf, bgrid)
+    dict(band_any)["trace_dda_any_lights"]()
+    assert {k: v[1] for k, v in band.prof_get().items() if k in PROF_STAGES} == {"worklist": 1, "trace_dda": 1, "reflect_gen": 0}
+    got = band_lights.cpu().numpy().reshape(3, N)
+    np.testing.assert_array_equal(got[:, p0:p0 + n], full[:, p0:p0 + n])
+    assert (got[:, :p0] == -7).all() and (got[:, p0 + n:] == -7).all()
+
+
 @pytest.mark.gpu
 def test_launch_options_do_not_change_the_frame(ugrt, O, REFS, torch):
     """The new options, and dda_kernel 0/1 x dda_split 0/1/4 for the levels around the occlusion launches: two frames

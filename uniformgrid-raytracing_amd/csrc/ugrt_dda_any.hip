@@ -368,59 +368,185 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 	}
 }
 
-// both exports: thru null = ugrt_trace_dda_any
-static int trace_dda_any(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
-			 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_rays,
-			 const int *d_active, float t_max, int *d_occluded, const ThruArg *thru)
+// ---------------------------------------------------------------------------
+// the host side: one path for every aim.  An export checks its arguments, fills its Aim::Arg and calls any_walk<Aim>.
+// ---------------------------------------------------------------------------
+// what every export is given; out: the flags, or the mask words; thru null: the plain kernel
+struct AnyCall {
+	ugrt_ctx *ctx;
+	const char *who;
+	const unsigned *value_list, *span, *offset;
+	const float *verts;
+	const int *tris;
+	const float *rays;
+	const int *active;
+	int *out;
+	const ThruArg *thru;
+};
+
+// own: the export's own pointer argument (the lights, the directions, the samples), where it has one
+static int any_null_check(const AnyCall &c, const void *own = "")
 {
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_occluded ||
-	    (thru && (!thru->mat_idx || !thru->transmit)))
-		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
-	if (!(t_max > 0.0f))
-		return ugrt_fail(UGRT_EINVAL, "%s: t_max must be greater than 0", who);
+	if (!c.ctx || !c.value_list || !c.span || !c.offset || !c.verts || !c.tris || !c.rays || !c.active || !own || !c.out ||
+	    (c.thru && (!c.thru->mat_idx || !c.thru->transmit)))
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", c.who);
+	return UGRT_OK;
+}
+
+// The prepare launch and the kernel for one aim.  What differs between the aims is read from the aim's flags:
+//   * the layers of the index space: AnyLights and AnyHemi walk (light or direction, ray group), aim.count layers;
+//   * the group: "any_rays_per_wave" rays (unset: 32); the area aims give L = "any_rays_per_wave" of a wave's lanes
+//     (at most and unset: all 64) rays, PPW = max(1, L / S) pixels' S samples each, and the kernel's RPW carries PPW;
+//   * dynamic LDS: AnyAreaSets' table, rounded up to the 16 bytes of the copy's float4 stores (at most 6 KB);
+//   * AnyLights' layers behind the first are cleared here; AnyHemi has no see-through kernel.
+template <class Aim> static int any_walk(const AnyCall &c, const typename Aim::Arg &aim)
+{
+	ugrt_ctx *ctx = c.ctx;
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
 	UGRT_HIP(hipSetDevice(ctx->device));
 	const DGrid g = ugrt_dgrid_of(G);
-	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
+	const float4 *rec = ugrt_trirec_of(ctx, c.verts, c.tris);
 	// launch shape (ugrt_ctx_set_option; no effect on results)
-	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
+	u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u, layers = 1u;
 	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	// the prepare launch in the form that writes no hit defaults (it clears the band's occlusion flags instead), always with
-	// the bitmap workgroups, never with the split walks' chunk table
+	size_t lds = 0;
+	if constexpr (Aim::area) {
+		const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
+		RPW = L / (u32)aim.count > 0u ? L / (u32)aim.count : 1u;
+	}
+	if constexpr (Aim::lights || Aim::hemi)
+		layers = (u32)aim.count;
+	if constexpr (Aim::sets)
+		lds = ((size_t)12 * (size_t)(aim.set_w * aim.set_h * (u32)aim.count) + 15u) & ~(size_t)15u;
+	// ONE prepare launch and one ray list for all layers, in the form that writes no hit defaults (it clears the band's
+	// flags or mask words instead: of AnyLights, layer 0), always with the bitmap workgroups, never with the split walks'
+	// chunk table.  AnyLights' layers behind are cleared here in stream order: one fill where the band is the frame (the
+	// layers are contiguous), one per layer otherwise.
 	u32 *list, *dcount;
+	hipError_t he = hipSuccess;
 	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const int rc = ugrt_dda_prepare(ctx, g, d_active, nullptr, d_occluded, d_span, true, nullptr, &list, &dcount);
+	const int rc = ugrt_dda_prepare(ctx, g, c.active, nullptr, c.out, c.span, true, nullptr, &list, &dcount);
+	if constexpr (Aim::lights) {
+		const size_t level = aim.level;
+		if (!rc && aim.count > 1) {
+			if ((size_t)ctx->npix == level)
+				he = hipMemsetAsync(c.out + level, 0, (size_t)(aim.count - 1) * level * sizeof(int), ctx->stream);
+			else
+				for (int l = 1; l < aim.count && he == hipSuccess; l++)
+					he = hipMemsetAsync(c.out + (size_t)l * level + (size_t)ctx->p0, 0, (size_t)ctx->npix * sizeof(int),
+							    ctx->stream);
+		}
+	}
 	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
 	if (rc)
 		return rc;
-	// persistent single-wave workgroups; "dda_blocks" caps them as it caps ugrt_trace_dda's
-	int blocks = launch_blocks_for((u32)ctx->npix / RPW + 1u);
+	UGRT_HIP(he);
+	// persistent single-wave workgroups over (layer, group); "dda_blocks" caps them as it caps ugrt_trace_dda's
+	int blocks = launch_blocks_for(((u32)ctx->npix / RPW + 1u) * layers);
 	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
 		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
+	auto launch = [&](const auto &thru) {
+		constexpr bool THRU = std::is_same_v<std::decay_t<decltype(thru)>, ThruArg>;
+		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, Aim, THRU> : k_trace_dda_any<false, Aim, THRU>), dim3(blocks), dim3(64),
+				   lds, ctx->stream, g, c.value_list, c.span, c.offset, (const u32 *)ctx->ubitmap.p, c.verts, c.tris, rec,
+				   c.rays, (const u32 *)list, (const u32 *)dcount, aim, c.out, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET,
+				   thru);
+	};
 	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	if (thru)
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays, true> : k_trace_dda_any<false, AnyRays, true>), dim3(blocks),
-				   dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist,
-				   d_trilist, rec, d_rays, (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
+	if constexpr (Aim::hemi)
+		launch(NoThru());
+	else if (c.thru)
+		launch(*c.thru);
 	else
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyRays> : k_trace_dda_any<false, AnyRays>), dim3(blocks), dim3(64), 0,
-				   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
-				   d_rays, (const u32 *)list, (const u32 *)dcount, t_max, d_occluded, RPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
+		launch(NoThru());
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
+}
+
+static int trace_dda_any(const AnyCall &c, float t_max)
+{
+	if (int rc = any_null_check(c))
+		return rc;
+	if (!(t_max > 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "%s: t_max must be greater than 0", c.who);
+	return any_walk<AnyRays>(c, t_max);
+}
+
+static int trace_dda_any_lights(const AnyCall &c, int num_lights, const float *light_pos)
+{
+	if (int rc = any_null_check(c, light_pos))
+		return rc;
+	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_lights %d is not in 1..%d", c.who, num_lights, UGRT_MAX_LIGHTS);
+	AnyLights::Arg lights = {};
+	for (int k = 0; k < 3 * num_lights; k++)
+		lights.pos[k] = light_pos[k];
+	lights.count = num_lights;
+	lights.level = (size_t)c.ctx->cfg.width * (size_t)c.ctx->cfg.height;
+	return any_walk<AnyLights>(c, lights);
+}
+
+static int trace_dda_any_hemi(const AnyCall &c, int num_dirs, const float *dirs, float radius)
+{
+	if (int rc = any_null_check(c, dirs))
+		return rc;
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_dirs %d is not in 1..%d", c.who, num_dirs, UGRT_MAX_AO_DIRS);
+	if (!(radius > 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "%s: radius must be greater than 0", c.who);
+	AnyHemi::Arg hemi = {};
+	for (int k = 0; k < 3 * num_dirs; k++)
+		hemi.dirs[k] = dirs[k];
+	hemi.count = num_dirs;
+	hemi.radius = radius;
+	return any_walk<AnyHemi>(c, hemi);
+}
+
+static int trace_dda_any_area(const AnyCall &c, int num_samples, const float *sample_pos)
+{
+	if (int rc = any_null_check(c, sample_pos))
+		return rc;
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", c.who, num_samples, UGRT_MAX_AREA_SAMPLES);
+	AnyArea::Arg area = {};
+	for (int k = 0; k < 3 * num_samples; k++)
+		area.pos[k] = sample_pos[k];
+	area.count = num_samples;
+	return any_walk<AnyArea>(c, area);
+}
+
+static int trace_dda_any_area_sets(const AnyCall &c, int num_samples, int set_w, int set_h, const float *d_sample_pos)
+{
+	if (int rc = any_null_check(c, d_sample_pos))
+		return rc;
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", c.who, num_samples, UGRT_MAX_AREA_SAMPLES);
+	if (set_w < 1 || set_w > UGRT_MAX_AREA_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w %d is not in 1..%d", c.who, set_w, UGRT_MAX_AREA_SET_TILE);
+	if (set_h < 1 || set_h > UGRT_MAX_AREA_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_h %d is not in 1..%d", c.who, set_h, UGRT_MAX_AREA_SET_TILE);
+	if (set_w * set_h * num_samples > UGRT_MAX_AREA_SET_POINTS)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w * set_h * num_samples = %d is more than %d", c.who,
+				 set_w * set_h * num_samples, UGRT_MAX_AREA_SET_POINTS);
+	AnyAreaSets::Arg area = {};
+	area.pos = d_sample_pos;
+	area.count = num_samples;
+	area.set_w = (u32)set_w;
+	area.set_h = (u32)set_h;
+	area.width = (u32)c.ctx->cfg.width;
+	return any_walk<AnyAreaSets>(c, area);
 }
 
 extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
 				  const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
 				  const float *d_rays, const int *d_active, float t_max, int *d_occluded)
 {
-	return trace_dda_any(ctx, "trace_dda_any", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active, t_max,
-			     d_occluded, nullptr);
+	return trace_dda_any({ ctx, "trace_dda_any", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active,
+			       d_occluded, nullptr },
+			     t_max);
 }
 
 extern "C" int ugrt_trace_dda_any_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -429,72 +555,9 @@ extern "C" int ugrt_trace_dda_any_thru(ugrt_ctx *ctx, const unsigned *d_value_li
 				       const int *d_mat_idx, const float *d_transmit, int num_materials)
 {
 	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
-	return trace_dda_any(ctx, "trace_dda_any_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active,
-			     t_max, d_occluded, &thru);
-}
-
-// both exports: thru null = ugrt_trace_dda_any_lights
-static int trace_dda_any_lights(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
-				const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
-				const int *d_oactive, int num_lights, const float *light_pos, int *d_occluded, const ThruArg *thru)
-{
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !light_pos ||
-	    !d_occluded || (thru && (!thru->mat_idx || !thru->transmit)))
-		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
-	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
-		return ugrt_fail(UGRT_EINVAL, "%s: num_lights %d is not in 1..%d", who, num_lights, UGRT_MAX_LIGHTS);
-	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
-	if (!G.valid)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const DGrid g = ugrt_dgrid_of(G);
-	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
-	AnyLights::Arg lights = {};
-	for (int k = 0; k < 3 * num_lights; k++)
-		lights.pos[k] = light_pos[k];
-	lights.count = num_lights;
-	lights.level = (size_t)ctx->cfg.width * (size_t)ctx->cfg.height;
-	// launch shape: ugrt_trace_dda_any's options
-	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
-	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	// ONE prepare launch and one ray list for all lights, taken as ugrt_trace_dda_any takes them (the turn of the ray
-	// counters, the ticket, the bitmap); it clears layer 0 of the band's flags, the layers behind are cleared here in
-	// stream order: one fill where the band is the frame (the layers are contiguous), one per layer otherwise
-	const size_t level = lights.level;
-	u32 *list, *dcount;
-	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, d_occluded, d_span, true, nullptr, &list, &dcount);
-	hipError_t he = hipSuccess;
-	if (!rc && num_lights > 1) {
-		if ((size_t)ctx->npix == level)
-			he = hipMemsetAsync(d_occluded + level, 0, (size_t)(num_lights - 1) * level * sizeof(int), ctx->stream);
-		else
-			for (int l = 1; l < num_lights && he == hipSuccess; l++)
-				he = hipMemsetAsync(d_occluded + (size_t)l * level + (size_t)ctx->p0, 0, (size_t)ctx->npix * sizeof(int),
-						    ctx->stream);
-	}
-	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
-	if (rc)
-		return rc;
-	UGRT_HIP(he);
-	// persistent single-wave workgroups over (light, group); "dda_blocks" caps them as it caps ugrt_trace_dda's
-	int blocks = launch_blocks_for(((u32)ctx->npix / RPW + 1u) * (u32)num_lights);
-	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
-		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
-	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	if (thru)
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights, true> : k_trace_dda_any<false, AnyLights, true>),
-				   dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p,
-				   d_vertlist, d_trilist, rec, d_orays, (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
-	else
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyLights> : k_trace_dda_any<false, AnyLights>), dim3(blocks), dim3(64),
-				   0, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
-				   d_orays, (const u32 *)list, (const u32 *)dcount, lights, d_occluded, RPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
-	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return trace_dda_any({ ctx, "trace_dda_any_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays,
+			       d_active, d_occluded, &thru },
+			     t_max);
 }
 
 extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -502,8 +565,9 @@ extern "C" int ugrt_trace_dda_any_lights(ugrt_ctx *ctx, const unsigned *d_value_
 					 const float *d_orays, const int *d_oactive, int num_lights, const float *light_pos,
 					 int *d_occluded)
 {
-	return trace_dda_any_lights(ctx, "trace_dda_any_lights", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
-				    d_oactive, num_lights, light_pos, d_occluded, nullptr);
+	return trace_dda_any_lights({ ctx, "trace_dda_any_lights", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				      d_orays, d_oactive, d_occluded, nullptr },
+				    num_lights, light_pos);
 }
 
 extern "C" int ugrt_trace_dda_any_lights_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -512,8 +576,9 @@ extern "C" int ugrt_trace_dda_any_lights_thru(ugrt_ctx *ctx, const unsigned *d_v
 					      int *d_occluded, const int *d_mat_idx, const float *d_transmit, int num_materials)
 {
 	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
-	return trace_dda_any_lights(ctx, "trace_dda_any_lights_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
-				    d_orays, d_oactive, num_lights, light_pos, d_occluded, &thru);
+	return trace_dda_any_lights({ ctx, "trace_dda_any_lights_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				      d_orays, d_oactive, d_occluded, &thru },
+				    num_lights, light_pos);
 }
 
 extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -521,140 +586,9 @@ extern "C" int ugrt_trace_dda_any_hemi(ugrt_ctx *ctx, const unsigned *d_value_li
 				       const float *d_orays, const int *d_oactive, int num_dirs, const float *dirs, float radius,
 				       unsigned *d_mask)
 {
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !dirs ||
-	    !d_mask)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: null argument");
-	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
-	if (!(radius > 0.0f))
-		return ugrt_fail(UGRT_EINVAL, "trace_dda_any_hemi: radius must be greater than 0");
-	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
-	if (!G.valid)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const DGrid g = ugrt_dgrid_of(G);
-	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
-	AnyHemi::Arg hemi = {};
-	for (int k = 0; k < 3 * num_dirs; k++)
-		hemi.dirs[k] = dirs[k];
-	hemi.count = num_dirs;
-	hemi.radius = radius;
-	// launch shape: ugrt_trace_dda_any's options
-	const u32 RPW = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 32u;
-	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	// ONE prepare launch and one ray list for all directions, taken as ugrt_trace_dda_any takes them (the turn of the ray
-	// counters, the ticket, the bitmap); it clears the band's mask words, which the walk then only ORs into
-	u32 *list, *dcount;
-	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, (int *)d_mask, d_span, true, nullptr, &list, &dcount);
-	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
-	if (rc)
-		return rc;
-	// persistent single-wave workgroups over (direction, group); "dda_blocks" caps them as it caps ugrt_trace_dda's
-	int blocks = launch_blocks_for(((u32)ctx->npix / RPW + 1u) * (u32)num_dirs);
-	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
-		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
-	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	hipLaunchKernelGGL((rec ? k_trace_dda_any<true, AnyHemi> : k_trace_dda_any<false, AnyHemi>), dim3(blocks), dim3(64), 0,
-			   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_orays,
-			   (const u32 *)list, (const u32 *)dcount, hemi, (int *)d_mask, RPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET,
-			   NoThru());
-	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
-}
-
-// the area walks: the prepare launch and the kernel over (pixel group, sample) for Aim = AnyArea or AnyAreaSets, with
-// `lds` bytes of dynamic LDS
-template <class Aim>
-static int area_walk(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
-		     const float *d_vertlist, const int *d_trilist, const float *d_orays, const int *d_oactive,
-		     const typename Aim::Arg &area, size_t lds, unsigned *d_mask, const ThruArg *thru)
-{
-	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
-	if (!G.valid)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const DGrid g = ugrt_dgrid_of(G);
-	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
-	// launch shape: of a wave's lanes L = "any_rays_per_wave" (unset: all 64) are given rays, PPW pixels' S samples each
-	const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
-	const u32 PPW = L / (u32)area.count > 0u ? L / (u32)area.count : 1u;
-	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	// ONE prepare launch and one ray list, taken as ugrt_trace_dda_any takes them (the turn of the ray counters, the
-	// ticket, the bitmap); it clears the band's mask words, and the walk stores the non-zero ones
-	u32 *list, *dcount;
-	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const int rc = ugrt_dda_prepare(ctx, g, d_oactive, nullptr, (int *)d_mask, d_span, true, nullptr, &list, &dcount);
-	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
-	if (rc)
-		return rc;
-	// persistent single-wave workgroups over the pixel groups; "dda_blocks" caps them as it caps ugrt_trace_dda's
-	int blocks = launch_blocks_for((u32)ctx->npix / PPW + 1u);
-	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
-		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
-	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	if (thru)
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, Aim, true> : k_trace_dda_any<false, Aim, true>), dim3(blocks), dim3(64),
-				   lds, ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist,
-				   rec, d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, *thru);
-	else
-		hipLaunchKernelGGL((rec ? k_trace_dda_any<true, Aim> : k_trace_dda_any<false, Aim>), dim3(blocks), dim3(64), lds,
-				   ctx->stream, g, d_value_list, d_span, d_offset, (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec,
-				   d_orays, (const u32 *)list, (const u32 *)dcount, area, (int *)d_mask, PPW, COOP,
-				   ctx->d_small + UGRT_DSMALL_TICKET, NoThru());
-	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
-}
-
-// both exports: thru null = ugrt_trace_dda_any_area
-static int trace_dda_any_area(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
-			      const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
-			      const int *d_oactive, int num_samples, const float *sample_pos, unsigned *d_mask, const ThruArg *thru)
-{
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !sample_pos ||
-	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
-		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
-	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
-		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
-	AnyArea::Arg area = {};
-	for (int k = 0; k < 3 * num_samples; k++)
-		area.pos[k] = sample_pos[k];
-	area.count = num_samples;
-	return area_walk<AnyArea>(ctx, d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays, d_oactive, area, 0, d_mask,
-				  thru);
-}
-
-// both exports: thru null = ugrt_trace_dda_any_area_sets
-static int trace_dda_any_area_sets(ugrt_ctx *ctx, const char *who, const unsigned *d_value_list, const unsigned *d_span,
-				   const unsigned *d_offset, const float *d_vertlist, const int *d_trilist, const float *d_orays,
-				   const int *d_oactive, int num_samples, int set_w, int set_h, const float *d_sample_pos,
-				   unsigned *d_mask, const ThruArg *thru)
-{
-	if (!ctx || !d_value_list || !d_span || !d_offset || !d_vertlist || !d_trilist || !d_orays || !d_oactive || !d_sample_pos ||
-	    !d_mask || (thru && (!thru->mat_idx || !thru->transmit)))
-		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
-	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
-		return ugrt_fail(UGRT_EINVAL, "%s: num_samples %d is not in 1..%d", who, num_samples, UGRT_MAX_AREA_SAMPLES);
-	if (set_w < 1 || set_w > UGRT_MAX_AREA_SET_TILE)
-		return ugrt_fail(UGRT_EINVAL, "%s: set_w %d is not in 1..%d", who, set_w, UGRT_MAX_AREA_SET_TILE);
-	if (set_h < 1 || set_h > UGRT_MAX_AREA_SET_TILE)
-		return ugrt_fail(UGRT_EINVAL, "%s: set_h %d is not in 1..%d", who, set_h, UGRT_MAX_AREA_SET_TILE);
-	if (set_w * set_h * num_samples > UGRT_MAX_AREA_SET_POINTS)
-		return ugrt_fail(UGRT_EINVAL, "%s: set_w * set_h * num_samples = %d is more than %d", who, set_w * set_h * num_samples,
-				 UGRT_MAX_AREA_SET_POINTS);
-	AnyAreaSets::Arg area = {};
-	area.pos = d_sample_pos;
-	area.count = num_samples;
-	area.set_w = (u32)set_w;
-	area.set_h = (u32)set_h;
-	area.width = (u32)ctx->cfg.width;
-	// the table's bytes, rounded up to the 16 of the copy's float4 stores (at most 6 KB)
-	const size_t lds = ((size_t)12 * (size_t)(set_w * set_h * num_samples) + 15u) & ~(size_t)15u;
-	return area_walk<AnyAreaSets>(ctx, d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays, d_oactive, area, lds,
-				      d_mask, thru);
+	return trace_dda_any_hemi({ ctx, "trace_dda_any_hemi", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
+				    d_oactive, (int *)d_mask, nullptr },
+				  num_dirs, dirs, radius);
 }
 
 extern "C" int ugrt_trace_dda_any_area(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -662,8 +596,9 @@ extern "C" int ugrt_trace_dda_any_area(ugrt_ctx *ctx, const unsigned *d_value_li
 				       const float *d_orays, const int *d_oactive, int num_samples, const float *sample_pos,
 				       unsigned *d_mask)
 {
-	return trace_dda_any_area(ctx, "trace_dda_any_area", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
-				  d_oactive, num_samples, sample_pos, d_mask, nullptr);
+	return trace_dda_any_area({ ctx, "trace_dda_any_area", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
+				    d_oactive, (int *)d_mask, nullptr },
+				  num_samples, sample_pos);
 }
 
 extern "C" int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -672,8 +607,9 @@ extern "C" int ugrt_trace_dda_any_area_thru(ugrt_ctx *ctx, const unsigned *d_val
 					    unsigned *d_mask, const int *d_mat_idx, const float *d_transmit, int num_materials)
 {
 	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
-	return trace_dda_any_area(ctx, "trace_dda_any_area_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_orays,
-				  d_oactive, num_samples, sample_pos, d_mask, &thru);
+	return trace_dda_any_area({ ctx, "trace_dda_any_area_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+				    d_orays, d_oactive, (int *)d_mask, &thru },
+				  num_samples, sample_pos);
 }
 
 extern "C" int ugrt_trace_dda_any_area_sets(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -681,8 +617,9 @@ extern "C" int ugrt_trace_dda_any_area_sets(ugrt_ctx *ctx, const unsigned *d_val
 					    const float *d_orays, const int *d_oactive, int num_samples, int set_w, int set_h,
 					    const float *d_sample_pos, unsigned *d_mask)
 {
-	return trace_dda_any_area_sets(ctx, "trace_dda_any_area_sets", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
-				       d_orays, d_oactive, num_samples, set_w, set_h, d_sample_pos, d_mask, nullptr);
+	return trace_dda_any_area_sets({ ctx, "trace_dda_any_area_sets", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+					 d_orays, d_oactive, (int *)d_mask, nullptr },
+				       num_samples, set_w, set_h, d_sample_pos);
 }
 
 extern "C" int ugrt_trace_dda_any_area_sets_thru(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
@@ -692,6 +629,8 @@ extern "C" int ugrt_trace_dda_any_area_sets_thru(ugrt_ctx *ctx, const unsigned *
 						 const float *d_transmit, int num_materials)
 {
 	const ThruArg thru = { d_mat_idx, d_transmit, num_materials };
-	return trace_dda_any_area_sets(ctx, "trace_dda_any_area_sets_thru", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
-				       d_orays, d_oactive, num_samples, set_w, set_h, d_sample_pos, d_mask, &thru);
+	return trace_dda_any_area_sets({ ctx, "trace_dda_any_area_sets_thru", d_value_list, d_span, d_offset, d_vertlist,
+					 d_trilist, d_orays, d_oactive, (int *)d_mask, &thru },
+				       num_samples, set_w, set_h, d_sample_pos);
 }
+

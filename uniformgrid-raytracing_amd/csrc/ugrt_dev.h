@@ -377,8 +377,9 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 }
 
 // where a ray leaves a hit: hit point P = o + t*d on the staged triangle tri ({., e1, e2}: d_stage_triangle),
-// nn = normalize(e1 x e2) turned against d, dn = d.nn (<= 0).  The text d_reflect_ray and k_ao_rays share (a macro, like
-// D_CROSS: the kernels that had it written out keep their code to the instruction).  D_HIT_FRAME_SIDED also says which
+// nn = normalize(e1 x e2) turned against d, dn = d.nn (<= 0).  The text d_reflect_ray and the generators' RAY_NORMAL rule
+// (d_secondary_ray, ugrt_bounce.hip: k_ao_rays) share (a macro, like D_CROSS: the kernels that had it written out keep
+// their code to the instruction).  D_HIT_FRAME_SIDED also says which
 // side was hit: front = the normal was not turned, d.normalize(e1 x e2) <= 0 (d_refract_ray).
 #define D_HIT_FRAME_SIDED(o, d, t, tri, P, nn, dn, front) \
 	do {                                              \
@@ -404,7 +405,8 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 	} while (0)
 
 // the reflection bounce's next ray: out = {P + eps*n, d - 2(d.n)n} of D_HIT_FRAME.
-// o is the camera for the first bounce (k_reflect_rays) and the ray's own origin after that (k_reflect_rays_next).
+// o is the camera for the first bounce (k_reflect_rays) and the ray's own origin after that (k_reflect_rays_next); both
+// kernels, like every secondary-ray generator, are d_secondary_ray of ugrt_bounce.hip.
 __device__ __forceinline__ void d_reflect_ray(const float *o, const float *d, float t, const float *tri, float eps,
 					      float *out)
 {

@@ -1,5 +1,5 @@
 // ugrt_shade.hip -- per-pixel stages: light-space ray mapping, ray re-ordering,
-// shading, secondary-ray generation, vertex animation.
+// shading, vertex animation.  (The secondary-ray generators: ugrt_bounce.hip.)
 #include "ugrt_dev.h"
 #include "ugrt_scan.h"
 
@@ -610,62 +610,9 @@ extern "C" int ugrt_shade_perlin(ugrt_ctx *ctx, unsigned char *d_img, const floa
 }
 
 // ---------------------------------------------------------------------------
-// reflection bounce helpers (not in the reference)
+// the first bounce's shading (not in the reference).  Its rays are ugrt_reflect_rays', which lives with
+// the other secondary-ray generators in ugrt_bounce.hip.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(PX_THREADS) void k_reflect_rays(const float *__restrict__ cam_pos,
-							      const float *__restrict__ t_list,
-							      const float *__restrict__ dir_list,
-							      const int *__restrict__ id_list, const int *__restrict__ mat_idx,
-							      const float *__restrict__ reflect, int mat_count,
-							      const float *__restrict__ verts, const int *__restrict__ tris,
-							      float eps, float *__restrict__ rays, int *__restrict__ active,
-							      int p0, int n)
-{
-	int i = blockIdx.x * PX_THREADS + threadIdx.x;
-	if (i >= n)
-		return;
-	int p = p0 + i;
-	int id = id_list[p];
-	float t = t_list[p];
-	float out[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f };
-	int act = 0;
-	if (t > 0 && id >= 0) {
-		int m = mat_idx[id];
-		if (m >= 0 && m < mat_count && reflect[m] > 0) {
-			float tri[9], d[3];
-			d_stage_triangle(verts, tris, (u32)id, 0.0f, 0.0f, 0.0f, tri);
-#pragma unroll
-			for (int k = 0; k < 3; k++)
-				d[k] = dir_list[p * 3 + k];
-			d_reflect_ray(cam_pos, d, t, tri, eps, out);
-			act = 1;
-		}
-	}
-#pragma unroll
-	for (int k = 0; k < 6; k++)
-		rays[p * 6 + k] = out[k];
-	active[p] = act;
-}
-
-extern "C" int ugrt_reflect_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value,
-				 const float *d_ray_dir, const int *d_intersect_id, const int *d_mat_idx,
-				 const float *d_reflect, int num_materials, const float *d_vertlist, const int *d_trilist,
-				 float eps, float *d_rays, int *d_active)
-{
-	if (!ctx || !d_cam_position || !d_t_value || !d_ray_dir || !d_intersect_id || !d_mat_idx || !d_reflect ||
-	    !d_vertlist || !d_trilist || !d_rays || !d_active)
-		return ugrt_fail(UGRT_EINVAL, "reflect_rays: null argument");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_REFLECT_GEN);
-	hipLaunchKernelGGL(k_reflect_rays, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, d_cam_position, d_t_value, d_ray_dir, d_intersect_id, d_mat_idx, d_reflect,
-			   num_materials, d_vertlist, d_trilist, eps, d_rays, d_active, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_REFLECT_GEN);
-	UGRT_HIP(hipGetLastError());
-	ctx->dda_deeper_level = false; // level 1: its ugrt_trace_dda uses the split-walk history (ugrt_bounce.hip)
-	return UGRT_OK;
-}
-
 struct ReflIn {
 	const float *reflect;
 	const float *verts;

@@ -20,6 +20,14 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _points(pts):
+    """Points as host floats [n, 3] (a sequence of triples or an array; None: no argument) -> (n, the 3n floats)."""
+    if pts is None:
+        return 0, None
+    flat = _f3(np.asarray(pts, np.float32).reshape(-1))
+    return len(flat) // 3, flat
+
+
 class Context:
     def __init__(self, width, height, device=0, light_grid=(128, 128), rows=None, flags=0,
                  uniform_dims=(64, 64, 32), slabs=1):
@@ -240,8 +248,7 @@ class Context:
                      is_shadowed=None):
         """shade_simple + shade_add_shadows per light and the mean, in one pass.  light_pos: one
         position (three host floats) per light; is_shadowed: the lights' flags stacked [L, W*H], or None."""
-        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
-        n = 0 if light_pos is None else len(light_pos)
+        n, pos = _points(light_pos)
         check(lib.ugrt_shade_lights(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
                                     _ptr(mat_idx), _ptr(mat_list), num_materials, n, pos, _ptr(is_shadowed)))
 
@@ -313,8 +320,7 @@ class Context:
     def trace_dda_any_lights(self, value, span, offset, verts, faces, orays, oactive, light_pos, occluded):
         """occluded[l, p] = trace_dda_any's flag (t_max 1) of the ray from orays' origin of p towards light_pos[l]; light_pos:
         one point (three host floats) per light; occluded: the lights' flags stacked [L, W*H]."""
-        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
-        n = 0 if light_pos is None else len(light_pos)
+        n, pos = _points(light_pos)
         check(lib.ugrt_trace_dda_any_lights(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
                                             _ptr(orays), _ptr(oactive), n, pos, _ptr(occluded)))
 
@@ -323,8 +329,7 @@ class Context:
                              occluded=None):
         """shade_reflect_depth_occluded + shade_add_shadows per light and the mean, in one pass.  light_pos: one position
         (three host floats) per light; is_shadowed: [L, W*H] or None; occluded: [depth, L, W*H] or None."""
-        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
-        n = 0 if light_pos is None else len(light_pos)
+        n, pos = _points(light_pos)
         check(lib.ugrt_shade_reflect_lights(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids),
                                             _ptr(cam_pos), _ptr(mat_idx), _ptr(mat_list), _ptr(reflect), num_materials,
                                             _ptr(verts), _ptr(faces), int(depth), _ptr(rays), _ptr(active), _ptr(hit_t),
@@ -341,8 +346,7 @@ class Context:
         """Bit s of mask[p] = trace_dda_any's flag (t_max radius) of the ray from orays' origin of p along dirs[s] in the
         basis of orays' normal of p; dirs: host floats [S, 3] (scenes.ao_directions), z along the normal; mask: uint32
         words (an int32 tensor serves)."""
-        flat = None if dirs is None else _f3(np.asarray(dirs, np.float32).reshape(-1))
-        n = 0 if dirs is None else len(flat) // 3
+        n, flat = _points(dirs)
         check(lib.ugrt_trace_dda_any_hemi(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
                                           _ptr(orays), _ptr(oactive), n, flat, radius, _ptr(mask)))
 
@@ -375,8 +379,7 @@ class Context:
     def trace_dda_any_lights_thru(self, value, span, offset, verts, faces, orays, oactive, light_pos, occluded, mat_idx,
                                   transmit, num_materials):
         """trace_dda_any_lights in which a triangle whose material has transmit > 0 does not occlude."""
-        pos = None if light_pos is None else _f3([x for p in light_pos for x in p])
-        n = 0 if light_pos is None else len(light_pos)
+        n, pos = _points(light_pos)
         check(lib.ugrt_trace_dda_any_lights_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts),
                                                  _ptr(faces), _ptr(orays), _ptr(oactive), n, pos, _ptr(occluded),
                                                  _ptr(mat_idx), _ptr(transmit), num_materials))
@@ -385,16 +388,14 @@ class Context:
     def trace_dda_any_area(self, value, span, offset, verts, faces, orays, oactive, samples, mask):
         """Bit s of mask[p] = trace_dda_any's flag (t_max 1) of the ray from orays' origin of p towards samples[s];
         samples: host floats [S, 3], world positions (scenes.area_samples); mask: uint32 words (an int32 tensor serves)."""
-        flat = None if samples is None else _f3(np.asarray(samples, np.float32).reshape(-1))
-        n = 0 if samples is None else len(flat) // 3
+        n, flat = _points(samples)
         check(lib.ugrt_trace_dda_any_area(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
                                           _ptr(orays), _ptr(oactive), n, flat, _ptr(mask)))
 
     def trace_dda_any_area_thru(self, value, span, offset, verts, faces, orays, oactive, samples, mask, mat_idx, transmit,
                                 num_materials):
         """trace_dda_any_area in which a triangle whose material has transmit > 0 does not occlude."""
-        flat = None if samples is None else _f3(np.asarray(samples, np.float32).reshape(-1))
-        n = 0 if samples is None else len(flat) // 3
+        n, flat = _points(samples)
         check(lib.ugrt_trace_dda_any_area_thru(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
                                                _ptr(orays), _ptr(oactive), n, flat, _ptr(mask), _ptr(mat_idx),
                                                _ptr(transmit), num_materials))

@@ -274,6 +274,17 @@ def refracts(f):
     return getattr(f, "refract", False)
 
 
+def see_through(f):
+    """What an any-hit walk is given to see through glass: (mat_idx, transmit, num_materials) in a refract frame, else
+    None."""
+    return (f.d_matidx, f.d_transmit, f.num_materials) if refracts(f) else None
+
+
+def any_hit(c, name, thru, *args):
+    """The context's any-hit call `name`, or with thru (see_through) its _thru twin, which takes thru's three behind."""
+    getattr(c, name if thru is None else name + "_thru")(*args, *(thru or ()))
+
+
 def level_weights(f):
     """What the shading calls are given as d_reflect: how much of a level's colour comes from the next level.  In a
     refract frame that is a glass material's transmit (f.d_continue), otherwise its reflect."""
@@ -325,22 +336,13 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
         if shadow_light is not None:
             c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_light, f.reflect_eps,
                              f.occlusion_rays, f.occlusion_active)
-            if refracts(f):
-                c.trace_dda_any_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active,
-                                     1.0, f.occluded_levels[j], f.d_matidx, f.d_transmit, f.num_materials)
-            else:
-                c.trace_dda_any(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays, f.occlusion_active, 1.0,
-                                f.occluded_levels[j])
+            any_hit(c, "trace_dda_any", see_through(f), uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays,
+                    f.occlusion_active, 1.0, f.occluded_levels[j])
         if shadow_lights is not None:
             c.occlusion_rays(rays, active, hit_t, hit_id, f.d_verts, f.d_faces, shadow_lights[0], f.reflect_eps,
                              f.occlusion_rays, f.occlusion_active)
-            if refracts(f):
-                c.trace_dda_any_lights_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays,
-                                            f.occlusion_active, shadow_lights, f.occluded_lights[j], f.d_matidx,
-                                            f.d_transmit, f.num_materials)
-            else:
-                c.trace_dda_any_lights(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.occlusion_rays,
-                                       f.occlusion_active, shadow_lights, f.occluded_lights[j])
+            any_hit(c, "trace_dda_any_lights", see_through(f), uvalue, uspan, uoffset, f.d_verts, f.d_faces,
+                    f.occlusion_rays, f.occlusion_active, shadow_lights, f.occluded_lights[j])
 
 
 def ao_pass(c, f, cam_pos, dirs, radius):
@@ -362,14 +364,11 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
     if sets is not None:
-        walk = c.trace_dda_any_area_sets if thru is None else c.trace_dda_any_area_sets_thru
-        walk(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, sets[0], sets[1], sets[2], samples,
-             f.area_mask, *(thru or ()))
-    elif thru is None:
-        c.trace_dda_any_area(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples, f.area_mask)
+        any_hit(c, "trace_dda_any_area_sets", thru, uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active,
+                sets[0], sets[1], sets[2], samples, f.area_mask)
     else:
-        c.trace_dda_any_area_thru(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, samples,
-                                  f.area_mask, *thru)
+        any_hit(c, "trace_dda_any_area", thru, uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active,
+                samples, f.area_mask)
 
 
 def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
@@ -756,7 +755,7 @@ class Renderer(_Frame, _Band):
         elif ao or area:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         if area:
-            thru = (self.d_matidx, self.d_transmit, self.num_materials) if self.refract else None
+            thru = see_through(self)
             if area_sets > 1:
                 area_pass(ctx, self, self.cam_pos, self._area_sets_stage(area, area_sets, area_radius, setup), thru,
                           (area,) + AREA_SET_TILES[area_sets])
