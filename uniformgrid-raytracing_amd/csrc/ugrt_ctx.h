@@ -248,6 +248,20 @@ static inline u32 ugrt_reported_status(const ugrt_ctx *ctx)
 void ugrt_prof_begin(ugrt_ctx *ctx, int stage);
 void ugrt_prof_end(ugrt_ctx *ctx, int stage);
 
+// A pass over the band's pixels, one thread each (pixel = p0 + blockIdx.x * PX_THREADS + threadIdx.x, the kernel's last
+// two parameters are p0 and n): `args` and the band, inside the stage's bracket.  The caller has checked its arguments.
+#define PX_THREADS 256
+template <class... P, class... A> static int ugrt_launch_pixels(ugrt_ctx *ctx, int stage, void (*kernel)(P...), A... args)
+{
+	UGRT_HIP(hipSetDevice(ctx->device));
+	ugrt_prof_begin(ctx, stage);
+	hipLaunchKernelGGL(kernel, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream, args...,
+			   ctx->p0, ctx->npix);
+	ugrt_prof_end(ctx, stage);
+	UGRT_HIP(hipGetLastError());
+	return UGRT_OK;
+}
+
 // prefix sums (ugrt_scan.hip) and the library wrappers (ugrt_prims.hip); all enqueue on ctx->stream
 int ugrt_prim_inclusive_scan(ugrt_ctx *ctx, const u32 *in, u32 *out, size_t n);
 int ugrt_prim_exclusive_scan(ugrt_ctx *ctx, const u32 *in, u32 *out, size_t n);

@@ -1,10 +1,9 @@
-// ugrt_filter.hip -- the edge-aware gather over mask words and the shading behind it (not in the reference; DESIGN.md
-// section 6.8).  Interleaved sample sets (ugrt_trace_dda_any_area_sets) give neighbouring pixels different S points of
-// the light; the gather sums the open bits of the pixels around p that lie on p's surface, with a tent weight, and
-// ugrt_shade_area_vis turns the two sums into ugrt_shade_area's byte.
+// ugrt_filter.hip -- the edge-aware gather over mask words (not in the reference).  Interleaved
+// sample sets (ugrt_trace_dda_any_area_sets) give neighbouring pixels different S points of the light; the gather sums
+// the open bits of the pixels around p that lie on p's surface, with a tent weight, and ugrt_shade_area_vis
+// (ugrt_shade.hip) turns the two sums into ugrt_shade_area's byte.
 #include "ugrt_dev.h"
 
-#define PX_THREADS 256
 #define FV_TW 32 // tile: FV_TH / 8 pixels per lane of a 256-lane workgroup, a wave = two rows of 32
 #ifndef FV_TH
 #define FV_TH 8 // (a multiple of 8; make EXTRA=-DFV_TH=16 builds the taller tile that DESIGN.md section 6.8 measures)
@@ -113,38 +112,6 @@ extern "C" int ugrt_filter_visibility(ugrt_ctx *ctx, const unsigned *d_mask, int
 	hipLaunchKernelGGL(k_filter_visibility, dim3((W + FV_TW - 1) / FV_TW, (rows + FV_TH - 1) / FV_TH), dim3(PX_THREADS), lds,
 			   ctx->stream, d_mask, d_orays, d_oactive, (u32)num_bits, low_bits, radius, normal_cos, plane_tol, W, row0,
 			   row0 + rows, d_vis);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
-}
-
-// the pass in the place of k_shade_area: num / den is the gathered share of open samples
-__global__ __launch_bounds__(PX_THREADS) void k_shade_area_vis(unsigned char *__restrict__ d_img, const u32 *__restrict__ vis,
-								u32 num_samples, int p0, int n)
-{
-	int i = blockIdx.x * PX_THREADS + threadIdx.x;
-	if (i >= n)
-		return;
-	const size_t pixelID = (size_t)(p0 + i);
-	const u32 num = vis[2 * pixelID], den = vis[2 * pixelID + 1];
-	if (den != 0u) {
-		const u32 a = num_samples * den + 2u * num, b = 3u * num_samples * den;
-#pragma unroll
-		for (int k = 0; k < 3; k++)
-			d_img[pixelID * 3 + k] = (unsigned char)(((u32)d_img[pixelID * 3 + k] * a) / b);
-	}
-}
-
-extern "C" int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_samples)
-{
-	if (!ctx || !d_img || !d_vis)
-		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: null argument");
-	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
-		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AREA_SAMPLES);
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_area_vis, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
-			   d_img, d_vis, (u32)num_samples, ctx->p0, ctx->npix);
 	ugrt_prof_end(ctx, UGRT_ST_SHADE);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;

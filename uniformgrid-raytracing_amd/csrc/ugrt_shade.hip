@@ -1,9 +1,8 @@
-// ugrt_shade.hip -- per-pixel stages: light-space ray mapping, ray re-ordering,
-// shading, vertex animation.  (The secondary-ray generators: ugrt_bounce.hip.)
+// ugrt_shade.hip -- per-pixel stages: light-space ray mapping, ray re-ordering, every shader (the reference's, and the
+// passes that blend reflection levels, lights and mask words into the image), vertex animation.  (The rays those levels
+// come from: ugrt_bounce.hip; the gather in front of ugrt_shade_area_vis: ugrt_filter.hip.)
 #include "ugrt_dev.h"
 #include "ugrt_scan.h"
-
-#define PX_THREADS 256
 
 // mapSort_Effective_kernel, misc_kernel.cu:255-296 (cam = LIGHT camera).
 // The reference launches one 8x8 block per tile; per-pixel work has no tile
@@ -43,14 +42,8 @@ extern "C" int ugrt_map_rays_to_light(ugrt_ctx *ctx, const float *d_t_value, con
 {
 	if (!ctx || !d_t_value || !d_ray_dir || !d_map || !d_cam_position)
 		return ugrt_fail(UGRT_EINVAL, "map_rays_to_light: null argument");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_MAP_RAYS);
-	hipLaunchKernelGGL(k_map_rays, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_t_value, d_ray_dir, d_map, d_cam_position, xM, yM,
-			   ctx->cfg.light_nbx, ctx->cfg.light_nby, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_MAP_RAYS);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_MAP_RAYS, k_map_rays, ctx->cam, d_t_value, d_ray_dir, d_map, d_cam_position, xM,
+				  yM, ctx->cfg.light_nbx, ctx->cfg.light_nby);
 }
 
 // ---------------------------------------------------------------------------
@@ -256,6 +249,58 @@ __device__ __forceinline__ float d_along_y(const CamBlock &cam, const float *vec
 	return (upDotValue > 0) ? angle : -1.0f * angle;
 }
 
+__device__ __forceinline__ void d_clamp1(float *color)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		color[k] = color[k] > 1.0f ? 1.0f : color[k];
+}
+
+// The primary hit of a pixel, as the kernels that shade one read it.  Each step reads what it names and nothing else, and
+// a kernel takes the steps inside its own guards (`in range`, `t_value > 0`, the spot light's none), so a miss reads no
+// material and no normal.
+struct PrimaryHit {
+	const float *__restrict__ dd_normal, *__restrict__ dd_t_value, *__restrict__ dd_dir;
+	int *__restrict__ dd_intersect_id;
+	const float *__restrict__ d_cam_pos;
+	const int *__restrict__ mat_idx;
+	const float *__restrict__ mat_list;
+	int mat_count, pixelID;
+
+	// the triangle id becomes the material id and is written back; returns it, or -1 where it is out of range.  The
+	// reference reads mat_idx[-2] for a miss (shader_kernel.cu:170); a miss keeps its id and shades black.
+	__device__ __forceinline__ int material_id() const
+	{
+		int tri_intersected = dd_intersect_id[pixelID];
+		int idx = tri_intersected >= 0 ? mat_idx[tri_intersected] : tri_intersected;
+		dd_intersect_id[pixelID] = idx;
+		return idx >= 0 && idx < mat_count ? idx : -1;
+	}
+	__device__ __forceinline__ float t_value() const { return dd_t_value[pixelID]; }
+	__device__ __forceinline__ void point(float t, float *p) const
+	{
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			p[k] = d_cam_pos[k] + t * dd_dir[pixelID * 3 + k];
+	}
+	__device__ __forceinline__ void normal(float *nrm) const
+	{
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			nrm[k] = dd_normal[pixelID * 3 + k];
+	}
+};
+
+// Kd of material m, twice: ambient uses Kd too (shader_kernel.cu:180-186)
+__device__ __forceinline__ void d_material_kd(const float *__restrict__ mat_list, int m, float *material)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		material[k] = mat_list[m * 6 + 3 + k];
+		material[3 + k] = mat_list[m * 6 + 3 + k];
+	}
+}
+
 template <bool SPOT>
 __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned char *__restrict__ d_img,
 						       const float *__restrict__ dd_normal,
@@ -268,16 +313,11 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned cha
 	if (i >= n)
 		return;
 	int pixelID = p0 + i;
-	float color[3] = { 0.0f, 0.0f, 0.0f }, drop_off = 1.0f;
-	int tri_intersected = dd_intersect_id[pixelID];
-	// the reference reads mat_idx[-2] for a miss (shader_kernel.cu:170); a miss keeps its id and shades black
-	int idx = tri_intersected >= 0 ? mat_idx[tri_intersected] : tri_intersected;
-	float t_value = dd_t_value[pixelID];
-	float dir[3] = { dd_dir[pixelID * 3 + 0], dd_dir[pixelID * 3 + 1], dd_dir[pixelID * 3 + 2] };
-	float point[3];
-	point[0] = d_cam_pos[0] + t_value * dir[0];
-	point[1] = d_cam_pos[1] + t_value * dir[1];
-	point[2] = d_cam_pos[2] + t_value * dir[2];
+	float color[3] = { 0.0f, 0.0f, 0.0f }, drop_off = 1.0f, point[3];
+	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
+	const int idx = hit.material_id();
+	const float t_value = hit.t_value();
+	hit.point(t_value, point);
 	if (SPOT) {
 		float lrd[3];
 		lrd[0] = point[0] - cam.cc[0];
@@ -292,25 +332,19 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned cha
 		const float qpi = (float)(3.14159265358979323846 / 4);
 		drop_off = (x < qpi && x > -qpi && y < qpi && y > -qpi) ? 1.0f : 0.25f;
 	}
-	dd_intersect_id[pixelID] = idx;
-	if (idx >= 0 && idx < mat_count && (SPOT || t_value > 0)) {
-		float material[6];
-#pragma unroll
-		for (int k = 0; k < 3; k++) {
-			material[k] = mat_list[idx * 6 + 3 + k]; // ambient uses Kd too (:180-186)
-			material[3 + k] = mat_list[idx * 6 + 3 + k];
-		}
-		float nrm[3] = { dd_normal[pixelID * 3 + 0], dd_normal[pixelID * 3 + 1], dd_normal[pixelID * 3 + 2] };
+	if (idx >= 0 && (SPOT || t_value > 0)) {
+		float material[6], nrm[3];
+		d_material_kd(mat_list, idx, material);
+		hit.normal(nrm);
 		d_lambert<SPOT>(cam, point, nrm, color, material, drop_off);
-#pragma unroll
-		for (int k = 0; k < 3; k++)
-			color[k] = color[k] > 1.0f ? 1.0f : color[k];
+		d_clamp1(color);
 	}
 	d_img[pixelID * 3 + 0] = d_to_u8(color[0]);
 	d_img[pixelID * 3 + 1] = d_to_u8(color[1]);
 	d_img[pixelID * 3 + 2] = d_to_u8(color[2]);
 }
 
+// the null check of every export that takes the primary arrays
 static int shade_args_ok(ugrt_ctx *ctx, const void *a, const void *b, const void *c, const void *d, const void *e,
 			 const void *f, const void *g, const void *h, const char *who)
 {
@@ -328,14 +362,8 @@ extern "C" int ugrt_shade_simple(ugrt_ctx *ctx, unsigned char *d_img, const floa
 			       d_mat_list, "shade_simple");
 	if (rc)
 		return rc;
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade<false>, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
-			   d_mat_idx, d_mat_list, num_materials, (float *)nullptr, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade<false>, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, (float *)nullptr);
 }
 
 // Shader::spotlight_shade, shader.h:88-113 (d_dump may be null; the reference
@@ -349,14 +377,8 @@ extern "C" int ugrt_shade_spotlight(ugrt_ctx *ctx, unsigned char *d_img, const f
 			       d_mat_list, "shade_spotlight");
 	if (rc)
 		return rc;
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade<true>, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
-			   d_mat_idx, d_mat_list, num_materials, d_dump, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade<true>, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, d_dump);
 }
 
 // shadow_kernel, shader_kernel.cu:347-359
@@ -379,17 +401,24 @@ extern "C" int ugrt_shade_add_shadows(ugrt_ctx *ctx, unsigned char *d_img, const
 {
 	if (!ctx || !d_img || !d_is_shadowed)
 		return ugrt_fail(UGRT_EINVAL, "shade_add_shadows: null argument");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_add_shadows, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, d_img, d_is_shadowed, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_add_shadows, d_img, d_is_shadowed);
 }
 
-// Ambient occlusion (not in the reference): a last integer pass over the image, like
-// k_add_shadows.  bit s of mask = hemisphere ray s is occluded; each byte is scaled by the share of open rays.
+// ---------------------------------------------------------------------------
+// The integer passes over the image that stand in k_add_shadows' place where a pixel has several occlusion rays (not in
+// the reference): each of the pixel's bytes becomes byte * a / b.
+// ---------------------------------------------------------------------------
+template <class I> __device__ __forceinline__ void d_scale_bytes(unsigned char *__restrict__ d_img, I pixelID, u32 a, u32 b)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		d_img[pixelID * 3 + k] = (unsigned char)(((u32)d_img[pixelID * 3 + k] * a) / b);
+}
+
+static u32 low_bits_of(int num_bits) { return num_bits == 32 ? 0xFFFFFFFFu : (1u << num_bits) - 1u; }
+
+// Ambient occlusion.  bit s of mask = hemisphere ray s is occluded; each byte is scaled by the
+// share of open rays.
 __global__ __launch_bounds__(PX_THREADS) void k_shade_ao(unsigned char *__restrict__ d_img, const u32 *__restrict__ mask,
 							  u32 num_dirs, u32 low_bits, int p0, int n)
 {
@@ -398,12 +427,8 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_ao(unsigned char *__restri
 		return;
 	int pixelID = p0 + i;
 	const u32 m = mask[pixelID] & low_bits;
-	if (m != 0u) {
-		const u32 open = num_dirs - (u32)__popc(m);
-#pragma unroll
-		for (int k = 0; k < 3; k++)
-			d_img[pixelID * 3 + k] = (unsigned char)(((u32)d_img[pixelID * 3 + k] * open) / num_dirs);
-	}
+	if (m != 0u)
+		d_scale_bytes(d_img, pixelID, num_dirs - (u32)__popc(m), num_dirs);
 }
 
 extern "C" int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, int num_dirs)
@@ -412,18 +437,11 @@ extern "C" int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned
 		return ugrt_fail(UGRT_EINVAL, "shade_ao: null argument");
 	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
 		return ugrt_fail(UGRT_EINVAL, "shade_ao: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const u32 low_bits = num_dirs == 32 ? 0xFFFFFFFFu : (1u << num_dirs) - 1u;
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_ao, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
-			   d_img, d_mask, (u32)num_dirs, low_bits, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_ao, d_img, d_mask, (u32)num_dirs, low_bits_of(num_dirs));
 }
 
-// Area lights (not in the reference): the pass in the place of k_add_shadows.  bit s of mask =
-// the shadow ray towards sample s of the light's disk is occluded; a byte goes from b (every sample lit) to b / 3 (none).
+// Area lights.  bit s of mask = the shadow ray towards sample s of the light's disk is occluded;
+// a byte goes from b (every sample lit) to b / 3 (none).
 __global__ __launch_bounds__(PX_THREADS) void k_shade_area(unsigned char *__restrict__ d_img, const u32 *__restrict__ mask,
 							    u32 num_samples, u32 low_bits, int p0, int n)
 {
@@ -434,10 +452,7 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_area(unsigned char *__rest
 	const u32 m = mask[pixelID] & low_bits;
 	if (m != 0u) {
 		const u32 lit = num_samples - (u32)__popc(m);
-#pragma unroll
-		for (int k = 0; k < 3; k++)
-			d_img[pixelID * 3 + k] =
-				(unsigned char)(((u32)d_img[pixelID * 3 + k] * (num_samples + 2u * lit)) / (3u * num_samples));
+		d_scale_bytes(d_img, pixelID, num_samples + 2u * lit, 3u * num_samples);
 	}
 }
 
@@ -447,14 +462,30 @@ extern "C" int ugrt_shade_area(ugrt_ctx *ctx, unsigned char *d_img, const unsign
 		return ugrt_fail(UGRT_EINVAL, "shade_area: null argument");
 	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
 		return ugrt_fail(UGRT_EINVAL, "shade_area: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AREA_SAMPLES);
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const u32 low_bits = num_samples == 32 ? 0xFFFFFFFFu : (1u << num_samples) - 1u;
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_area, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0, ctx->stream,
-			   d_img, d_mask, (u32)num_samples, low_bits, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_area, d_img, d_mask, (u32)num_samples, low_bits_of(num_samples));
+}
+
+// the pass in the place of k_shade_area behind the edge-aware gather (ugrt_filter.hip): num / den
+// is the gathered share of open samples
+__global__ __launch_bounds__(PX_THREADS) void k_shade_area_vis(unsigned char *__restrict__ d_img, const u32 *__restrict__ vis,
+								u32 num_samples, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t pixelID = (size_t)(p0 + i);
+	const u32 num = vis[2 * pixelID], den = vis[2 * pixelID + 1];
+	if (den != 0u)
+		d_scale_bytes(d_img, pixelID, num_samples * den + 2u * num, 3u * num_samples * den);
+}
+
+extern "C" int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_samples)
+{
+	if (!ctx || !d_img || !d_vis)
+		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: null argument");
+	if (num_samples < 1 || num_samples > UGRT_MAX_AREA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "shade_area_vis: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AREA_SAMPLES);
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_area_vis, d_img, d_vis, (u32)num_samples);
 }
 
 // ---------------------------------------------------------------------------
@@ -466,6 +497,18 @@ struct LightsIn {
 	float pos[3 * UGRT_MAX_LIGHTS]; // by value: uniform over the launch, read from the kernarg segment
 	int count;
 };
+
+// the lights of export `who`: the range check, then the by-value block
+static int lights_in(const char *who, int num_lights, const float *light_pos, LightsIn *lights)
+{
+	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_lights %d is not in 1..%d", who, num_lights, UGRT_MAX_LIGHTS);
+	*lights = {};
+	for (int k = 0; k < 3 * num_lights; k++)
+		lights->pos[k] = light_pos[k];
+	lights->count = num_lights;
+	return UGRT_OK;
+}
 
 __global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsigned char *__restrict__ d_img,
 							      const float *__restrict__ dd_normal,
@@ -483,28 +526,23 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsig
 		return;
 	int pixelID = p0 + i;
 	u32 sum[3] = { 0u, 0u, 0u };
-	int tri_intersected = dd_intersect_id[pixelID];
-	int idx = tri_intersected >= 0 ? mat_idx[tri_intersected] : tri_intersected; // as k_shade
-	float t_value = dd_t_value[pixelID];
-	dd_intersect_id[pixelID] = idx;
-	if (idx >= 0 && idx < mat_count && t_value > 0) {
-		float dir[3] = { dd_dir[pixelID * 3 + 0], dd_dir[pixelID * 3 + 1], dd_dir[pixelID * 3 + 2] };
-		float nrm[3] = { dd_normal[pixelID * 3 + 0], dd_normal[pixelID * 3 + 1], dd_normal[pixelID * 3 + 2] };
-		float point[3], material[6], pv[3], nv[3];
-#pragma unroll
-		for (int k = 0; k < 3; k++) {
-			point[k] = d_cam_pos[k] + t_value * dir[k];
-			material[k] = mat_list[idx * 6 + 3 + k];
-			material[3 + k] = mat_list[idx * 6 + 3 + k];
-		}
+	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
+	const int idx = hit.material_id();
+	const float t_value = hit.t_value();
+	if (idx >= 0 && t_value > 0) {
+		float material[6], point[3], nrm[3], pv[3], nv[3];
+		hit.point(t_value, point);
+		hit.normal(nrm);
+		d_material_kd(mat_list, idx, material);
 		d_lambert_view(cam, point, nrm, pv, nv);
 		for (int l = 0; l < lights.count; l++) {
 			float color[3] = { 0.0f, 0.0f, 0.0f };
 			d_lambert_from(cam, &lights.pos[3 * l], pv, nv, color, material);
+			d_clamp1(color);
 			const bool dark = is_shadowed && is_shadowed[(size_t)l * level + (size_t)pixelID] == 1;
 #pragma unroll
 			for (int k = 0; k < 3; k++) {
-				unsigned char b = d_to_u8(color[k] > 1.0f ? 1.0f : color[k]);
+				unsigned char b = d_to_u8(color[k]);
 				sum[k] += dark ? (u32)(b / 3) : (u32)b;
 			}
 		}
@@ -525,21 +563,12 @@ extern "C" int ugrt_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const floa
 		return rc;
 	if (!light_pos)
 		return ugrt_fail(UGRT_EINVAL, "shade_lights: null argument");
-	if (num_lights < 1 || num_lights > UGRT_MAX_LIGHTS)
-		return ugrt_fail(UGRT_EINVAL, "shade_lights: num_lights %d is not in 1..%d", num_lights, UGRT_MAX_LIGHTS);
-	LightsIn lights = {};
-	for (int k = 0; k < 3 * num_lights; k++)
-		lights.pos[k] = light_pos[k];
-	lights.count = num_lights;
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_lights, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
-			   d_mat_idx, d_mat_list, num_materials, lights, d_is_shadowed,
-			   (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	LightsIn lights;
+	if ((rc = lights_in("shade_lights", num_lights, light_pos, &lights)))
+		return rc;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_lights, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, lights, d_is_shadowed,
+				  (size_t)ctx->cfg.width * (size_t)ctx->cfg.height);
 }
 
 // shader_kernel.cu:4-44 Noise / InterPolation / PerlinNoise with octaves = 1
@@ -600,19 +629,87 @@ extern "C" int ugrt_shade_perlin(ugrt_ctx *ctx, unsigned char *d_img, const floa
 	(void)d_cam_position;
 	if (!ctx || !d_img || !d_intersect_id)
 		return ugrt_fail(UGRT_EINVAL, "shade_perlin: null argument");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_perlin, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, d_img, d_intersect_id, ctx->cfg.width, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_perlin, d_img, d_intersect_id, ctx->cfg.width);
 }
 
 // ---------------------------------------------------------------------------
-// the first bounce's shading (not in the reference).  Its rays are ugrt_reflect_rays', which lives with
-// the other secondary-ray generators in ugrt_bounce.hip.
+// reflections (not in the reference): the levels' hits blended front to back.  Their rays
+// are the secondary-ray generators' (ugrt_bounce.hip), which also says how a frame's levels lie in the arrays.
 // ---------------------------------------------------------------------------
+struct DepthIn {
+	const float *reflect;
+	const float *verts;
+	const int *tris;
+	const float *rays;  // level j at (j-1) * level * 6
+	const int *active;  // level j at (j-1) * level
+	const float *hit_t;
+	const int *hit_id;
+	size_t level;       // W*H
+	int depth;
+	const int *occluded; // level j at (j-1) * level (ugrt_shade_reflect_depth_occluded; otherwise null and never read)
+};
+
+// the levels of export `who`: the null and range checks, then the by-value block
+static int depth_in(ugrt_ctx *ctx, const char *who, const float *d_reflect, const float *d_vertlist, const int *d_trilist,
+		    int depth, const float *d_rays, const int *d_active, const float *d_hit_t, const int *d_hit_id,
+		    const int *d_occluded, DepthIn *in)
+{
+	if (!d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id)
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if (depth < 1 || depth > UGRT_MAX_REFLECT_DEPTH)
+		return ugrt_fail(UGRT_EINVAL, "%s: depth %d outside 1..%d", who, depth, UGRT_MAX_REFLECT_DEPTH);
+	*in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id,
+		(size_t)ctx->cfg.width * (size_t)ctx->cfg.height, depth, d_occluded };
+	return UGRT_OK;
+}
+
+// The hit of level j, whose arrays lie at q = (j-1) * level + pixel.  False for a miss or a material out of range: it has
+// no colour and leaves *kr.  Otherwise *kr is the hit material's reflect (read only where the level goes on, i.e. it is
+// in range), `material` its Kd twice, hp the hit point on the level's ray and nn the triangle's unit normal.
+// (k_shade_reflect and k_shade_reflect_lights have this body written out, for their speed and register count: see there.)
+__device__ __forceinline__ bool d_level_hit(const DepthIn &in, const int *__restrict__ mat_idx,
+					    const float *__restrict__ mat_list, int mat_count, size_t q, float *kr,
+					    float *material, float *hp, float *nn)
+{
+	int hid = in.hit_id[q];
+	if (hid < 0)
+		return false;
+	int hm = mat_idx[hid];
+	if (hm < 0 || hm >= mat_count)
+		return false;
+	float t9[9];
+	float ht = in.hit_t[q];
+	*kr = in.reflect[hm];
+	d_stage_triangle(in.verts, in.tris, (u32)hid, 0.0f, 0.0f, 0.0f, t9);
+	float *e1 = &t9[3], *e2 = &t9[6];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		hp[k] = in.rays[q * 6 + k] + ht * in.rays[q * 6 + 3 + k];
+	d_material_kd(mat_list, hm, material);
+	D_NORMALIZE(e1);
+	D_NORMALIZE(e2);
+	D_CROSS(nn, e1, e2);
+	D_NORMALIZE(nn);
+	return true;
+}
+
+// the clamped Lambert colour of level j's hit (as k_shade shades the primary hit); 0 where the level has no colour
+__device__ __forceinline__ void d_level_color(const CamBlock &cam, const DepthIn &in, const int *__restrict__ mat_idx,
+					      const float *__restrict__ mat_list, int mat_count, size_t q, float *rc,
+					      float *kr)
+{
+	float hmat[6], hp[3], nn[3];
+	rc[0] = rc[1] = rc[2] = 0.0f;
+	if (!d_level_hit(in, mat_idx, mat_list, mat_count, q, kr, hmat, hp, nn))
+		return;
+	d_lambert<false>(cam, hp, nn, rc, hmat, 1.0f);
+	d_clamp1(rc);
+}
+
+// The first bounce alone: (1 - k) * primary colour + k * level 1's colour where the pixel has a level-1
+// ray.  These are k_shade_reflect_depth<false>'s bytes at depth 1 (tests/test_reflect_depth.py pins the two).  The frame
+// with one bounce, the benchmark's, keeps this kernel and its written-out body: through the depth kernel it shades 2 to 4 %
+// slower there, and written with PrimaryHit and d_level_color 0.9 % slower (profiles/shade_refactor.txt).
 struct ReflIn {
 	const float *reflect;
 	const float *verts;
@@ -697,6 +794,85 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_reflect(CamBlock cam, unsi
 	d_img[pixelID * 3 + 2] = d_to_u8(color[2]);
 }
 
+// acc = 0, w = 1; level j that goes on (active_{j+1}): acc += (w*(1-k_j))*L_j, w *= k_j; the first level that does not
+// (level `depth` at the latest): acc += w*L_j.  At depth 1 this is k_shade_reflect operation for operation.  A
+// pixel reads the levels it reaches and no others.  OCC: a level j >= 1 whose hit is occluded (in.occluded) is darkened
+// to L_j / 3, the float counterpart of add_shadows' /= 3, before it is weighted.
+template <bool OCC>
+__global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_depth(CamBlock cam, unsigned char *__restrict__ d_img,
+								     const float *__restrict__ dd_normal,
+								     const float *__restrict__ dd_t_value,
+								     const float *__restrict__ dd_dir,
+								     int *__restrict__ dd_intersect_id,
+								     const float *__restrict__ d_cam_pos,
+								     const int *__restrict__ mat_idx,
+								     const float *__restrict__ mat_list, int mat_count,
+								     DepthIn in, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	float acc[3] = { 0.0f, 0.0f, 0.0f };
+	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
+	const int idx = hit.material_id();
+	if (idx >= 0) {
+		float color[3] = { 0.0f, 0.0f, 0.0f }, material[6];
+		const float t_value = hit.t_value();
+		d_material_kd(mat_list, idx, material);
+		if (t_value > 0) {
+			float point[3], nrm[3];
+			hit.point(t_value, point);
+			hit.normal(nrm);
+			d_lambert<false>(cam, point, nrm, color, material, 1.0f);
+			d_clamp1(color);
+		}
+		float w = 1.0f, kr = in.reflect[idx];
+		// level j (0 = the primary hit) goes on when active_{j+1}, which lies at j * level
+		for (int j = 0;; j++) {
+			const size_t q = (size_t)j * in.level + (size_t)pixelID;
+			if (j >= in.depth || !in.active[q]) {
+#pragma unroll
+				for (int k = 0; k < 3; k++)
+					acc[k] = acc[k] + w * color[k];
+				break;
+			}
+#pragma unroll
+			for (int k = 0; k < 3; k++)
+				acc[k] = acc[k] + (w * (1.0f - kr)) * color[k];
+			w = w * kr;
+			d_level_color(cam, in, mat_idx, mat_list, mat_count, q, color, &kr);
+			if (OCC && in.occluded[q] == 1) {
+#pragma unroll
+				for (int k = 0; k < 3; k++)
+					color[k] = color[k] / 3.0f;
+			}
+		}
+	}
+	d_img[pixelID * 3 + 0] = d_to_u8(acc[0]);
+	d_img[pixelID * 3 + 1] = d_to_u8(acc[1]);
+	d_img[pixelID * 3 + 2] = d_to_u8(acc[2]);
+}
+
+// both exports: d_occluded null = ugrt_shade_reflect_depth
+static int shade_reflect_depth(ugrt_ctx *ctx, const char *who, unsigned char *d_img, const float *d_normal,
+			       const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+			       const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+			       const float *d_reflect, int num_materials, const float *d_vertlist, const int *d_trilist,
+			       int depth, const float *d_rays, const int *d_active, const float *d_hit_t, const int *d_hit_id,
+			       const int *d_occluded)
+{
+	DepthIn in;
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, who);
+	if (rc || (rc = depth_in(ctx, who, d_reflect, d_vertlist, d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id,
+				 d_occluded, &in)))
+		return rc;
+	const auto kernel = d_occluded ? k_shade_reflect_depth<true> : k_shade_reflect_depth<false>;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, kernel, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+				  d_mat_list, num_materials, in);
+}
+
 extern "C" int ugrt_shade_reflect(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
 				  const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
 				  const int *d_mat_idx, const float *d_mat_list, const float *d_reflect, int num_materials,
@@ -709,15 +885,177 @@ extern "C" int ugrt_shade_reflect(ugrt_ctx *ctx, unsigned char *d_img, const flo
 		return rc;
 	if (!d_reflect || !d_vertlist || !d_trilist || !d_rays || !d_active || !d_hit_t || !d_hit_id)
 		return ugrt_fail(UGRT_EINVAL, "shade_reflect: null argument");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	ReflIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id };
-	ugrt_prof_begin(ctx, UGRT_ST_SHADE);
-	hipLaunchKernelGGL(k_shade_reflect, dim3((ctx->npix + PX_THREADS - 1) / PX_THREADS), dim3(PX_THREADS), 0,
-			   ctx->stream, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position,
-			   d_mat_idx, d_mat_list, num_materials, in, ctx->p0, ctx->npix);
-	ugrt_prof_end(ctx, UGRT_ST_SHADE);
-	UGRT_HIP(hipGetLastError());
-	return UGRT_OK;
+	const ReflIn in = { d_reflect, d_vertlist, d_trilist, d_rays, d_active, d_hit_t, d_hit_id };
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_reflect, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, in);
+}
+
+extern "C" int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
+					const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+					const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+					const float *d_reflect, int num_materials, const float *d_vertlist,
+					const int *d_trilist, int depth, const float *d_rays, const int *d_active,
+					const float *d_hit_t, const int *d_hit_id)
+{
+	return shade_reflect_depth(ctx, "shade_reflect_depth", d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id,
+				   d_cam_position, d_mat_idx, d_mat_list, d_reflect, num_materials, d_vertlist, d_trilist, depth,
+				   d_rays, d_active, d_hit_t, d_hit_id, nullptr);
+}
+
+extern "C" int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal,
+						 const float *d_t_value, const float *d_ray_dir, int *d_intersect_id,
+						 const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list,
+						 const float *d_reflect, int num_materials, const float *d_vertlist,
+						 const int *d_trilist, int depth, const float *d_rays, const int *d_active,
+						 const float *d_hit_t, const int *d_hit_id, const int *d_occluded)
+{
+	if (!d_occluded)
+		return ugrt_fail(UGRT_EINVAL, "shade_reflect_depth_occluded: null argument");
+	return shade_reflect_depth(ctx, "shade_reflect_depth_occluded", d_img, d_normal, d_t_value, d_ray_dir,
+				   d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, d_reflect, num_materials, d_vertlist,
+				   d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id, d_occluded);
+}
+
+// ---------------------------------------------------------------------------
+// reflections under several lights: the depth composition of k_shade_reflect_depth<OCC> and
+// k_add_shadows once per light and the mean of the bytes, in one pass.  The level chain (active_{j+1}, k_j, w) does not
+// know the light: it is walked once, every level's hit is fetched once and brought to view space once (d_lambert_view),
+// and shaded per light from registers (d_lambert_from) into the light's own accumulator.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(PX_THREADS) void k_shade_reflect_lights(CamBlock cam, unsigned char *__restrict__ d_img,
+								      const float *__restrict__ dd_normal,
+								      const float *__restrict__ dd_t_value,
+								      const float *__restrict__ dd_dir,
+								      int *__restrict__ dd_intersect_id,
+								      const float *__restrict__ d_cam_pos,
+								      const int *__restrict__ mat_idx,
+								      const float *__restrict__ mat_list, int mat_count,
+								      DepthIn in, LightsIn lights,
+								      const int *__restrict__ is_shadowed, // [count][level], or null
+								      const int *__restrict__ occluded, // [depth][count][level], or null
+								      int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	u32 sum[3] = { 0u, 0u, 0u };
+	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
+	const int idx = hit.material_id();
+	if (idx >= 0) {
+		// the hit of the level at hand: lit = it has a colour at all; view-space point and normal; Kd
+		float pv[3] = { 0.0f, 0.0f, 0.0f }, nv[3] = { 0.0f, 0.0f, 0.0f }, kd[3];
+		const float t_value = hit.t_value();
+		bool lit = t_value > 0;
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			kd[k] = mat_list[idx * 6 + 3 + k];
+		if (lit) {
+			float point[3], nrm[3];
+			hit.point(t_value, point);
+			hit.normal(nrm);
+			d_lambert_view(cam, point, nrm, pv, nv);
+		}
+		float acc[UGRT_MAX_LIGHTS][3];
+#pragma unroll
+		for (int l = 0; l < UGRT_MAX_LIGHTS; l++)
+			acc[l][0] = acc[l][1] = acc[l][2] = 0.0f;
+		float w = 1.0f, kr = in.reflect[idx];
+		// level j (0 = the primary hit) goes on when active_{j+1}, which lies at j * level
+		for (int j = 0;; j++) {
+			const size_t q = (size_t)j * in.level + (size_t)pixelID;
+			const bool goes_on = j < in.depth && in.active[q];
+			const float wt = goes_on ? w * (1.0f - kr) : w;
+			const float material[6] = { kd[0], kd[1], kd[2], kd[0], kd[1], kd[2] };
+			// (the lights unrolled with a uniform guard: acc stays in registers)
+#pragma unroll
+			for (int l = 0; l < UGRT_MAX_LIGHTS; l++) {
+				if (l < lights.count) {
+					float color[3] = { 0.0f, 0.0f, 0.0f };
+					if (lit) {
+						d_lambert_from(cam, &lights.pos[3 * l], pv, nv, color, material);
+						const bool dark = j >= 1 && occluded &&
+								  occluded[((size_t)(j - 1) * (size_t)lights.count + (size_t)l) * in.level + (size_t)pixelID] == 1;
+#pragma unroll
+						for (int k = 0; k < 3; k++) {
+							color[k] = color[k] > 1.0f ? 1.0f : color[k];
+							if (dark)
+								color[k] = color[k] / 3.0f;
+						}
+					}
+#pragma unroll
+					for (int k = 0; k < 3; k++)
+						acc[l][k] = acc[l][k] + wt * color[k];
+				}
+			}
+			if (!goes_on)
+				break;
+			w = w * kr;
+			// level j + 1's hit: d_level_hit written out.  As a call of it the compiler needs 101 to 105 vector
+			// registers for this kernel instead of 91, one wave per SIMD fewer (profiles/shade_refactor.txt).
+			lit = false;
+			int hid = in.hit_id[q];
+			if (hid >= 0) {
+				int hm = mat_idx[hid];
+				if (hm >= 0 && hm < mat_count) {
+					float t9[9], nn[3], hp[3];
+					float ht = in.hit_t[q];
+					kr = in.reflect[hm];
+					d_stage_triangle(in.verts, in.tris, (u32)hid, 0.0f, 0.0f, 0.0f, t9);
+					float *e1 = &t9[3], *e2 = &t9[6];
+#pragma unroll
+					for (int k = 0; k < 3; k++) {
+						hp[k] = in.rays[q * 6 + k] + ht * in.rays[q * 6 + 3 + k];
+						kd[k] = mat_list[hm * 6 + 3 + k];
+					}
+					D_NORMALIZE(e1);
+					D_NORMALIZE(e2);
+					D_CROSS(nn, e1, e2);
+					D_NORMALIZE(nn);
+					d_lambert_view(cam, hp, nn, pv, nv);
+					lit = true;
+				}
+			}
+		}
+#pragma unroll
+		for (int l = 0; l < UGRT_MAX_LIGHTS; l++) {
+			if (l < lights.count) {
+				const bool dark = is_shadowed && is_shadowed[(size_t)l * in.level + (size_t)pixelID] == 1;
+#pragma unroll
+				for (int k = 0; k < 3; k++) {
+					unsigned char b = d_to_u8(acc[l][k]);
+					sum[k] += dark ? (u32)(b / 3) : (u32)b;
+				}
+			}
+		}
+	}
+	d_img[pixelID * 3 + 0] = (unsigned char)(sum[0] / (u32)lights.count);
+	d_img[pixelID * 3 + 1] = (unsigned char)(sum[1] / (u32)lights.count);
+	d_img[pixelID * 3 + 2] = (unsigned char)(sum[2] / (u32)lights.count);
+}
+
+extern "C" int ugrt_shade_reflect_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+					 const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+					 const int *d_mat_idx, const float *d_mat_list, const float *d_reflect, int num_materials,
+					 const float *d_vertlist, const int *d_trilist, int depth, const float *d_rays,
+					 const int *d_active, const float *d_hit_t, const int *d_hit_id, int num_lights,
+					 const float *light_pos, const int *d_is_shadowed, const int *d_occluded)
+{
+	const char *who = "shade_reflect_lights";
+	DepthIn in;
+	LightsIn lights;
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, who);
+	if (rc)
+		return rc;
+	if (!light_pos)
+		return ugrt_fail(UGRT_EINVAL, "%s: null argument", who);
+	if ((rc = depth_in(ctx, who, d_reflect, d_vertlist, d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id, nullptr, &in)) ||
+	    (rc = lights_in(who, num_lights, light_pos, &lights)))
+		return rc;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_reflect_lights, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, in, lights, d_is_shadowed,
+				  d_occluded);
 }
 
 // ---------------------------------------------------------------------------
