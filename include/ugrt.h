@@ -60,7 +60,9 @@ enum {
 	 * through ugrt_animate, or that it calls ugrt_geometry_changed after changing them itself
 	 * (the reference's other writer is the per-frame upload of scene.h:70 frames).  The builds then
 	 * keep the per-triangle records of the previous build instead of rewriting them three times a
-	 * frame.  Without the flag every build assumes new geometry, as the reference does. */
+	 * frame.  Without the flag every build assumes new geometry, as the reference does.
+	 * The same promise keeps the uniform grid: it has no other input than these arrays, the box and the
+	 * context's uniform_dims, so ugrt_grid_build_uniform enqueues nothing while they stand (see there). */
 	UGRT_FLAG_STATIC_GEOMETRY = 4u,
 	/* ray set-up (trace_kernel.cu:96-105, per_frame_funcs.h:421-433): the reference samples its 5x5 direction
 	 * texture through the texture unit's linear filter, whose interpolation weights have 8 fractional bits.  By default
@@ -217,6 +219,7 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * ballots instead of LDS atomics, "ray_sort" 1 = the deferred ugrt_sort_rays sorts at once also where nothing needs it
  * (see there); "dda_blocks", "primary_waves",
  * "any_rays_per_wave", "any_coop": ugrt_trace_dda_any (see there);
+ * "uniform_reuse" 0 = ugrt_grid_build_uniform builds every time (default 1: it keeps the grid while its inputs stand, see there);
  * "shadow_waves": number of persistent single-wave workgroups of the bounce, the primary tracer and the two
  * shadow kernels (the primary tracer and the exact shadow pass run one wave per work item by default, "primary_xcd_run" /
  * "shadow_xcd_run" neighbouring items per XCD in turn; "primary_waves" set / "shadow_xcd_run" 0 restore their persistent
@@ -237,6 +240,7 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * "radix_launches" histogram + pass kernels of the built-in radix sort enqueued so far, "sort_rank_atomic" 1 = the radix passes rank by LDS
  * atomics (the context's self-test found them served in lane order on this device), 0 = by ballots, -1 = no sort
  * has run yet; "shadow_key_bits" key bits the last ugrt_trace_shadow sorted its rays on (0 = no pass has sorted yet);
+ * "uniform_builds_reused" ugrt_grid_build_uniform calls so far that kept the grid the context held instead of building;
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and
  * returns the number of operands whose result differs from 1.0f / x (0), "f2i_mismatches" does the same for the device
  * forms of ugrt_f2i / ugrt_f2u / ugrt_floor2i against the portable ones of ugrt_fmath.h (0), "lane_reduce_mismatches"
@@ -258,7 +262,17 @@ int ugrt_grid_build_perspective(ugrt_ctx *ctx, const int *d_facelist, const floa
 /* FrustumGrid::buildSphericalGrid(int*, float*, float, float), frustum_grid.h:368 */
 int ugrt_grid_build_spherical(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces,
 			      float xM, float yM);
-/* uniform world-space grid for the reflection bounce (README.md:1; no reference code) */
+/* uniform world-space grid for the reflection bounce (README.md:1; no reference code).
+ * The grid depends on the triangles, the box and the context's uniform_dims only -- no camera, no light.  The call
+ * returns UGRT_OK without enqueuing or changing anything (counted by "uniform_builds_reused") when the grid the context
+ * holds is the one it would build: UGRT_FLAG_STATIC_GEOMETRY is set; d_facelist, d_vertlist, num_faces, the face window
+ * and the bits of bbmin / bbmax are those of the grid's last build; neither ugrt_animate nor ugrt_geometry_changed has
+ * been called since, and no grid build has met arrays the context had not seen; ugrt_grid_merge_shards has not
+ * rewritten the grid; no overflow of an asynchronous call is reported or under repair; and that last build waited
+ * for its counts.  A build in the asynchronous form ("async_build") is never kept, since one that overflowed its
+ * estimate leaves an emptied grid: the next build of the same inputs waits instead, and the calls after it keep that
+ * one.  Where the geometry changes every frame nothing waits that did not wait before.  Option "uniform_reuse" 0
+ * builds every time.  The arrays handed out by ugrt_grid_get_info are read-only for the caller either way. */
 int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces,
 			    const float bbmin[3], const float bbmax[3]);
 /* The grid's arrays.  The merged lists exist after this call: a build of the PERSPECTIVE grid that has wide

@@ -990,7 +990,9 @@ extern "C" int ugrt_grid_build_batch_end(ugrt_ctx *ctx)
 }
 
 // sizes/rng/wide list are filled, ny/nz give the key layout, [ylo, yhi] the y range of the cells a wide triangle covers
-static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, int ylo, int yhi)
+// (wait: the build waits and sizes exactly whatever the option says -- ugrt_grid_build_uniform, to confirm a grid it
+// is about to keep)
+static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, int ylo, int yhi, bool wait = false)
 {
 	int rc;
 	const int gi = (int)(&G - ctx->grid);
@@ -1000,7 +1002,7 @@ static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, in
 	}
 	// asynchronous when asked for, when this grid has been built before (an estimate exists), when no overflow is
 	// pending or being repaired, and when the wide list fits the rank kernel
-	const bool async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && G.have_est && G.est_w <= 3000u && ctx->cfg.slabs == 1 &&
+	const bool async = !wait && ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && G.have_est && G.est_w <= 3000u && ctx->cfg.slabs == 1 &&
 			   ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen && !ctx->overflow_repair;
 	if (!async) {
 		if (ugrt_reported_status(ctx) != 0u)
@@ -1008,6 +1010,7 @@ static int build_common(ugrt_ctx *ctx, Grid &G, int F, u32 C, int ny, int nz, in
 		G.async_pending = false;
 	}
 	G.valid = false;
+	G.waited = !async;
 	G.merge_pending = false; // (a merge nobody asked for is dropped with the grid it belonged to)
 	G.C = C;
 	G.F = F;
@@ -1058,6 +1061,7 @@ static int build_prologue(ugrt_ctx *ctx, Grid &G, const int *d_facelist, const f
 		return UGRT_OK;
 	}
 	ctx->rec_valid = false;
+	ctx->geom_gen++; // arrays the context does not know to stand: whatever was kept of the last ones goes
 	G.wide_zeroed = nullptr;
 	if ((rc = ugrt_buf_reserve(ctx, ctx->trirec, (size_t)F * 48)))
 		return rc;
@@ -1138,6 +1142,23 @@ extern "C" int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, con
 	if (!ctx || !bbmin || !bbmax)
 		return ugrt_fail(UGRT_EINVAL, "grid_build_uniform: null argument");
 	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	// The grid has no per-frame input: it depends on the triangles, the box and uniform_dims (fixed with the context)
+	// alone.  Where the caller vouches for the triangles (UGRT_FLAG_STATIC_GEOMETRY) and everything else is what the
+	// held grid was built from, the call enqueues nothing and touches nothing.
+	ugrt_ctx::UniformKept &K = ctx->ukept;
+	const bool same = K.have && (ctx->cfg.flags & UGRT_FLAG_STATIC_GEOMETRY) && K.faces == d_facelist && K.verts == d_vertlist &&
+			  K.F == F && K.gen == ctx->geom_gen && K.face_lo == ctx->face_lo && K.face_hi == ctx->face_hi &&
+			  memcmp(K.bb, bbmin, 12) == 0 && memcmp(K.bb + 3, bbmax, 12) == 0;
+	if (same && K.exact && G.valid && ctx->opt[UGRT_OPT_UNIFORM_REUSE] != 0 && ugrt_reported_status(ctx) == 0u &&
+	    !ctx->overflow_seen && !ctx->overflow_repair) {
+		ctx->uniform_reused++;
+		return UGRT_OK;
+	}
+	// An asynchronous build of these very inputs is held, and nobody has confirmed that it fitted its estimate (one that
+	// did not leaves an emptied grid): this build waits, and the next call keeps it.
+	const bool confirm = same && !K.exact && ctx->opt[UGRT_OPT_UNIFORM_REUSE] != 0;
+	K.have = false;
+	ctx->ubuild_id++;
 	int rc = build_prologue(ctx, G, d_facelist, d_vertlist, F, "grid_build_uniform");
 	if (rc)
 		return rc;
@@ -1162,8 +1183,19 @@ extern "C" int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, con
 			   wide_counter(G, F), ctx->face_lo, ctx->face_hi >= 0 ? ctx->face_hi : F);
 	ugrt_prof_end(ctx, UGRT_ST_BUILD_COUNT);
 	UGRT_HIP(hipGetLastError());
-	return build_common(ctx, G, F, (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2], g.dims[1], g.dims[2], 0,
-			    g.dims[1] - 1);
+	if ((rc = build_common(ctx, G, F, (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2], g.dims[1], g.dims[2], 0,
+			       g.dims[1] - 1, confirm)))
+		return rc;
+	// (a build of an open batch is finished by _end, which comes before anybody may use the grid or build it again;
+	// `gen` is taken behind the prologue, which counts arrays it had not seen)
+	K.faces = d_facelist, K.verts = d_vertlist, K.F = F;
+	K.face_lo = ctx->face_lo, K.face_hi = ctx->face_hi;
+	K.gen = ctx->geom_gen;
+	memcpy(K.bb, bbmin, 12);
+	memcpy(K.bb + 3, bbmax, 12);
+	K.exact = G.waited;
+	K.have = true;
+	return UGRT_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -1240,6 +1272,10 @@ extern "C" int ugrt_grid_merge_shards(ugrt_ctx *ctx, int which, int nparts, cons
 	if (!G.valid)
 		return ugrt_fail(UGRT_EINVAL, "grid_merge_shards: build this rank's shard first (it defines the cells)");
 	UGRT_HIP(hipSetDevice(ctx->device));
+	if (which == UGRT_GRID_UNIFORM) { // the grid's arrays are rewritten: no longer the build ugrt_grid_build_uniform could keep
+		ctx->ukept.have = false;
+		ctx->ubuild_id++;
+	}
 	hipStream_t st = ctx->stream;
 	const u32 C = G.C;
 	MergeParts mp;
@@ -1315,5 +1351,6 @@ extern "C" int ugrt_geometry_changed(ugrt_ctx *ctx)
 	if (!ctx)
 		return ugrt_fail(UGRT_EINVAL, "geometry_changed: null context");
 	ctx->rec_valid = false;
+	ctx->geom_gen++;
 	return UGRT_OK;
 }

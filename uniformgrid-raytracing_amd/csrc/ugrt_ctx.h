@@ -53,6 +53,7 @@ enum {
 	UGRT_OPT_SHADOW_SIEVE,     // "shadow_sieve": items a sieve wave of the exact shadow pass looks at (default 8; 0 / 1 = a wave per item)
 	UGRT_OPT_ANY_RPW,          // "any_rays_per_wave": rays per wave of ugrt_trace_dda_any (1..64; 0 = default)
 	UGRT_OPT_ANY_COOP,         // "any_coop": ugrt_trace_dda_any: list length from which a ray's cell is tested by the whole wave
+	UGRT_OPT_UNIFORM_REUSE,    // "uniform_reuse": 0 = ugrt_grid_build_uniform builds every time (default 1: the grid is kept while its inputs stand)
 	UGRT_OPT_COUNT
 };
 
@@ -90,6 +91,7 @@ struct Grid {
 	// asynchronous builds: what the grid needed last time (narrow references, wide triangles)
 	u32 est_rn = 0, est_w = 0;
 	bool have_est = false, async_pending = false, r_exact = true;
+	bool waited = false; // the last build of the grid read its counts back (build_common): they are exact, nothing overflowed
 	unsigned long long active_cells = 0;
 	u32 *keys = nullptr, *vals = nullptr; // sorted result (one of key[i]/val[i])
 	u32 R = 0, C = 0, cells_used = 0;
@@ -173,6 +175,27 @@ struct ugrt_ctx {
 	const int *rec_tris = nullptr;
 	int rec_faces = 0;
 	bool rec_valid = false;
+	// Geometry generation: bumped wherever the triangles may have changed -- ugrt_animate, ugrt_geometry_changed, and
+	// the branch of build_prologue that refreshes the records (no UGRT_FLAG_STATIC_GEOMETRY, or arrays it has not seen).
+	// (rec_valid cannot serve: after ugrt_animate the next build of ANY grid sets it again.)
+	unsigned long long geom_gen = 0;
+	// The inputs of the uniform grid the context holds (ugrt_grid_build_uniform keeps the grid while they stand).
+	// `have`: the held grid is a finished build of these inputs and nothing has written its arrays since;
+	// `exact`: that build waited, so its counts are known to be exact and complete (an asynchronous build may have
+	// overflowed its estimate and left an emptied grid: it is never reused, the next build of the same inputs waits).
+	struct UniformKept {
+		bool have = false, exact = false;
+		const int *faces = nullptr;
+		const float *verts = nullptr;
+		int F = 0, face_lo = 0, face_hi = -1;
+		unsigned long long gen = 0;
+		float bb[6] = { 0 };
+	} ukept;
+	unsigned long long uniform_reused = 0; // ugrt_grid_build_uniform calls that kept the grid ("uniform_builds_reused")
+	// every build of the uniform grid, and every merge into it, takes a new number; the bitmap carries the number (and
+	// the span array) it was made from
+	unsigned long long ubuild_id = 0, ubitmap_id = 0;
+	const u32 *ubitmap_span = nullptr;
 	DevBuf witems, wscan; // tracer work lists
 	DevBuf ubitmap;               // bounce: occupancy bitmap of the uniform grid's cells (1 bit per cell)
 	DevBuf dsort;                 // bounce, option dda_sort: keys + sorted keys + sorted list

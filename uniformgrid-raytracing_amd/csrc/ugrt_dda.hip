@@ -291,16 +291,28 @@ static inline size_t dda_list_cap(const ugrt_ctx *ctx)
 }
 
 // The one k_dda_prepare launch of ugrt_trace_dda and ugrt_trace_dda_any (ugrt_dda_any.hip): the band's defaults, the ray list
-// and its counter, and (with_bitmap: extra workgroups of the same launch) the occupancy bitmap of the grid's cells.
+// and its counter, and (with_bitmap: extra workgroups of the same launch, unless the bitmap the context holds is current)
+// the occupancy bitmap of the grid's cells.
 // d_hit_t null: the form of ugrt_trace_dda_any, whose `d_hit_id` is its occlusion flags.  chunk: the split walks' table, or null.
 int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
 		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out)
 {
 	int rc;
 	const u32 ncell_all = (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2];
+	const void *bitmap_was = ctx->ubitmap.p;
 	if ((rc = ugrt_buf_reserve(ctx, ctx->wscan, dda_list_cap(ctx) * 4)) ||
 	    (with_bitmap && (rc = ugrt_buf_reserve(ctx, ctx->ubitmap, ((size_t)ncell_all + 63) / 64 * 8 + 8))))
 		return rc;
+	// The bitmap is a function of the spans alone.  The one made from the context's own uniform grid carries the number
+	// of the build (or merge) that wrote those spans, and stands until the next one: the bounce and every any-hit walk
+	// of a frame, and the frames that keep the grid (ugrt_grid_build_uniform), share it.  Spans of the caller's own are
+	// not known to stand from call to call: their bitmap is written every time and carries no number.
+	const Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
+	const bool own = G.valid && d_span == (const u32 *)G.span.p;
+	if (with_bitmap && own && ctx->ubitmap_id == ctx->ubuild_id && ctx->ubitmap_span == d_span && ctx->ubitmap.p == bitmap_was)
+		with_bitmap = false; // current
+	if (with_bitmap)
+		ctx->ubitmap_id = 0ull; // (being rewritten; numbered again once the launch is enqueued)
 	// (two ray counters in turn: a launch's prepare kernel clears the other one for the launch that follows -- no fill)
 	// (the turn is taken at the launch: a call that fails before leaves both as they were)
 	const u32 turn = ctx->dda_turn ^ 1u;
@@ -313,6 +325,8 @@ int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *
 			   ctx->d_small + UGRT_DSMALL_TICKET, pix_blocks, d_span, ncell_all, (u32 *)ctx->ubitmap.p, chunk, dcount_next);
 	ctx->dda_turn = turn;
 	UGRT_HIP(hipGetLastError());
+	if (with_bitmap && own)
+		ctx->ubitmap_id = ctx->ubuild_id, ctx->ubitmap_span = d_span;
 	*list_out = (u32 *)ctx->wscan.p;
 	*dcount_out = dcount;
 	return UGRT_OK;

@@ -107,6 +107,10 @@ class Context:
         check(lib.ugrt_grid_build_spherical(self._h, _ptr(d_faces), _ptr(d_verts), num_faces, xM, yM))
 
     def grid_build_uniform(self, d_faces, d_verts, num_faces, bbmin, bbmax):
+        """The uniform grid of the bounce.  With FLAG_STATIC_GEOMETRY the call enqueues nothing while the grid the
+        context holds was built from the same tensors, box and face window and the geometry has not changed since
+        (rotate_bunny / geometry_changed); get_state("uniform_builds_reused") counts such calls, option
+        "uniform_reuse" 0 builds every time (ugrt.h: ugrt_grid_build_uniform)."""
         check(lib.ugrt_grid_build_uniform(self._h, _ptr(d_faces), _ptr(d_verts), num_faces, _f3(bbmin), _f3(bbmax)))
 
     def grid_build_batch_begin(self):
@@ -152,12 +156,14 @@ class Context:
                 self.wrap_u32(gi.d_span, gi.num_cells), self.wrap_u32(gi.d_offset, gi.num_cells), gi)
 
     def set_option(self, key, value):
-        """Launch-shape options (no effect on results), e.g. "dda_rays_per_wave"."""
+        """Launch-shape options (no effect on results), e.g. "dda_rays_per_wave"; "uniform_reuse" 0 makes
+        grid_build_uniform build every time."""
         check(lib.ugrt_ctx_set_option(self._h, key.encode(), int(value)))
 
     def get_state(self, key):
         """Counters and findings of the context: "radix_launches", "sort_rank_atomic", "shadow_key_bits" (key bits the
-        last shadow pass sorted its rays on), "primary_deferred_merges" / "primary_completed_merges" /
+        last shadow pass sorted its rays on), "uniform_builds_reused" (grid_build_uniform calls that kept the grid the
+        context held), "primary_deferred_merges" / "primary_completed_merges" /
         "primary_merge_pending" (screen-grid builds that put their merge off, those merged later after all, one pending), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
         on the device), "f2i_mismatches" (the same for the device's float -> integer conversions), "lane_reduce_mismatches"
         (the tracers' DPP / permlane-swap reductions against __shfl_xor)."""
@@ -166,7 +172,8 @@ class Context:
         return int(v.value)
 
     def geometry_changed(self):
-        """With FLAG_STATIC_GEOMETRY: the vertex or face array was rewritten outside ugrt_animate."""
+        """With FLAG_STATIC_GEOMETRY: the vertex or face array was rewritten outside ugrt_animate (the triangle
+        records and the uniform grid kept from the old contents are built again)."""
         check(lib.ugrt_geometry_changed(self._h))
 
     def sort_pairs(self, keys_in, keys_out, values_in, values_out, key_bits, library=False):
