@@ -709,6 +709,42 @@ int ugrt_filter_visibility(ugrt_ctx *ctx, const unsigned *d_mask, int num_bits, 
  * null argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_samples);
 
+/* ---- device: ambient occlusion over interleaved direction sets ----
+ * Section 6.8's two means for the hemisphere rays of section 6.5: neighbouring pixels walk along different sets of local
+ * directions, and ugrt_filter_visibility, fed with the hemisphere masks, averages them over pixels of the same surface.
+ * Per frame: ugrt_trace_dda_any_hemi_sets in the place of ugrt_trace_dda_any_hemi, ugrt_filter_visibility +
+ * ugrt_ao_shade_vis in the place of ugrt_shade_ao.  All arithmetic is fp32 without contraction or unsigned 32-bit
+ * integer. */
+#define UGRT_MAX_AO_SET_TILE 4   /* set_w, set_h */
+#define UGRT_MAX_AO_SET_DIRS 512 /* set_w * set_h * num_dirs */
+/* ugrt_trace_dda_any_hemi with one set of directions per pixel of a set_w x set_h tile, in ugrt_trace_dda_any_area's
+ * index space: pixel p of the band has the full-image coordinates x = p % width, y = p / width and the set
+ * k(p) = (y % set_h) * set_w + (x % set_w); for an active pixel bit s of d_mask[p] is exactly what
+ * ugrt_trace_dda_any(..., t_max = radius) writes for the ray {o, D}, o = floats 0..2 and n = floats 3..5 of
+ * d_orays[6 * p], D = ugrt_trace_dda_any_hemi's D_s formed from the local direction d_dirs[3 * (k(p) * num_dirs + s) ..]
+ * with the same basis rule and the same operation order.  d_dirs is DEVICE memory, [set_w * set_h][num_dirs][3] floats
+ * (local directions, z along the normal); every workgroup copies it to LDS once.  Bits >= num_dirs are 0, inactive
+ * pixels of the band get 0, pixels outside the band are not written.  The index space is (pixel group, direction): the
+ * num_dirs rays of a pixel sit in neighbouring lanes of one wave, which writes the pixel's word whole, with one store and
+ * no atomic operation.  One prepare launch and one ray list serve the call; it clears the band's words.  Options
+ * "any_rays_per_wave" (the lanes of a wave that are given rays; unset: 64), "any_coop" and "dda_blocks" shape the launch
+ * and change no result.  Stages UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of
+ * ugrt_trace_dda and what ugrt_reflect_rays_next told it alone.  With set_w = set_h = 1 the words are
+ * ugrt_trace_dda_any_hemi's for the same directions.  There is no see-through form (glass does enclose).  num_dirs
+ * outside 1..UGRT_MAX_AO_DIRS, set_w or set_h outside 1..UGRT_MAX_AO_SET_TILE, set_w * set_h * num_dirs >
+ * UGRT_MAX_AO_SET_DIRS, radius <= 0 or NaN, or a null argument: UGRT_EINVAL (the message names the argument) and nothing
+ * is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_trace_dda_any_hemi_sets(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+				 const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+				 const float *d_orays, const int *d_oactive, int num_dirs, int set_w, int set_h,
+				 const float *d_dirs, float radius, unsigned *d_mask);
+/* The image scaled by the gathered share of open hemisphere rays, for the context's band: with num = d_vis[2p] and
+ * den = d_vis[2p + 1] != 0 (what ugrt_filter_visibility wrote for the hemisphere masks) each of the pixel's three bytes
+ * b becomes (b * num) / (num_dirs * den) in unsigned 32-bit integers (the largest product is 255 * 32 * 6561); den = 0
+ * leaves the pixel as it is.  Behind a gather of radius 0 the bytes are ugrt_shade_ao's.  Stage UGRT_ST_SHADE.  num_dirs
+ * outside 1..UGRT_MAX_AO_DIRS or a null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_ao_shade_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_dirs);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

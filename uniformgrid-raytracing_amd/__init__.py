@@ -60,6 +60,8 @@ MAX_AREA_SAMPLES = 32  # UGRT_MAX_AREA_SAMPLES
 MAX_AREA_SET_TILE = 4  # UGRT_MAX_AREA_SET_TILE
 MAX_AREA_SET_POINTS = 512  # UGRT_MAX_AREA_SET_POINTS
 MAX_FILTER_RADIUS = 8  # UGRT_MAX_FILTER_RADIUS
+MAX_AO_SET_TILE = 4  # UGRT_MAX_AO_SET_TILE
+MAX_AO_SET_DIRS = 512  # UGRT_MAX_AO_SET_DIRS
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -185,6 +187,8 @@ PROTOTYPES = {
     "ugrt_trace_dda_any_area_sets_thru": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int]),
     "ugrt_filter_visibility": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_float, C.c_float, _P]),
     "ugrt_shade_area_vis": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ugrt_trace_dda_any_hemi_sets": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P]),
+    "ugrt_ao_shade_vis": (C.c_int, [_P, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

@@ -23,6 +23,8 @@
 // rays of a pixel towards S points of a light's disk in neighbouring lanes of one wave, one mask word per pixel.
 // ugrt_trace_dda_any_area_sets and its _thru form are that walk with one sample set per pixel of a
 // set_w x set_h tile of the image: the sets lie in device memory, a workgroup copies them to LDS once.
+// ugrt_trace_dda_any_hemi_sets is the hemisphere walk in that index space: the S directions of a
+// pixel in neighbouring lanes, one set of local directions per pixel of the tile, the word stored whole from one ballot.
 #include "ugrt_dda.h"
 #include <type_traits>
 
@@ -92,7 +94,22 @@ struct AnyAreaSets {
 	};
 	static constexpr bool lights = false, hemi = false, area = true, sets = true;
 };
-// (dynamic LDS, its base 16-byte aligned; AnyAreaSets is the only aim that has any)
+// AnyHemiSets: AnyHemi in AnyAreaSets' index space (ugrt_trace_dda_any_hemi_sets): pixel p walks
+// along set k(p) of `pos`, device memory [set_w * set_h][S][3] LOCAL directions, up to `radius`.  The fields AnyAreaSets
+// has carry its names: the table's copy, k(p), the lane mapping and the ballot store are its code.  A lane reads the
+// pixel's normal and its three local floats from LDS, and d_hemi_dir forms the world direction per lane: the S lanes of
+// a pixel repeat the basis, which is dead before the first cell (no register of the walk) and needs no lane exchange.
+struct AnyHemiSets {
+	struct Arg {
+		const float *pos;
+		int count;          // S
+		u32 set_w, set_h;   // 1..4 each
+		u32 width;          // of the full image
+		float radius;
+	};
+	static constexpr bool lights = false, hemi = true, area = true, sets = true;
+};
+// (dynamic LDS, its base 16-byte aligned; the aims over sets are the only ones that have any)
 extern __shared__ __attribute__((aligned(16))) float s_sets_pos[];
 // Which slot of its group (pix) and which sample (smp) a lane serves: lane / S and lane % S, the quotient by a
 // multiplication that is exact for lane < 64 and S <= 32.  They are formed again where they are used, before and behind
@@ -175,7 +192,7 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 {
 	const int lane = threadIdx.x;
 	const u32 count = *count_p;
-	constexpr bool layered = Aim::lights || Aim::hemi; // the index space is (light or direction, ray group)
+	constexpr bool layered = Aim::lights || (Aim::hemi && !Aim::area); // the index space is (light or direction, ray group)
 	float t_max;
 	if constexpr (Aim::lights)
 		t_max = 1.0f;
@@ -248,14 +265,17 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 				o[k] = rays[p * 6 + k];
 				if constexpr (Aim::lights)
 					d[k] = aim.pos[3u * light + (u32)k] - o[k];
-				else if constexpr (Aim::sets)
+				else if constexpr (Aim::sets && !Aim::hemi)
 					d[k] = s_sets_pos[3u * asmp + (u32)k] - o[k];
-				else if constexpr (Aim::area)
+				else if constexpr (Aim::area && !Aim::hemi)
 					d[k] = d_area_lds()[3u * asmp + (u32)k] - o[k];
 				else
 					d[k] = rays[p * 6 + 3 + k];
 			}
-			if constexpr (Aim::hemi) {
+			if constexpr (Aim::hemi && Aim::sets) { // (d is the normal; the local direction is the lane's own)
+				const float nrm[3] = { d[0], d[1], d[2] };
+				d_hemi_dir(nrm, s_sets_pos[3u * asmp], s_sets_pos[3u * asmp + 1u], s_sets_pos[3u * asmp + 2u], d);
+			} else if constexpr (Aim::hemi) {
 				const float nrm[3] = { d[0], d[1], d[2] };
 				d_hemi_dir(nrm, aim.dirs[3u * light], aim.dirs[3u * light + 1u], aim.dirs[3u * light + 2u], d);
 			}
@@ -394,11 +414,12 @@ static int any_null_check(const AnyCall &c, const void *own = "")
 }
 
 // The prepare launch and the kernel for one aim.  What differs between the aims is read from the aim's flags:
-//   * the layers of the index space: AnyLights and AnyHemi walk (light or direction, ray group), aim.count layers;
+//   * the layers of the index space: AnyLights and AnyHemi walk (light or direction, ray group), aim.count layers
+//     (AnyHemiSets is an area aim: one layer);
 //   * the group: "any_rays_per_wave" rays (unset: 32); the area aims give L = "any_rays_per_wave" of a wave's lanes
 //     (at most and unset: all 64) rays, PPW = max(1, L / S) pixels' S samples each, and the kernel's RPW carries PPW;
-//   * dynamic LDS: AnyAreaSets' table, rounded up to the 16 bytes of the copy's float4 stores (at most 6 KB);
-//   * AnyLights' layers behind the first are cleared here; AnyHemi has no see-through kernel.
+//   * dynamic LDS: the table of the aims over sets, rounded up to the 16 bytes of the copy's float4 stores (at most 6 KB);
+//   * AnyLights' layers behind the first are cleared here; the hemisphere aims have no see-through kernel.
 template <class Aim> static int any_walk(const AnyCall &c, const typename Aim::Arg &aim)
 {
 	ugrt_ctx *ctx = c.ctx;
@@ -416,7 +437,7 @@ template <class Aim> static int any_walk(const AnyCall &c, const typename Aim::A
 		const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
 		RPW = L / (u32)aim.count > 0u ? L / (u32)aim.count : 1u;
 	}
-	if constexpr (Aim::lights || Aim::hemi)
+	if constexpr (Aim::lights || (Aim::hemi && !Aim::area))
 		layers = (u32)aim.count;
 	if constexpr (Aim::sets)
 		lds = ((size_t)12 * (size_t)(aim.set_w * aim.set_h * (u32)aim.count) + 15u) & ~(size_t)15u;
@@ -540,6 +561,31 @@ static int trace_dda_any_area_sets(const AnyCall &c, int num_samples, int set_w,
 	return any_walk<AnyAreaSets>(c, area);
 }
 
+static int trace_dda_any_hemi_sets(const AnyCall &c, int num_dirs, int set_w, int set_h, const float *d_dirs, float radius)
+{
+	if (int rc = any_null_check(c, d_dirs))
+		return rc;
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "%s: num_dirs %d is not in 1..%d", c.who, num_dirs, UGRT_MAX_AO_DIRS);
+	if (set_w < 1 || set_w > UGRT_MAX_AO_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w %d is not in 1..%d", c.who, set_w, UGRT_MAX_AO_SET_TILE);
+	if (set_h < 1 || set_h > UGRT_MAX_AO_SET_TILE)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_h %d is not in 1..%d", c.who, set_h, UGRT_MAX_AO_SET_TILE);
+	if (set_w * set_h * num_dirs > UGRT_MAX_AO_SET_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "%s: set_w * set_h * num_dirs = %d is more than %d", c.who, set_w * set_h * num_dirs,
+				 UGRT_MAX_AO_SET_DIRS);
+	if (!(radius > 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "%s: radius must be greater than 0", c.who);
+	AnyHemiSets::Arg hemi = {};
+	hemi.pos = d_dirs;
+	hemi.count = num_dirs;
+	hemi.set_w = (u32)set_w;
+	hemi.set_h = (u32)set_h;
+	hemi.width = (u32)c.ctx->cfg.width;
+	hemi.radius = radius;
+	return any_walk<AnyHemiSets>(c, hemi);
+}
+
 extern "C" int ugrt_trace_dda_any(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
 				  const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
 				  const float *d_rays, const int *d_active, float t_max, int *d_occluded)
@@ -632,5 +678,15 @@ extern "C" int ugrt_trace_dda_any_area_sets_thru(ugrt_ctx *ctx, const unsigned *
 	return trace_dda_any_area_sets({ ctx, "trace_dda_any_area_sets_thru", d_value_list, d_span, d_offset, d_vertlist,
 					 d_trilist, d_orays, d_oactive, (int *)d_mask, &thru },
 				       num_samples, set_w, set_h, d_sample_pos);
+}
+
+extern "C" int ugrt_trace_dda_any_hemi_sets(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
+					    const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
+					    const float *d_orays, const int *d_oactive, int num_dirs, int set_w, int set_h,
+					    const float *d_dirs, float radius, unsigned *d_mask)
+{
+	return trace_dda_any_hemi_sets({ ctx, "trace_dda_any_hemi_sets", d_value_list, d_span, d_offset, d_vertlist, d_trilist,
+					 d_orays, d_oactive, (int *)d_mask, nullptr },
+				       num_dirs, set_w, set_h, d_dirs, radius);
 }
 

@@ -488,6 +488,29 @@ extern "C" int ugrt_shade_area_vis(ugrt_ctx *ctx, unsigned char *d_img, const un
 	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_area_vis, d_img, d_vis, (u32)num_samples);
 }
 
+// the pass in the place of k_shade_ao behind the gather over the hemisphere masks: num / den is the
+// gathered share of open rays
+__global__ __launch_bounds__(PX_THREADS) void k_shade_ao_vis(unsigned char *__restrict__ d_img, const u32 *__restrict__ vis,
+							      u32 num_dirs, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t pixelID = (size_t)(p0 + i);
+	const u32 num = vis[2 * pixelID], den = vis[2 * pixelID + 1];
+	if (den != 0u)
+		d_scale_bytes(d_img, pixelID, num, num_dirs * den);
+}
+
+extern "C" int ugrt_ao_shade_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_dirs)
+{
+	if (!ctx || !d_img || !d_vis)
+		return ugrt_fail(UGRT_EINVAL, "ao_shade_vis: null argument");
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "ao_shade_vis: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_ao_vis, d_img, d_vis, (u32)num_dirs);
+}
+
 // ---------------------------------------------------------------------------
 // several lights (the reference's loop over h_numLights, main.cu:148-203, runs with one and
 // its shading kernels index light 0): k_shade<false> and k_add_shadows once per light and the mean of the bytes, in

@@ -441,6 +441,20 @@ class Context:
         """Each byte b of a pixel with den = vis[2p + 1] != 0 becomes (b * (S * den + 2 * vis[2p])) // (3 * S * den)."""
         check(lib.ugrt_shade_area_vis(self._h, _ptr(img), _ptr(vis), int(num_samples)))
 
+    # -- ambient occlusion over interleaved direction sets (DESIGN.md section 6.9)
+    def trace_dda_any_hemi_sets(self, value, span, offset, verts, faces, orays, oactive, num_dirs, set_w, set_h, dirs,
+                                radius, mask):
+        """trace_dda_any_hemi with a set of directions per pixel of a set_w x set_h tile, the rays of a pixel side by side
+        in a wave: pixel (x, y) of the full image walks along set (y % set_h) * set_w + x % set_w of dirs, a DEVICE tensor
+        of floats [set_w * set_h, num_dirs, 3] (scenes.ao_direction_sets, uploaded), z along the normal."""
+        check(lib.ugrt_trace_dda_any_hemi_sets(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                               _ptr(orays), _ptr(oactive), int(num_dirs), int(set_w), int(set_h),
+                                               _ptr(dirs), radius, _ptr(mask)))
+
+    def shade_ao_vis(self, img, vis, num_dirs):
+        """Each byte b of a pixel with den = vis[2p + 1] != 0 becomes (b * vis[2p]) // (num_dirs * den)."""
+        check(lib.ugrt_ao_shade_vis(self._h, _ptr(img), _ptr(vis), int(num_dirs)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

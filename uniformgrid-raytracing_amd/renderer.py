@@ -27,7 +27,8 @@ materials.  With ``area=S`` the one-stream single-light 
 per primary hit towards a disk around the light through the uniform grid in the place of the light-space shadow stage,
 and a last pass that darkens the image by the share of occluded samples; with ``area_sets``
 the pixels of a tile aim at different sets of S points, and with ``area_filter`` a gather over the pixels of the same
-surface averages their shares before that pass.
+surface averages their shares before that pass; ``ao_sets`` and ``ao_filter`` do the same for the
+hemisphere rays of ``ao``, in a walk that keeps a pixel's rays side by side in a wave.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -168,6 +169,28 @@ def default_filter_plane(bbmin, bbmax):
     return float(np.float32(0.01 * float((np.asarray(bbmax, np.float32) - np.asarray(bbmin, np.float32)).max())))
 
 
+def _check_sets_filter(name, needs, on, sets, radius, cos, plane):
+    """check_area_filter and check_ao_filter: the keywords <name>_sets, <name>_filter, <name>_filter_cos and
+    <name>_filter_plane of a frame whose `name` keyword is `on`."""
+    if isinstance(sets, (bool, np.bool_)) or not isinstance(sets, (int, np.integer)) or int(sets) not in AREA_SET_TILES:
+        raise ValueError("%s_sets must be 1, 4 or 16, not %r" % (name, sets))
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) \
+            or not 0 <= radius <= MAX_FILTER_RADIUS:
+        raise ValueError("%s_filter must be an integer in 0..%d, not %r" % (name, MAX_FILTER_RADIUS, radius))
+    if not on and (sets != 1 or radius != 0):
+        raise ValueError("%s_sets and %s_filter need %s > 0: they shape %s" % (name, name, name, needs))
+    if not radius:
+        return int(sets), 0, None, None
+    number = (int, float, np.integer, np.floating)
+    if isinstance(cos, (bool, np.bool_)) or not isinstance(cos, number) or np.isnan(np.float32(cos)):
+        raise ValueError("%s_filter_cos must be a number, not %r" % (name, cos))
+    if plane is not None:
+        if isinstance(plane, (bool, np.bool_)) or not isinstance(plane, number) or not float(np.float32(plane)) >= 0.0:
+            raise ValueError("%s_filter_plane must be None or a number not below 0, not %r" % (name, plane))
+        plane = float(np.float32(plane))
+    return int(sets), int(radius), float(np.float32(cos)), plane
+
+
 def check_area_filter(area, area_sets=1, area_filter=0, area_filter_cos=0.9, area_filter_plane=None):
     """The interleaved sample sets and the gather of an area light, checked in check_area's
     manner behind it (area: what check_area returned).  area_sets: 1, 4 or 16 (tiles of 1 x 1, 2 x 2, 4 x 4 pixels);
@@ -175,25 +198,16 @@ def check_area_filter(area, area_sets=1, area_filter=0, area_filter_cos=0.9, are
     area > 0.  area_filter_cos: a number (no NaN); area_filter_plane: None (default_filter_plane) or a number >= 0; the
     two are looked at with area_filter > 0 only.  ValueError before anything is enqueued.  Returns
     (area_sets, area_filter, cos or None, plane or None)."""
-    if isinstance(area_sets, (bool, np.bool_)) or not isinstance(area_sets, (int, np.integer)) or int(area_sets) not in AREA_SET_TILES:
-        raise ValueError("area_sets must be 1, 4 or 16, not %r" % (area_sets,))
-    if isinstance(area_filter, (bool, np.bool_)) or not isinstance(area_filter, (int, np.integer)) \
-            or not 0 <= area_filter <= MAX_FILTER_RADIUS:
-        raise ValueError("area_filter must be an integer in 0..%d, not %r" % (MAX_FILTER_RADIUS, area_filter))
-    if not area and (area_sets != 1 or area_filter != 0):
-        raise ValueError("area_sets and area_filter need area > 0: they shape the area light's samples and penumbra")
-    if not area_filter:
-        return int(area_sets), 0, None, None
-    number = (int, float, np.integer, np.floating)
-    if isinstance(area_filter_cos, (bool, np.bool_)) or not isinstance(area_filter_cos, number) \
-            or np.isnan(np.float32(area_filter_cos)):
-        raise ValueError("area_filter_cos must be a number, not %r" % (area_filter_cos,))
-    if area_filter_plane is not None:
-        if isinstance(area_filter_plane, (bool, np.bool_)) or not isinstance(area_filter_plane, number) \
-                or not float(np.float32(area_filter_plane)) >= 0.0:
-            raise ValueError("area_filter_plane must be None or a number not below 0, not %r" % (area_filter_plane,))
-        area_filter_plane = float(np.float32(area_filter_plane))
-    return int(area_sets), int(area_filter), float(np.float32(area_filter_cos)), area_filter_plane
+    return _check_sets_filter("area", "the area light's samples and penumbra", area, area_sets, area_filter, area_filter_cos,
+                              area_filter_plane)
+
+
+def check_ao_filter(ao, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None):
+    """The interleaved direction sets and the gather of ambient occlusion: check_area_filter's
+    rules for ao_sets, ao_filter, ao_filter_cos and ao_filter_plane, behind check_ao (ao: what check_ao returned).
+    Returns (ao_sets, ao_filter, cos or None, plane or None)."""
+    return _check_sets_filter("ao", "the hemisphere's rays and their shading", ao, ao_sets, ao_filter, ao_filter_cos,
+                              ao_filter_plane)
 
 
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
@@ -345,13 +359,29 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
                     f.occlusion_rays, f.occlusion_active, shadow_lights, f.occluded_lights[j])
 
 
-def ao_pass(c, f, cam_pos, dirs, radius):
+def ao_pass(c, f, cam_pos, dirs, radius, sets=None):
     """Ambient occlusion's rays and walk: {origin, normal} of every primary hit, then the any-hit
-    walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  Runs behind the
-    uniform grid's build and before the shading call that rewrites the ids."""
+    walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  sets
+    ((table, (set_w, set_h), gather)) with a table: the device table of a direction set per pixel
+    of the tile, and the walk is the pixel-major one over direction sets.  Runs behind the uniform grid's build and before
+    the shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
-    c.trace_dda_any_hemi(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, dirs, radius, f.ao_mask)
+    if sets is not None and sets[0] is not None:
+        c.trace_dda_any_hemi_sets(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, len(dirs), sets[1][0],
+                                  sets[1][1], sets[0], radius, f.ao_mask)
+    else:
+        c.trace_dda_any_hemi(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, dirs, radius, f.ao_mask)
+
+
+def ao_shade(c, f, dirs, radius, sets=None):
+    """Ambient occlusion's last pass over the image (ao_pass' arguments): shade_ao, or with a gather ((radius, cos, plane),
+    DESIGN.md section 6.9) filter_visibility over f.ao_mask into f.ao_vis and shade_ao_vis."""
+    if sets is not None and sets[2] is not None:
+        c.filter_visibility(f.ao_mask, len(dirs), f.ao_rays, f.ao_active, sets[2][0], sets[2][1], sets[2][2], f.ao_vis)
+        c.shade_ao_vis(f.image, f.ao_vis, len(dirs))
+    else:
+        c.shade_ao(f.image, f.ao_mask, len(dirs))
 
 
 def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
@@ -472,6 +502,9 @@ class _Frame:
         # area_filter: the gather's two sums per pixel (_ensure_area_filter_buffers); area_sets: the uploaded tables
         self.area_vis = None
         self._area_set_tables = {}
+        # ao_filter: the gather's two sums per pixel (_ensure_ao_filter_buffers); ao_sets: the uploaded tables (_ao_stage)
+        self.ao_vis = None
+        self._ao_set_tables = {}
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -687,7 +720,8 @@ class Renderer(_Frame, _Band):
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
                 reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1,
-                area_filter=0, area_filter_cos=0.9, area_filter_plane=None):
+                area_filter=0, area_filter_cos=0.9, area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9,
+                ao_filter_plane=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -714,7 +748,11 @@ class Renderer(_Frame, _Band):
         points (scenes.area_sample_sets; the table is uploaded once per (area, area_sets, area_radius, light)).
         area_filter (needs area > 0; 0: off): a gather of radius 1..8 over the pixels of the same surface -- normals within
         area_filter_cos, planes within area_filter_plane (None: 1 % of the scene's largest extent) -- averages the masks
-        before the penumbra is shaded; area_vis holds its sums."""
+        before the penumbra is shaded; area_vis holds its sums.
+        ao_sets (needs ao > 0; 1, 4 or 16): the pixels of a 1 x 1, 2 x 2 or 4 x 4 tile walk along different sets of `ao`
+        directions (scenes.ao_direction_sets; the table is uploaded once per (ao, ao_sets)) in the pixel-major walk.
+        ao_filter (needs ao > 0; 0: off): area_filter's gather, with ao_filter_cos and ao_filter_plane, over ao_mask
+        before the image is scaled; ao_vis holds its sums."""
         area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
         area_sets, area_filter, area_filter_cos, area_filter_plane = check_area_filter(area, area_sets, area_filter,
                                                                                        area_filter_cos, area_filter_plane)
@@ -723,14 +761,15 @@ class Renderer(_Frame, _Band):
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
         ao, ao_radius = check_ao(ao, ao_radius, self.aux is not None)
+        ao_more = check_ao_filter(ao, ao_sets, ao_filter, ao_filter_cos, ao_filter_plane)
         if reflect_lights:
             lights = check_lights(setup.lights, reflect, self.aux is not None, True)
             return self._display_reflect_lights(setup, lights, shadows, shade, bounces, reflect_shadows,
-                                                self._ao_stage(ao, ao_radius, shade))
+                                                self._ao_stage(ao, ao_radius, shade, ao_more))
         if getattr(setup, "lights", None) is not None:
             lights = check_lights(setup.lights, reflect, self.aux is not None)
-            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade))
-        ao = self._ao_stage(ao, ao_radius, shade)
+            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more))
+        ao = self._ao_stage(ao, ao_radius, shade, ao_more)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
@@ -773,12 +812,40 @@ class Renderer(_Frame, _Band):
         elif area:
             ctx.shade_area(self.image, self.area_mask, area)
         if ao:
-            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
+            ao_shade(ctx, self, *ao)
 
-    def _ao_stage(self, ao, ao_radius, shade):
-        """(directions, radius) for ao_pass and shade_ao, with the buffers in place; None: the frame has no ambient
-        occlusion (ao == 0, or nothing is shaded)."""
-        return (self._ensure_ao_buffers(ao), ao_radius) if ao and shade else None
+    def _ao_stage(self, ao, ao_radius, shade, sets=(1, 0, None, None)):
+        """(directions, radius) for ao_pass and ao_shade, with the buffers in place; None: the frame has no ambient
+        occlusion (ao == 0, or nothing is shaded).  sets (what check_ao_filter returned) away from the defaults: a third
+        entry (table, (set_w, set_h), gather) -- the device table of scenes.ao_direction_sets, uploaded once per
+        (ao, ao_sets) and kept, or None with ao_sets = 1; the gather's (radius, cos, plane), with ao_vis in place, or None
+        without one."""
+        if not (ao and shade):
+            return None
+        ao_sets, ao_filter, ao_filter_cos, ao_filter_plane = sets
+        stage = (self._ensure_ao_buffers(ao), ao_radius)
+        if ao_sets == 1 and not ao_filter:
+            return stage
+        table = gather = None
+        if ao_sets > 1:
+            if (ao, ao_sets) not in self._ao_set_tables:
+                from .scenes import ao_direction_sets
+
+                self._ao_set_tables[(ao, ao_sets)] = self._upload_ao_sets(ao_direction_sets(ao, ao_sets))
+            table = self._ao_set_tables[(ao, ao_sets)]
+        if ao_filter:
+            self._ensure_ao_filter_buffers()
+            plane = default_filter_plane(self.bbmin, self.bbmax) if ao_filter_plane is None else ao_filter_plane
+            gather = (ao_filter, ao_filter_cos, plane)
+        return stage + ((table, AREA_SET_TILES[ao_sets], gather),)
+
+    def _upload_ao_sets(self, table):
+        return self.ctx.upload(table.reshape(-1))
+
+    def _ensure_ao_filter_buffers(self):
+        """ao_vis [2 W*H] (uint32 words in an int32 tensor), allocated on first use."""
+        if self.ao_vis is None:
+            self.ao_vis = self.torch.zeros(2 * self.N, dtype=self.torch.int32, device=self.image.device)
 
     def _area_stage(self, area, area_radius, setup):
         """The sample points for area_pass, with the buffers in place: the disk of area_radius around the light camera's
@@ -830,7 +897,7 @@ class Renderer(_Frame, _Band):
             ao_pass(ctx, self, self.cam_pos, *ao)
         shade_lights(ctx, self, self.cam_pos, lights, shadows)
         if ao:
-            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
+            ao_shade(ctx, self, *ao)
 
     def _display_reflect_lights(self, setup, lights, shadows, shade, bounces, reflect_shadows, ao=None):
         """_display_lights' camera pass and per-light shadow stages, then the reflection levels once (the uniform grid and
@@ -864,7 +931,7 @@ class Renderer(_Frame, _Band):
             ao_pass(ctx, self, self.cam_pos, *ao)
         shade_reflect_lights(ctx, self, self.cam_pos, lights, bounces, shadows, reflect_shadows)
         if ao:
-            ctx.shade_ao(self.image, self.ao_mask, len(ao[0]))
+            ao_shade(ctx, self, *ao)
 
     def _display_overlapped(self, setup, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
         """display() on two streams.  Side stream (second context, driven by the helper thread): light grid,
@@ -1053,9 +1120,10 @@ class BandedRenderer(_Frame):
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
                 ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
-                area_filter_plane=None):
+                area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None):
         check_area(area, area_radius, shadows, getattr(setup, "lights", None), True)  # raises with area > 0, as ao does
         check_area_filter(0, area_sets, area_filter, area_filter_cos, area_filter_plane)  # raises unless at the defaults
+        check_ao_filter(0, ao_sets, ao_filter, ao_filter_cos, ao_filter_plane)  # the same
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)

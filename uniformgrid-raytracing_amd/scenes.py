@@ -424,6 +424,24 @@ def ao_directions(S):
 AREA_SET_RANK = {1: (0,), 4: (0, 2, 3, 1), 16: (0, 8, 2, 10, 12, 4, 14, 6, 3, 11, 1, 9, 15, 7, 13, 5)}  # 4 x 4: Bayer
 
 
+def _spiral_directions(S, turn):
+    """ao_directions' directions with `turn` added to every angle."""
+    s = np.arange(int(S), dtype=np.float64)
+    r = np.sqrt((s + 0.5) / float(S))
+    phi = s * (np.pi * (3.0 - np.sqrt(5.0))) + turn
+    return np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - r * r)], 1).astype(np.float32)
+
+
+def ao_direction_sets(S, sets):
+    """The interleaved direction sets of the ambient-occlusion hemisphere: sets = 1, 4 or 16 for a
+    tile of 1 x 1, 2 x 2 or 4 x 4 pixels; set k (row-major in the tile) is ao_directions' formula with
+    phi = s * pi * (3 - sqrt(5)) + 2 pi * rank[k] / sets, rank = AREA_SET_RANK[sets], as area_sample_sets turns the disk.
+    Computed in float64 and returned as float32 [sets, S, 3]; set 0 is ao_directions bit for bit."""
+    if sets not in AREA_SET_RANK:
+        raise ValueError("sets must be 1, 4 or 16, not %r" % (sets,))
+    return np.stack([_spiral_directions(S, 2.0 * np.pi * rank / float(sets)) for rank in AREA_SET_RANK[sets]])
+
+
 def _disk_points(S, centre, axis, radius, turn):
     """area_samples' points with `turn` added to every angle."""
     c = np.asarray(centre, np.float64).reshape(3)
