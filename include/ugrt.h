@@ -220,6 +220,7 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * (see there); "dda_blocks", "primary_waves",
  * "any_rays_per_wave", "any_coop": ugrt_trace_dda_any (see there);
  * "uniform_reuse" 0 = ugrt_grid_build_uniform builds every time (default 1: it keeps the grid while its inputs stand, see there);
+ * "light_reuse" 0 = ugrt_grid_build_spherical builds every time (default 1: it keeps the grid while the light and the geometry stand, see there);
  * "shadow_waves": number of persistent single-wave workgroups of the bounce, the primary tracer and the two
  * shadow kernels (the primary tracer and the exact shadow pass run one wave per work item by default, "primary_xcd_run" /
  * "shadow_xcd_run" neighbouring items per XCD in turn; "primary_waves" set / "shadow_xcd_run" 0 restore their persistent
@@ -241,6 +242,7 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * atomics (the context's self-test found them served in lane order on this device), 0 = by ballots, -1 = no sort
  * has run yet; "shadow_key_bits" key bits the last ugrt_trace_shadow sorted its rays on (0 = no pass has sorted yet);
  * "uniform_builds_reused" ugrt_grid_build_uniform calls so far that kept the grid the context held instead of building;
+ * "light_builds_reused" the same for ugrt_grid_build_spherical;
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and
  * returns the number of operands whose result differs from 1.0f / x (0), "f2i_mismatches" does the same for the device
  * forms of ugrt_f2i / ugrt_f2u / ugrt_floor2i against the portable ones of ugrt_fmath.h (0), "lane_reduce_mismatches"
@@ -259,7 +261,14 @@ int ugrt_set_light_position(ugrt_ctx *ctx, const float pos[3]);
 /* ---- device: grid build (frustum_grid.h) ------------------------------- */
 /* FrustumGrid::buildGrid(int*, float*), frustum_grid.h:210 */
 int ugrt_grid_build_perspective(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces);
-/* FrustumGrid::buildSphericalGrid(int*, float*, float, float), frustum_grid.h:368 */
+/* FrustumGrid::buildSphericalGrid(int*, float*, float, float), frustum_grid.h:368: the light grid of the current camera
+ * block (ugrt_upload_camera: the light's).  It depends on the triangles, the context's light_nbx / light_nby / slabs, xM,
+ * yM and that camera block only -- no pixel camera, no rays, no frame number -- and the reference's light stands still
+ * (per_frame_funcs.h:8-10, main.cu:155-166).  The call returns UGRT_OK without enqueuing or changing anything (counted by
+ * "light_builds_reused") under the conditions of ugrt_grid_build_uniform below, with xM, yM and the 64 floats of the
+ * camera block, bit for bit, in the place of the box.  An asynchronous build is confirmed by a waiting one in the same
+ * way; a light that moves every frame, or several lights that take the one light grid in turn, never meet the inputs of
+ * the build before and so neither keep anything nor wait.  Option "light_reuse" 0 builds every time. */
 int ugrt_grid_build_spherical(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces,
 			      float xM, float yM);
 /* uniform world-space grid for the reflection bounce (README.md:1; no reference code).

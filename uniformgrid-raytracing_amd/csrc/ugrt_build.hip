@@ -1075,6 +1075,44 @@ static int build_prologue(ugrt_ctx *ctx, Grid &G, const int *d_facelist, const f
 	return UGRT_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Kept builds.  The uniform grid and the light grid have no per-frame input: where the caller vouches for the triangles
+// (UGRT_FLAG_STATIC_GEOMETRY) and everything else the build reads is what the held grid was built from, the build call
+// enqueues nothing and touches nothing.  `in` holds a call's inputs (kept_inputs), the context's record the held
+// build's (ugrt_ctx::KeptBuild).
+// ---------------------------------------------------------------------------
+static ugrt_ctx::KeptBuild kept_inputs(const ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int F)
+{
+	ugrt_ctx::KeptBuild in;
+	in.faces = d_facelist, in.verts = d_vertlist, in.F = F;
+	in.face_lo = ctx->face_lo, in.face_hi = ctx->face_hi;
+	return in;
+}
+
+// same inputs as the held build?  (the generation is the context's own: a record is taken behind the prologue, which
+// counts arrays it had not seen)
+static bool kept_same(const ugrt_ctx *ctx, const ugrt_ctx::KeptBuild &K, const ugrt_ctx::KeptBuild &in)
+{
+	return K.have && (ctx->cfg.flags & UGRT_FLAG_STATIC_GEOMETRY) && K.faces == in.faces && K.verts == in.verts && K.F == in.F &&
+	       K.gen == ctx->geom_gen && K.face_lo == in.face_lo && K.face_hi == in.face_hi && memcmp(K.par, in.par, sizeof(K.par)) == 0;
+}
+
+// the held build of these inputs may stand for this call: it waited, and no overflow is reported, seen or under repair
+static bool kept_usable(const ugrt_ctx *ctx, const ugrt_ctx::KeptBuild &K, const Grid &G)
+{
+	return K.exact && G.valid && ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen && !ctx->overflow_repair;
+}
+
+// remember this build (a build of an open batch is finished by _end, which comes before anybody may use the grid or
+// build it again)
+static void kept_remember(const ugrt_ctx *ctx, ugrt_ctx::KeptBuild &K, const ugrt_ctx::KeptBuild &in, const Grid &G)
+{
+	K = in;
+	K.gen = ctx->geom_gen;
+	K.exact = G.waited;
+	K.have = true;
+}
+
 // FrustumGrid::buildGrid, frustum_grid.h:210
 extern "C" int ugrt_grid_build_perspective(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int F)
 {
@@ -1111,11 +1149,29 @@ extern "C" int ugrt_grid_build_spherical(ugrt_ctx *ctx, const int *d_facelist, c
 	if (!ctx)
 		return ugrt_fail(UGRT_EINVAL, "grid_build_spherical: null context");
 	Grid &G = ctx->grid[UGRT_GRID_SPHERICAL];
+	int lx = ctx->cfg.light_nbx, ly = ctx->cfg.light_nby;
+	const int K = ctx->cfg.slabs;
+	// The grid has no per-frame input either: it depends on the triangles, its cells and slabs, xM, yM and the light's
+	// camera block alone (k_count_sph reads cc[0..2] and, through d_effective_x / _y, cc[16..26]; all of cc is compared).
+	// The pixel camera, the rays and the frame number do not enter, and the shadow pass takes the grid by pointers.
+	ugrt_ctx::KeptBuild &kept = ctx->lkept, in = kept_inputs(ctx, d_facelist, d_vertlist, F);
+	static_assert(sizeof(ugrt_ctx::KeptBuild::par) >= 5 * 4 + sizeof(CamBlock::cc), "the light grid's inputs do not fit the record");
+	in.par[0] = (u32)lx, in.par[1] = (u32)ly, in.par[2] = (u32)K;
+	memcpy(in.par + 3, &xM, 4);
+	memcpy(in.par + 4, &yM, 4);
+	memcpy(in.par + 5, ctx->cam.cc, sizeof(ctx->cam.cc));
+	const bool same = kept_same(ctx, kept, in), reuse = ctx->opt[UGRT_OPT_LIGHT_REUSE] != 0;
+	if (same && reuse && kept_usable(ctx, kept, G)) {
+		ctx->light_reused++;
+		return UGRT_OK;
+	}
+	// (an asynchronous build of these very inputs is held: this one waits to confirm it, see ugrt_grid_build_uniform.
+	// Two lights taken in turn never get here: each call's inputs differ from the build before it.)
+	const bool confirm = same && !kept.exact && reuse;
+	kept.have = false;
 	int rc = build_prologue(ctx, G, d_facelist, d_vertlist, F, "grid_build_spherical");
 	if (rc)
 		return rc;
-	int lx = ctx->cfg.light_nbx, ly = ctx->cfg.light_nby;
-	const int K = ctx->cfg.slabs;
 	G.slabs = K;
 	if (K > 1 && (rc = ugrt_buf_reserve(ctx, G.projz, (size_t)F * 4 + 8)))
 		return rc;
@@ -1131,7 +1187,10 @@ extern "C" int ugrt_grid_build_spherical(ugrt_ctx *ctx, const int *d_facelist, c
 	G.dims[0] = lx;
 	G.dims[1] = ly;
 	G.dims[2] = K;
-	return build_common(ctx, G, F, (u32)lx * (u32)ly * (u32)K, ly, K, 0, ly - 1);
+	if ((rc = build_common(ctx, G, F, (u32)lx * (u32)ly * (u32)K, ly, K, 0, ly - 1, confirm)))
+		return rc;
+	kept_remember(ctx, kept, in, G);
+	return UGRT_OK;
 }
 
 // uniform grid over the scene box (Model::{x,y,z}{Min,Max}, scene.h:273-292),
@@ -1145,18 +1204,17 @@ extern "C" int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, con
 	// The grid has no per-frame input: it depends on the triangles, the box and uniform_dims (fixed with the context)
 	// alone.  Where the caller vouches for the triangles (UGRT_FLAG_STATIC_GEOMETRY) and everything else is what the
 	// held grid was built from, the call enqueues nothing and touches nothing.
-	ugrt_ctx::UniformKept &K = ctx->ukept;
-	const bool same = K.have && (ctx->cfg.flags & UGRT_FLAG_STATIC_GEOMETRY) && K.faces == d_facelist && K.verts == d_vertlist &&
-			  K.F == F && K.gen == ctx->geom_gen && K.face_lo == ctx->face_lo && K.face_hi == ctx->face_hi &&
-			  memcmp(K.bb, bbmin, 12) == 0 && memcmp(K.bb + 3, bbmax, 12) == 0;
-	if (same && K.exact && G.valid && ctx->opt[UGRT_OPT_UNIFORM_REUSE] != 0 && ugrt_reported_status(ctx) == 0u &&
-	    !ctx->overflow_seen && !ctx->overflow_repair) {
+	ugrt_ctx::KeptBuild &K = ctx->ukept, in = kept_inputs(ctx, d_facelist, d_vertlist, F);
+	memcpy(in.par, bbmin, 12);
+	memcpy(in.par + 3, bbmax, 12);
+	const bool same = kept_same(ctx, K, in), reuse = ctx->opt[UGRT_OPT_UNIFORM_REUSE] != 0;
+	if (same && reuse && kept_usable(ctx, K, G)) {
 		ctx->uniform_reused++;
 		return UGRT_OK;
 	}
 	// An asynchronous build of these very inputs is held, and nobody has confirmed that it fitted its estimate (one that
 	// did not leaves an emptied grid): this build waits, and the next call keeps it.
-	const bool confirm = same && !K.exact && ctx->opt[UGRT_OPT_UNIFORM_REUSE] != 0;
+	const bool confirm = same && !K.exact && reuse;
 	K.have = false;
 	ctx->ubuild_id++;
 	int rc = build_prologue(ctx, G, d_facelist, d_vertlist, F, "grid_build_uniform");
@@ -1186,15 +1244,7 @@ extern "C" int ugrt_grid_build_uniform(ugrt_ctx *ctx, const int *d_facelist, con
 	if ((rc = build_common(ctx, G, F, (u32)g.dims[0] * (u32)g.dims[1] * (u32)g.dims[2], g.dims[1], g.dims[2], 0,
 			       g.dims[1] - 1, confirm)))
 		return rc;
-	// (a build of an open batch is finished by _end, which comes before anybody may use the grid or build it again;
-	// `gen` is taken behind the prologue, which counts arrays it had not seen)
-	K.faces = d_facelist, K.verts = d_vertlist, K.F = F;
-	K.face_lo = ctx->face_lo, K.face_hi = ctx->face_hi;
-	K.gen = ctx->geom_gen;
-	memcpy(K.bb, bbmin, 12);
-	memcpy(K.bb + 3, bbmax, 12);
-	K.exact = G.waited;
-	K.have = true;
+	kept_remember(ctx, K, in, G);
 	return UGRT_OK;
 }
 
@@ -1275,6 +1325,8 @@ extern "C" int ugrt_grid_merge_shards(ugrt_ctx *ctx, int which, int nparts, cons
 	if (which == UGRT_GRID_UNIFORM) { // the grid's arrays are rewritten: no longer the build ugrt_grid_build_uniform could keep
 		ctx->ukept.have = false;
 		ctx->ubuild_id++;
+	} else {
+		ctx->lkept.have = false;
 	}
 	hipStream_t st = ctx->stream;
 	const u32 C = G.C;

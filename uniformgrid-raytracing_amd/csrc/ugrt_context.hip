@@ -201,6 +201,7 @@ static const struct {
 	{ "dda_split", 0, 4 }, { "dda_split_load", 50, 100000 }, { "dda_split_segments", 1, 4 }, { "primary_xcd_run", 0, 4096 }, { "shadow_xcd_run", 0, 4096 },
 	{ "primary_centre", 0, 1 }, { "sort_rank", 0, 1 }, { "ray_sort", 0, 1 }, { "shadow_sieve", 0, 64 },
 	{ "any_rays_per_wave", 0, 64 }, { "any_coop", 1, 1 << 30 }, { "uniform_reuse", 0, 1 },
+	{ "light_reuse", 0, 1 },
 };
 
 extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *value)
@@ -221,6 +222,8 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = ctx->grid[UGRT_GRID_PERSPECTIVE].valid && ctx->grid[UGRT_GRID_PERSPECTIVE].merge_pending ? 1 : 0;
 	else if (strcmp(key, "uniform_builds_reused") == 0)
 		*value = (long long)ctx->uniform_reused;
+	else if (strcmp(key, "light_builds_reused") == 0)
+		*value = (long long)ctx->light_reused;
 	else if (strcmp(key, "recip_mismatches") == 0) {
 		// exhaustive: every float through the tracers' short reciprocal against the division (ugrt_dev.h d_recip_det)
 		unsigned long long bad = 0;

@@ -54,6 +54,7 @@ enum {
 	UGRT_OPT_ANY_RPW,          // "any_rays_per_wave": rays per wave of ugrt_trace_dda_any (1..64; 0 = default)
 	UGRT_OPT_ANY_COOP,         // "any_coop": ugrt_trace_dda_any: list length from which a ray's cell is tested by the whole wave
 	UGRT_OPT_UNIFORM_REUSE,    // "uniform_reuse": 0 = ugrt_grid_build_uniform builds every time (default 1: the grid is kept while its inputs stand)
+	UGRT_OPT_LIGHT_REUSE,      // "light_reuse": 0 = ugrt_grid_build_spherical builds every time (default 1: the grid is kept while the light and the geometry stand)
 	UGRT_OPT_COUNT
 };
 
@@ -179,19 +180,25 @@ struct ugrt_ctx {
 	// the branch of build_prologue that refreshes the records (no UGRT_FLAG_STATIC_GEOMETRY, or arrays it has not seen).
 	// (rec_valid cannot serve: after ugrt_animate the next build of ANY grid sets it again.)
 	unsigned long long geom_gen = 0;
-	// The inputs of the uniform grid the context holds (ugrt_grid_build_uniform keeps the grid while they stand).
+	// The inputs of a grid build the context holds: ugrt_grid_build_uniform and ugrt_grid_build_spherical keep their
+	// grid while these stand (ugrt_build.hip: kept_same, kept_remember).
 	// `have`: the held grid is a finished build of these inputs and nothing has written its arrays since;
 	// `exact`: that build waited, so its counts are known to be exact and complete (an asynchronous build may have
 	// overflowed its estimate and left an emptied grid: it is never reused, the next build of the same inputs waits).
-	struct UniformKept {
+	// `par`: what the build reads beside the triangles and the face window, compared bit for bit -- the uniform grid's
+	// box; the light grid's cells and slabs, xM, yM and the light's camera block (CamBlock::cc, the copy its count
+	// kernel is passed by value).
+	struct KeptBuild {
 		bool have = false, exact = false;
 		const int *faces = nullptr;
 		const float *verts = nullptr;
 		int F = 0, face_lo = 0, face_hi = -1;
 		unsigned long long gen = 0;
-		float bb[6] = { 0 };
-	} ukept;
+		u32 par[72] = { 0 };
+	};
+	KeptBuild ukept, lkept; // the uniform grid's, the light grid's
 	unsigned long long uniform_reused = 0; // ugrt_grid_build_uniform calls that kept the grid ("uniform_builds_reused")
+	unsigned long long light_reused = 0;   // ugrt_grid_build_spherical calls that kept the grid ("light_builds_reused")
 	// every build of the uniform grid, and every merge into it, takes a new number; the bitmap carries the number (and
 	// the span array) it was made from
 	unsigned long long ubuild_id = 0, ubitmap_id = 0;

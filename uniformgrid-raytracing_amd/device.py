@@ -104,6 +104,10 @@ class Context:
         check(lib.ugrt_grid_build_perspective(self._h, _ptr(d_faces), _ptr(d_verts), num_faces))
 
     def grid_build_spherical(self, d_faces, d_verts, num_faces, xM, yM):
+        """The light grid of the camera block uploaded last (upload_camera).  With FLAG_STATIC_GEOMETRY the call enqueues
+        nothing while the grid the context holds was built from the same tensors, face window, xM, yM and camera block
+        and the geometry has not changed since (rotate_bunny / geometry_changed); get_state("light_builds_reused")
+        counts such calls, option "light_reuse" 0 builds every time (ugrt.h: ugrt_grid_build_spherical)."""
         check(lib.ugrt_grid_build_spherical(self._h, _ptr(d_faces), _ptr(d_verts), num_faces, xM, yM))
 
     def grid_build_uniform(self, d_faces, d_verts, num_faces, bbmin, bbmax):
@@ -157,13 +161,13 @@ class Context:
 
     def set_option(self, key, value):
         """Launch-shape options (no effect on results), e.g. "dda_rays_per_wave"; "uniform_reuse" 0 makes
-        grid_build_uniform build every time."""
+        grid_build_uniform build every time, "light_reuse" 0 grid_build_spherical."""
         check(lib.ugrt_ctx_set_option(self._h, key.encode(), int(value)))
 
     def get_state(self, key):
         """Counters and findings of the context: "radix_launches", "sort_rank_atomic", "shadow_key_bits" (key bits the
         last shadow pass sorted its rays on), "uniform_builds_reused" (grid_build_uniform calls that kept the grid the
-        context held), "primary_deferred_merges" / "primary_completed_merges" /
+        context held), "light_builds_reused" (the same for grid_build_spherical), "primary_deferred_merges" / "primary_completed_merges" /
         "primary_merge_pending" (screen-grid builds that put their merge off, those merged later after all, one pending), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
         on the device), "f2i_mismatches" (the same for the device's float -> integer conversions), "lane_reduce_mismatches"
         (the tracers' DPP / permlane-swap reductions against __shfl_xor)."""
@@ -173,7 +177,7 @@ class Context:
 
     def geometry_changed(self):
         """With FLAG_STATIC_GEOMETRY: the vertex or face array was rewritten outside ugrt_animate (the triangle
-        records and the uniform grid kept from the old contents are built again)."""
+        records, the light grid and the uniform grid kept from the old contents are built again)."""
         check(lib.ugrt_geometry_changed(self._h))
 
     def sort_pairs(self, keys_in, keys_out, values_in, values_out, key_bits, library=False):
