@@ -431,7 +431,12 @@ int ugrt_reflect_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d
 		      const float *d_ray_dir, const int *d_intersect_id, const int *d_mat_idx,
 		      const float *d_reflect, int num_materials, const float *d_vertlist, const int *d_trilist,
 		      float eps, float *d_rays, int *d_active);
-/* Amanatides-Woo traversal of the context's uniform grid */
+/* Amanatides-Woo traversal of the context's uniform grid.  d_rays holds {origin, direction} per pixel; a direction need
+ * not be a unit vector: any finite length is taken for which the Moller-Trumbore determinants of the ray against the
+ * scene's triangles (d.(e2 x e1), d.(e2 x tvec), d.(tvec x e1)) stay below 1e15 in magnitude, and d_hit_t is the
+ * parameter along the direction as given.  The closest hit is the one the exact float test finds over the cells the
+ * ray walks: the window kernel's bundle cull only decides which exact tests run, and its margins follow the length of
+ * the directions (csrc/ugrt_dda.h). */
 int ugrt_trace_dda(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span,
 		   const unsigned *d_offset, const float *d_vertlist, const int *d_trilist,
 		   const float *d_rays, const int *d_active, float *d_hit_t, int *d_hit_id);

@@ -116,6 +116,18 @@ def _soup(u, seed, ntri):
     return s, u.FrameSetup(cam, light, tuple(rng.uniform(100.0, 450.0, 3)))
 
 
+def _cullsyn(u):
+    """The main frame of tests/test_primary_cull_synthetic.py: small triangles with an edge or a vertex on the rays of
+    chosen pixels, and pairs of tile-filling triangles a relative 0 to 0.3 apart in depth; a light beside the eye."""
+    import test_primary_cull_synthetic as PC
+
+    S = PC.scene(O, "near")
+    s = dict(u.scenes.cornell())
+    s.update(verts=S.verts, faces=S.faces, matidx=(np.arange(S.F) % len(s["mat_list"])).astype(np.int32))
+    light = dict(eye=(3.0, 4.0, -2.0), look=(0.5, 0.5, 30.0), up=(0.0, 0.0, 1.0), near=0.1, far=5000.0)
+    return s, u.FrameSetup(PC.camera_params(False), light, (3.0, 4.0, -2.0))
+
+
 def _near_far(build, near, far):
     """A case's scene and setup with the camera's near/far planes moved: the GL depth of its hits spreads over
     [0, 1) and so over every z-slab."""
@@ -143,6 +155,7 @@ CASES = {
     "ties_192x160": (_ties_and_grazing, 192, 160),
     "soup1_128x96": (lambda u: _soup(u, 1, 600), 128, 96),
     "soup2_160x128": (lambda u: _soup(u, 2, 6000), 160, 128),
+    "cullsyn_128x64": (_cullsyn, 128, 64),
     # the reference's own constants: 1024 x 1024, NUM_BLOCKS 128, a 128 x 128 light grid
     "hall_1024": (lambda u: _named(u, "hall", "ref"), 1024, 1024),
 }

@@ -156,9 +156,34 @@ __device__ __forceinline__ bool d_dda_step(const DGrid &g, int *c, const int *st
 // by |d| |e2| |o' - oc| instead leaves twice as many triangles for the exact tests.)  The margins cover the rounding of the exact test, whose operands are
 // tvec = o - v0 with the ray's own origin: `reach` bounds |o - oc|.  A culled triangle fails the exact
 // float test on every ray of the bundle, so results do not change by a bit.
+//
+// The length of the directions.  ugrt_trace_dda takes directions of any finite length (ugrt.h), and everything the
+// margins stand against grows with it.  With s = max_k max|d_k| over the bundle, a = max|tvec_k| (<= max|tc_k| + reach),
+// b = max|e1_k|, c = max|e2_k| and u = 2^-24:
+//   * the exact test forms A = tvec.(d x e2) from six products d_i e2_j tvec_k of at most s c a, each behind three
+//     roundings (the product d_i e2_j, the difference of two of them, the product with tvec_k) and two additions:
+//     |error| <= 6 * 5u * s a c < 2^-19 s a c; likewise B (s a b) and det (s b c);
+//   * the cull forms the same numbers as n.dc from n = e2 x tc: the same bound with tc for tvec, and what tc differs
+//     from the ray's own tvec by is the origin term's (orad) or, for the rounding of o' = o + t_in d itself, at most
+//     u |t_in d| <= u reach per component: again u s c reach, inside s a c with a's `reach`.
+// So the margins have to be K s a c, K s a b, K s b c: K = 6/65536 = 2^-13.4 leaves 2^5 over the bounds above, as the
+// single-origin culls of ugrt_packet.h have for their unit directions (s <= 1 there).  Every number the cull compares
+// with a margin is linear in the direction box (dc, dr), so instead of the margins the BOX is scaled: d_beam_box stores
+// dc / s and dr / s, and d_cull_beam's K a c against A / s is K s a c against A.  s is wave-uniform: one reciprocal
+// per bundle, carried by the box's own halving, nothing per triangle, and no value more to keep (the kernel has no
+// scalar register to spare).  s = 1 is kept for shorter directions: 1 / 1 is exact, the box and every decision are
+// then bit for bit those of a box that is not scaled, the margins merely wider than needed.  (reach is |t_in d|, a length in space: s
+// is multiplied back into it.)  (tests/test_dda_cull_synthetic.py walks directions of length 1e-3 to 1e6.)
+// The direction box's absolute floor follows s too: dc = (lo + hi) / 2 and hi - lo round by up to half an ulp of s
+// (2^-24 s each), which 1e-6 covers only while s < 16: two adjacent floats lo, hi of magnitude 32 are 3.8e-6 apart,
+// dc rounds onto one of them and the half width 0.5 (hi - lo) 1.0001 + 1e-6 = 2.9e-6 no longer reaches the other.
+// 1e-6 s is 16 half-ulps of s at least; over s it is 1e-6 against components of at most 1, which
+// also covers the reciprocal's and the products' rounding (2^-22.5 together).  (orad's floor is relative already:
+// 7.63e-6 = 2^-17 of |o'|.)
 struct BeamBox {
-	float oc[3], orad[3], dc[3], dr[3];
-	float reach; // >= |o - oc|_inf over the bundle
+	float oc[3], orad[3];
+	float dc[3], dr[3]; // the direction box over s = max(1, largest |direction component| of the bundle)
+	float reach;        // >= |o - oc|_inf over the bundle
 };
 
 __device__ __forceinline__ float d_uniform(float v)
@@ -170,24 +195,32 @@ __device__ __forceinline__ BeamBox d_beam_box(const float *o, const float *d, fl
 {
 	BeamBox bx;
 	const float inf = __builtin_huge_valf();
-	float on2 = 0.0f, dm2 = 0.0f;
+	float on2 = 0.0f, dm2 = 0.0f, s = 1.0f;
+	float dlo[3], dhi[3];
 #pragma unroll
 	for (int k = 0; k < 3; k++) {
 		const float p = o[k] + tin * d[k];
-		float lo = d_wave_fmin(in ? p : inf), hi = d_wave_fmax(in ? p : -inf);
+		const float lo = d_wave_fmin(in ? p : inf), hi = d_wave_fmax(in ? p : -inf);
 		bx.oc[k] = 0.5f * (lo + hi);
 		// half width + the distance of the computed o' from the exact point of the ray (a few ulps of |o'|)
 		bx.orad[k] = 0.5f * (hi - lo) * 1.0001f + 7.63e-6f * fmaxf(fabsf(lo), fabsf(hi)) + 1e-6f;
 		on2 += bx.orad[k] * bx.orad[k];
-		lo = d_wave_fmin(in ? d[k] : inf);
-		hi = d_wave_fmax(in ? d[k] : -inf);
-		bx.dc[k] = 0.5f * (lo + hi);
-		bx.dr[k] = 0.5f * (hi - lo) * 1.0001f + 1e-6f;
+		dlo[k] = d_wave_fmin(in ? d[k] : inf);
+		dhi[k] = d_wave_fmax(in ? d[k] : -inf);
+		s = fmaxf(s, fmaxf(fabsf(dlo[k]), fabsf(dhi[k])));
+	}
+	// the direction box over s: the halving carries the division (h = 0.5 for s == 1: the box as it always was)
+	const float h = 0.5f * __builtin_amdgcn_rcpf(s);
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		bx.dc[k] = h * (dlo[k] + dhi[k]);
+		bx.dr[k] = h * (dhi[k] - dlo[k]) * 1.0001f + 1e-6f;
 		const float da = fabsf(bx.dc[k]) + bx.dr[k];
 		dm2 += da * da;
 	}
 	const float tmax = d_wave_fmax(in ? tin : 0.0f);
-	const float on = __builtin_sqrtf(on2) * 1.0001f, dmax = __builtin_sqrtf(dm2) * 1.0001f;
+	// (reach is a length in space: the directions' own length goes back into it)
+	const float on = __builtin_sqrtf(on2) * 1.0001f, dmax = __builtin_sqrtf(dm2) * 1.0001f * s;
 	bx.reach = (tmax * dmax + on) * 1.001f;
 	// uniform values: keep them in scalar registers
 #pragma unroll
@@ -216,7 +249,7 @@ __device__ __forceinline__ bool d_cull_beam(const float *v0, const float *e1, co
 	const float a = fmaxf(fmaxf(fabsf(tc[0]), fabsf(tc[1])), fabsf(tc[2])) + bx.reach;
 	const float b = fmaxf(fmaxf(fabsf(e1[0]), fabsf(e1[1])), fabsf(e1[2]));
 	const float c = fmaxf(fmaxf(fabsf(e2[0]), fabsf(e2[1])), fabsf(e2[2]));
-	const float K = 6.0f / 65536.0f;
+	const float K = 6.0f / 65536.0f; // (against numerators over the length of the bundle's directions: d_beam_box)
 	const float mA = fmaxf(K * a * c, 1e-25f), mB = fmaxf(K * a * b, 1e-25f), mD = fmaxf(K * b * c, 1e-25f);
 	const float Dm = nD[0] * bx.dc[0] + nD[1] * bx.dc[1] + nD[2] * bx.dc[2];
 	const float Dr = fabsf(nD[0]) * bx.dr[0] + fabsf(nD[1]) * bx.dr[1] + fabsf(nD[2]) * bx.dr[2];

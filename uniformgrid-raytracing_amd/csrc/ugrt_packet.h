@@ -26,9 +26,15 @@ __device__ __forceinline__ u32 d_xcd_block()
 // of the item's directions shows "no lane can pass" for most triangles of a cell list (the
 // lists come from clamped bounding boxes); only survivors get the per-lane test.
 // One LANE culls one TRIANGLE, so a batch of 64 is culled for the price of one per-lane test.
-// The margins (2^-16 relative to the operand magnitudes, against rounding errors of ~2^-22)
-// make the cull strictly conservative: a culled triangle fails the exact float test of
-// intersectTriUV / intersectTri on every lane, so results do not change by a bit.
+// The margins are K = 6/65536 (2^-13.4) times the product of the two operands' largest components: a = max|tvec_k|,
+// b = max|e1_k|, c = max|e2_k| give mA = K a c, mB = K a b, mD = K b c.  The third factor of every numerator, the
+// direction, is left out because it is a unit vector by construction here: the primary pass normalises it with
+// D_NORMALIZE at the end of d_ray_dir (ugrt_dev.h), the shadow pass in d_shadow_ray (ugrt_trace_shadow.hip), so each
+// of its components is at most 1 and the numerators' rounding errors are at most 30 * 2^-24 a c (< 2^-19 a c; the same
+// for a b and b c).  The absolute floor of a direction box's half width (1e-6, d_cbox and the tracers' own boxes) is
+// sized for unit directions too: half an ulp of a component is at most 2^-25.  (The bounce walk takes directions of
+// any length and scales both: ugrt_dda.h.)  That makes the cull strictly conservative: a culled triangle fails the
+// exact float test of intersectTriUV / intersectTri on every lane, so results do not change by a bit.
 // ---------------------------------------------------------------------------
 struct DirBox {
 	float lo[3], hi[3];
