@@ -759,6 +759,53 @@ int ugrt_trace_dda_any_hemi_sets(ugrt_ctx *ctx, const unsigned *d_value_list, co
  * outside 1..UGRT_MAX_AO_DIRS or a null argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_ao_shade_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_vis, int num_dirs);
 
+/* ---- device: indirect diffuse light, one bounce ----
+ * A surface lit by the surfaces around it: every primary hit gathers the colour of what its hemisphere rays hit first.
+ * Per frame: ugrt_ao_rays, ugrt_gi_gather, the shading calls, ugrt_gi_filter (optional), ugrt_gi_apply.  All arithmetic is
+ * fp32 without contraction or unsigned 32-bit integer. */
+/* The closest-hit hemisphere gather.  For an active pixel p of the band and sample s < num_dirs the ray {o, D} is exactly
+ * ugrt_trace_dda_any_hemi_sets' (same k(p), same basis rule, same operation order; d_dirs is DEVICE memory,
+ * [set_w * set_h][num_dirs][3] local directions).  Its hit is ugrt_trace_dda's -- the same cells, list order, a test
+ * accepted with 0 < t < best, the walk ended behind the first cell whose exit parameter is not below an accepted t --
+ * with two additions: best starts at min(3.0e38f, radius), and the walk also ends behind a cell whose exit parameter is
+ * not below radius (the any-hit walk's rule; radius may be +inf).  A miss, or a hit whose material d_mat_idx[hit] is
+ * outside 0..num_materials-1, has the colour 0; otherwise the colour is what ugrt_shade_reflect_depth gives a level's hit
+ * at {o, D}, t and that triangle: the clamped Lambert term under the context's camera block and ugrt_set_light_position's
+ * light.  With shadow_light (host float[3], passed on by value; NULL: no shadow phase) the colour is divided by 3.0f where
+ * ugrt_trace_dda_any(t_max = 1) flags the ray ugrt_occlusion_rays forms from {o, D}, t, the triangle, shadow_light and
+ * eps; glass is an ordinary surface in both phases.  d_sum, unsigned [4 * width * height], 16-byte aligned:
+ * d_sum[4p + k], k = 0..2, is the sum over s of the colour's byte k (as the shading kernels turn a float into a byte; at
+ * most 32 * 255) and d_sum[4p + 3] = 1; inactive pixels of the band get four zeros, pixels outside the band are not
+ * written.  The index space is ugrt_trace_dda_any_area's (pixel group, sample): a pixel's rays sit in neighbouring lanes
+ * of one wave, the ray, its hit, the occlusion ray and the colour stay in registers, the byte sums are added across the
+ * lanes and stored with one 16-byte store, without atomic operations.  One prepare launch and one ray list serve the call;
+ * the band's words are cleared in stream order.  Options "any_rays_per_wave" (unset: 64), "any_coop" and "dda_blocks"
+ * shape the launch and change no word.  Stages UGRT_ST_WORKLIST / UGRT_ST_TRACE_DDA.  The call leaves the split-walk
+ * history of ugrt_trace_dda and what ugrt_reflect_rays_next told it alone.  num_dirs outside 1..UGRT_MAX_AO_DIRS, set_w or
+ * set_h outside 1..UGRT_MAX_AO_SET_TILE, set_w * set_h * num_dirs > UGRT_MAX_AO_SET_DIRS, radius <= 0 or NaN, eps NaN,
+ * num_materials < 1, a d_sum that is not 16-byte aligned, or a null argument other than shadow_light: UGRT_EINVAL (the
+ * message names the argument) and nothing is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_gi_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+		   const float *d_vertlist, const int *d_trilist, const float *d_orays, const int *d_oactive, int num_dirs,
+		   int set_w, int set_h, const float *d_dirs, float radius, const int *d_mat_idx, const float *d_mat_list,
+		   int num_materials, const float *shadow_light, float eps, unsigned *d_sum);
+/* ugrt_filter_visibility's gather -- its window, weights and acceptance tests -- over ugrt_gi_gather's sums: for an active
+ * pixel d_acc[4p + k], k = 0..2, is the sum of w * d_sum[4q + k] over the accepted q (at most 6561 * 8160) and
+ * d_acc[4p + 3] the sum of w (at most 6561); inactive pixels of the band get four zeros, pixels outside the band are not
+ * written, radius 0 reproduces d_sum.  d_sum and d_acc are unsigned [4 * width * height], 16-byte aligned.  The stage,
+ * the band rule and the errors are ugrt_filter_visibility's. */
+int ugrt_gi_filter(ugrt_ctx *ctx, const unsigned *d_sum, const float *d_orays, const int *d_oactive, int radius,
+		   float normal_cos, float plane_tol, unsigned *d_acc);
+/* The gathered light onto the image, behind the shading call of the frame (d_intersect_id[p] holds the material index m by
+ * then; it is only read).  d_acc is ugrt_gi_filter's output or ugrt_gi_gather's sums.  For a pixel of the band with m in
+ * 0..num_materials-1 and den = d_acc[4p + 3] != 0, per component k:
+ * a = (Kd_k * gain) * ((float)d_acc[4p + k] / (float)(255u * num_dirs * den)), the unsigned product converted once, a
+ * clamped to 1 as the shading kernels clamp, and the byte b becomes min(255, b + byte(a)).  Every other pixel is left as
+ * it is.  Stage UGRT_ST_SHADE.  gain < 0 or NaN, num_dirs outside 1..UGRT_MAX_AO_DIRS, a d_acc that is not 16-byte
+ * aligned or a null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_gi_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_dirs, float gain,
+		  const int *d_intersect_id, const float *d_mat_list, int num_materials);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

@@ -189,6 +189,9 @@ PROTOTYPES = {
     "ugrt_shade_area_vis": (C.c_int, [_P, _P, _P, C.c_int]),
     "ugrt_trace_dda_any_hemi_sets": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P]),
     "ugrt_ao_shade_vis": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ugrt_gi_gather": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, C.c_int, _F3, C.c_float, _P]),
+    "ugrt_gi_filter": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P]),
+    "ugrt_gi_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

@@ -145,6 +145,52 @@ __device__ __forceinline__ bool d_dda_step(const DGrid &g, int *c, const int *st
 	return outside;
 }
 
+// The pixel-major index space of the walks that give a pixel S rays (ugrt_dda_any.hip: the area aims; ugrt_gi.hip).
+// Which slot of its group (pix) and which sample (smp) a lane serves: lane / S and lane % S, the quotient by a
+// multiplication that is exact for lane < 64 and S <= 32.  They are formed again where they are used, before and behind
+// the walk (the lane id is made opaque), so the walk carries no register for them.
+__device__ __forceinline__ void d_area_lane(int lane, u32 S, u32 &pix, u32 &smp)
+{
+	u32 l = (u32)lane;
+	asm volatile("" : "+v"(l));
+	pix = (l * ((65536u + S - 1u) / S)) >> 16;
+	smp = l - pix * S;
+}
+
+// The hemisphere rays' basis rule.
+// D = (x*T + y*B) + z*n over the normal n: a = the axis of the smallest |n[k]| (strict <, 1 against 0, then 2 against the
+// winner: ties go to the lowest k), T = normalize(n x e_a) -- a swizzle with one exact negation --, B = n x T.
+__device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, float z, float *D)
+{
+	int a = 0;
+	float m = __builtin_fabsf(n[0]);
+	if (__builtin_fabsf(n[1]) < m) {
+		a = 1;
+		m = __builtin_fabsf(n[1]);
+	}
+	if (__builtin_fabsf(n[2]) < m)
+		a = 2;
+	float T[3], B[3];
+	if (a == 0) {
+		T[0] = 0.0f;
+		T[1] = n[2];
+		T[2] = -n[1];
+	} else if (a == 1) {
+		T[0] = -n[2];
+		T[1] = 0.0f;
+		T[2] = n[0];
+	} else {
+		T[0] = n[1];
+		T[1] = -n[0];
+		T[2] = 0.0f;
+	}
+	D_NORMALIZE(T);
+	D_CROSS(B, n, T);
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		D[k] = (x * T[k] + y * B[k]) + z * n[k];
+}
+
 // Cull of one triangle against a BUNDLE of rays with different origins.  Moller-Trumbore's numerators do
 // not change when the origin slides along its ray (A = d.(e2 x tvec), and d.(e2 x d) = 0), so every ray of
 // the bundle is represented by the point o' = o + t_in * d where it enters the current cell: the points of

@@ -16,29 +16,6 @@
 
 #define DDA_AHEAD 4   // cells planned (and their headers fetched) per round trip
 
-// 64-bit wave minimum on the DPP path (two 32-bit moves per step); the result is uniform
-__device__ __forceinline__ unsigned long long d_wave_min_u64(unsigned long long v)
-{
-	u32 lo = (u32)v, hi = (u32)(v >> 32);
-#define D_MIN64_STEP(CTRL, RM)                                                                   \
-	{                                                                                        \
-		const u32 olo = (u32)d_dpp_i<CTRL, RM>(-1, (int)lo), ohi = (u32)d_dpp_i<CTRL, RM>(-1, (int)hi); \
-		const bool less = ohi < hi || (ohi == hi && olo < lo);                           \
-		lo = less ? olo : lo;                                                            \
-		hi = less ? ohi : hi;                                                            \
-	}
-	D_MIN64_STEP(0x111, 0xF)
-	D_MIN64_STEP(0x112, 0xF)
-	D_MIN64_STEP(0x114, 0xF)
-	D_MIN64_STEP(0x118, 0xF)
-	D_MIN64_STEP(0x142, 0xA)
-	D_MIN64_STEP(0x143, 0xC)
-#undef D_MIN64_STEP
-	lo = (u32)__builtin_amdgcn_readlane((int)lo, 63);
-	hi = (u32)__builtin_amdgcn_readlane((int)hi, 63);
-	return ((unsigned long long)hi << 32) | lo;
-}
-
 // Default results for every pixel of the band + the list of active secondary rays, in 8x8 TILE order: 64
 // consecutive entries are neighbours on the screen, i.e. rays that start next to each other and point the
 // same way (the order is irrelevant for the results).  Each wave owns DDA_PREP_SPAN / 64 consecutive tiles

@@ -111,16 +111,7 @@ struct AnyHemiSets {
 };
 // (dynamic LDS, its base 16-byte aligned; the aims over sets are the only ones that have any)
 extern __shared__ __attribute__((aligned(16))) float s_sets_pos[];
-// Which slot of its group (pix) and which sample (smp) a lane serves: lane / S and lane % S, the quotient by a
-// multiplication that is exact for lane < 64 and S <= 32.  They are formed again where they are used, before and behind
-// the walk (the lane id is made opaque), so the walk carries no register for them.
-__device__ __forceinline__ void d_area_lane(int lane, u32 S, u32 &pix, u32 &smp)
-{
-	u32 l = (u32)lane;
-	asm volatile("" : "+v"(l));
-	pix = (l * ((65536u + S - 1u) / S)) >> 16;
-	smp = l - pix * S;
-}
+// (d_area_lane, which slot of its group and which sample a lane serves: ugrt_dda.h)
 // (function-scope LDS: only the kernels that call this carry it)
 __device__ __forceinline__ float *d_area_lds()
 {
@@ -144,38 +135,7 @@ __device__ __forceinline__ bool d_see_through(const ThruArg &a, const u32 *__res
 	return m >= 0 && m < a.mat_count && a.transmit[m] > 0;
 }
 
-// D = (x*T + y*B) + z*n over the normal n: a = the axis of the smallest |n[k]| (strict <, 1 against 0, then 2 against the
-// winner: ties go to the lowest k), T = normalize(n x e_a) -- a swizzle with one exact negation --, B = n x T.
-__device__ __forceinline__ void d_hemi_dir(const float *n, float x, float y, float z, float *D)
-{
-	int a = 0;
-	float m = __builtin_fabsf(n[0]);
-	if (__builtin_fabsf(n[1]) < m) {
-		a = 1;
-		m = __builtin_fabsf(n[1]);
-	}
-	if (__builtin_fabsf(n[2]) < m)
-		a = 2;
-	float T[3], B[3];
-	if (a == 0) {
-		T[0] = 0.0f;
-		T[1] = n[2];
-		T[2] = -n[1];
-	} else if (a == 1) {
-		T[0] = -n[2];
-		T[1] = 0.0f;
-		T[2] = n[0];
-	} else {
-		T[0] = n[1];
-		T[1] = -n[0];
-		T[2] = 0.0f;
-	}
-	D_NORMALIZE(T);
-	D_CROSS(B, n, T);
-#pragma unroll
-	for (int k = 0; k < 3; k++)
-		D[k] = (x * T[k] + y * B[k]) + z * n[k];
-}
+// (d_hemi_dir, the world direction of a local one over a normal: ugrt_dda.h)
 
 // `occluded` of the band was cleared by the prepare kernel (AnyLights: layer 0; the layers behind by the host call): only
 // the flags of occluded rays are written (AnyHemi: `occluded` is the mask words, bit s is OR-ed in by direction s's lane;

@@ -376,6 +376,45 @@ __device__ __forceinline__ void d_lambert_from(const CamBlock &cam, const float 
 	}
 }
 
+__device__ __forceinline__ void d_clamp1(float *color)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		color[k] = color[k] > 1.0f ? 1.0f : color[k];
+}
+
+// Kd of material m, twice: ambient uses Kd too (shader_kernel.cu:180-186)
+__device__ __forceinline__ void d_material_kd(const float *__restrict__ mat_list, int m, float *material)
+{
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		material[k] = mat_list[m * 6 + 3 + k];
+		material[3 + k] = mat_list[m * 6 + 3 + k];
+	}
+}
+
+// The clamped Lambert colour of a hit that its kernel holds in registers (ugrt_gi.hip): the hit at parameter ht of the ray
+// {o, d} on the staged triangle tri ({., e1, e2}: d_stage_triangle; e1 and e2 are normalised in place), material hm in
+// range.  The point and the normal are d_level_hit's arithmetic and the shading is d_level_color's (ugrt_shade.hip),
+// operation for operation, so rc gets the bits the level's shading gives the same hit.
+__device__ __forceinline__ void d_hit_color(const CamBlock &cam, const float *o, const float *d, float ht, float *tri,
+					    const float *__restrict__ mat_list, int hm, float *rc)
+{
+	float hmat[6], hp[3], nn[3];
+	float *e1 = &tri[3], *e2 = &tri[6];
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		hp[k] = o[k] + ht * d[k];
+	d_material_kd(mat_list, hm, hmat);
+	D_NORMALIZE(e1);
+	D_NORMALIZE(e2);
+	D_CROSS(nn, e1, e2);
+	D_NORMALIZE(nn);
+	rc[0] = rc[1] = rc[2] = 0.0f;
+	d_lambert<false>(cam, hp, nn, rc, hmat, 1.0f);
+	d_clamp1(rc);
+}
+
 // where a ray leaves a hit: hit point P = o + t*d on the staged triangle tri ({., e1, e2}: d_stage_triangle),
 // nn = normalize(e1 x e2) turned against d, dn = d.nn (<= 0).  The text d_reflect_ray and the generators' RAY_NORMAL rule
 // (d_secondary_ray, ugrt_bounce.hip: k_ao_rays) share (a macro, like D_CROSS: the kernels that had it written out keep

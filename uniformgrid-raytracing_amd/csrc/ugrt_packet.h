@@ -320,6 +320,30 @@ __device__ __forceinline__ float d_unordered(int b) { return __int_as_float(b ^ 
 __device__ __forceinline__ float d_wave_fmin(float v) { return d_unordered(d_wave_imin(d_ordered(v))); }
 __device__ __forceinline__ float d_wave_fmax(float v) { return d_unordered(d_wave_imax(d_ordered(v))); }
 
+// 64-bit wave minimum on the DPP path (two 32-bit moves per step); the result is uniform
+// (the closest-hit walks' cooperative rounds: ugrt_dda.hip, ugrt_gi.hip)
+__device__ __forceinline__ unsigned long long d_wave_min_u64(unsigned long long v)
+{
+	u32 lo = (u32)v, hi = (u32)(v >> 32);
+#define D_MIN64_STEP(CTRL, RM)                                                                   \
+	{                                                                                        \
+		const u32 olo = (u32)d_dpp_i<CTRL, RM>(-1, (int)lo), ohi = (u32)d_dpp_i<CTRL, RM>(-1, (int)hi); \
+		const bool less = ohi < hi || (ohi == hi && olo < lo);                           \
+		lo = less ? olo : lo;                                                            \
+		hi = less ? ohi : hi;                                                            \
+	}
+	D_MIN64_STEP(0x111, 0xF)
+	D_MIN64_STEP(0x112, 0xF)
+	D_MIN64_STEP(0x114, 0xF)
+	D_MIN64_STEP(0x118, 0xF)
+	D_MIN64_STEP(0x142, 0xA)
+	D_MIN64_STEP(0x143, 0xC)
+#undef D_MIN64_STEP
+	lo = (u32)__builtin_amdgcn_readlane((int)lo, 63);
+	hi = (u32)__builtin_amdgcn_readlane((int)hi, 63);
+	return ((unsigned long long)hi << 32) | lo;
+}
+
 // box of the directions of the lanes with `valid`; other lanes do not contribute (uniform: scalar registers)
 __device__ __forceinline__ DirBox d_dir_box(const float *d, bool valid)
 {

@@ -249,12 +249,7 @@ __device__ __forceinline__ float d_along_y(const CamBlock &cam, const float *vec
 	return (upDotValue > 0) ? angle : -1.0f * angle;
 }
 
-__device__ __forceinline__ void d_clamp1(float *color)
-{
-#pragma unroll
-	for (int k = 0; k < 3; k++)
-		color[k] = color[k] > 1.0f ? 1.0f : color[k];
-}
+// (d_clamp1, d_material_kd: ugrt_dev.h)
 
 // The primary hit of a pixel, as the kernels that shade one read it.  Each step reads what it names and nothing else, and
 // a kernel takes the steps inside its own guards (`in range`, `t_value > 0`, the spot light's none), so a miss reads no
@@ -290,16 +285,6 @@ struct PrimaryHit {
 			nrm[k] = dd_normal[pixelID * 3 + k];
 	}
 };
-
-// Kd of material m, twice: ambient uses Kd too (shader_kernel.cu:180-186)
-__device__ __forceinline__ void d_material_kd(const float *__restrict__ mat_list, int m, float *material)
-{
-#pragma unroll
-	for (int k = 0; k < 3; k++) {
-		material[k] = mat_list[m * 6 + 3 + k];
-		material[3 + k] = mat_list[m * 6 + 3 + k];
-	}
-}
 
 template <bool SPOT>
 __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned char *__restrict__ d_img,
@@ -509,6 +494,49 @@ extern "C" int ugrt_ao_shade_vis(ugrt_ctx *ctx, unsigned char *d_img, const unsi
 	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
 		return ugrt_fail(UGRT_EINVAL, "ao_shade_vis: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
 	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade_ao_vis, d_img, d_vis, (u32)num_dirs);
+}
+
+// Indirect diffuse light onto the image, behind the shading call: intersect_id holds the
+// material index m by then and is only read.  acc is what ugrt_gi_filter wrote, or ugrt_gi_gather's sums themselves (den
+// 1): the mean byte of the gathered samples over 255 is the incoming light, Kd * gain of it is added to the pixel.
+__global__ __launch_bounds__(PX_THREADS) void k_gi_apply(unsigned char *__restrict__ d_img, const u32 *__restrict__ acc,
+							  u32 num_dirs, float gain, const int *__restrict__ intersect_id,
+							  const float *__restrict__ mat_list, int mat_count, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t pixelID = (size_t)(p0 + i);
+	const int m = intersect_id[pixelID];
+	const uint4 sums = *(const uint4 *)(acc + 4 * pixelID);
+	if (m < 0 || m >= mat_count || sums.w == 0u)
+		return;
+	const float over = (float)(255u * num_dirs * sums.w);
+	float a[3] = { (float)sums.x / over, (float)sums.y / over, (float)sums.z / over };
+#pragma unroll
+	for (int k = 0; k < 3; k++)
+		a[k] = (mat_list[m * 6 + 3 + k] * gain) * a[k];
+	d_clamp1(a);
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		const u32 b = (u32)d_img[pixelID * 3 + k] + (u32)d_to_u8(a[k]);
+		d_img[pixelID * 3 + k] = (unsigned char)(b > 255u ? 255u : b);
+	}
+}
+
+extern "C" int ugrt_gi_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_dirs, float gain,
+			     const int *d_intersect_id, const float *d_mat_list, int num_materials)
+{
+	if (!ctx || !d_img || !d_acc || !d_intersect_id || !d_mat_list)
+		return ugrt_fail(UGRT_EINVAL, "gi_apply: null argument");
+	if (num_dirs < 1 || num_dirs > UGRT_MAX_AO_DIRS)
+		return ugrt_fail(UGRT_EINVAL, "gi_apply: num_dirs %d is not in 1..%d", num_dirs, UGRT_MAX_AO_DIRS);
+	if (!(gain >= 0.0f))
+		return ugrt_fail(UGRT_EINVAL, "gi_apply: gain must be 0 or greater");
+	if (((size_t)d_acc & 15u) != 0u)
+		return ugrt_fail(UGRT_EINVAL, "gi_apply: d_acc is not 16-byte aligned");
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_gi_apply, d_img, (const u32 *)d_acc, (u32)num_dirs, gain, d_intersect_id,
+				  d_mat_list, num_materials);
 }
 
 // ---------------------------------------------------------------------------

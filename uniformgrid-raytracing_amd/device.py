@@ -459,6 +459,31 @@ class Context:
         """Each byte b of a pixel with den = vis[2p + 1] != 0 becomes (b * vis[2p]) // (num_dirs * den)."""
         check(lib.ugrt_ao_shade_vis(self._h, _ptr(img), _ptr(vis), int(num_dirs)))
 
+    # -- indirect diffuse light (DESIGN.md section 6.10) -------------------------
+    def gi_gather(self, value, span, offset, verts, faces, orays, oactive, num_dirs, set_w, set_h, dirs, radius, mat_idx,
+                  mat_list, num_materials, shadow_light, eps, sums):
+        """The closest-hit hemisphere gather: pixel p walks trace_dda_any_hemi_sets' num_dirs rays (dirs: the DEVICE
+        table [set_w * set_h, num_dirs, 3]) to their first hit below radius (float('inf'): the whole grid), shades the
+        hit as a reflection level's hit is shaded, divides by 3 where the hit does not see shadow_light (three host floats,
+        or None: no shadow phase), and sums the bytes: sums[4p + k] for k < 3, sums[4p + 3] = 1; sums: uint32 words
+        [4 * W * H] (an int32 tensor serves)."""
+        light = None if shadow_light is None else _points([shadow_light])[1]
+        check(lib.ugrt_gi_gather(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces), _ptr(orays),
+                                 _ptr(oactive), int(num_dirs), int(set_w), int(set_h), _ptr(dirs), radius, _ptr(mat_idx),
+                                 _ptr(mat_list), int(num_materials), light, eps, _ptr(sums)))
+
+    def gi_filter(self, sums, orays, oactive, radius, normal_cos, plane_tol, acc):
+        """filter_visibility's gather over gi_gather's sums: acc[4p + k] = sum of w * sums[4q + k] for k < 3 and
+        acc[4p + 3] = sum of w; acc: uint32 words [4 * W * H]."""
+        check(lib.ugrt_gi_filter(self._h, _ptr(sums), _ptr(orays), _ptr(oactive), int(radius), normal_cos, plane_tol,
+                                 _ptr(acc)))
+
+    def gi_apply(self, img, acc, num_dirs, gain, ids, mat_list, num_materials):
+        """Behind the shading call (ids holds material indices): each byte b of a pixel with a material in range and
+        den = acc[4p + 3] != 0 becomes min(255, b + byte(clamp((Kd * gain) * (acc[4p + k] / (255 * num_dirs * den)))))."""
+        check(lib.ugrt_gi_apply(self._h, _ptr(img), _ptr(acc), int(num_dirs), gain, _ptr(ids), _ptr(mat_list),
+                                int(num_materials)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

@@ -28,7 +28,9 @@ per primary hit towards a disk around the light through the uniform grid in the 
 and a last pass that darkens the image by the share of occluded samples; with ``area_sets``
 the pixels of a tile aim at different sets of S points, and with ``area_filter`` a gather over the pixels of the same
 surface averages their shares before that pass; ``ao_sets`` and ``ao_filter`` do the same for the
-hemisphere rays of ``ao``, in a walk that keeps a pixel's rays side by side in a wave.
+hemisphere rays of ``ao``, in a walk that keeps a pixel's rays side by side in a wave.  With
+``gi=S`` the one-stream single-light frame adds one bounce of indirect diffuse light: S hemisphere rays per primary hit to
+their first hit, which is shaded and shadowed, and a pass that adds the mean to the image.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -210,6 +212,40 @@ def check_ao_filter(ao, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_pla
                               ao_filter_plane)
 
 
+def check_gi(gi, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9,
+             gi_filter_plane=None, lights=None, reflect_lights=False, two_streams=False):
+    """The keywords of the indirect diffuse light.  gi: check_ao's rule, an integer
+    0..MAX_AO_DIRS (0: off, and every other gi_* keyword must be at its default); gi_radius: None (+inf: the whole grid) or
+    a number greater than 0; gi_gain: a number not below 0; gi_shadows: a bool; gi_sets, gi_filter, gi_filter_cos and
+    gi_filter_plane: check_ao_filter's rules.  gi > 0 needs a single-light frame (lights: setup.lights; reflect_lights)
+    and the one-stream Renderer, where check_area asks for them.  ValueError before anything is enqueued.  Returns None
+    (off) or (gi, radius, gain, shadows, gi_sets, gi_filter, cos or None, plane or None)."""
+    if isinstance(gi, (bool, np.bool_)) or not isinstance(gi, (int, np.integer)) or not 0 <= gi <= MAX_AO_DIRS:
+        raise ValueError("gi must be an integer in 0..%d, not %r" % (MAX_AO_DIRS, gi))
+    number = (int, float, np.integer, np.floating)
+    if gi_radius is not None:
+        if isinstance(gi_radius, (bool, np.bool_)) or not isinstance(gi_radius, number) \
+                or not float(np.float32(gi_radius)) > 0.0:
+            raise ValueError("gi_radius must be None or a number greater than 0, not %r" % (gi_radius,))
+    if isinstance(gi_gain, (bool, np.bool_)) or not isinstance(gi_gain, number) or not float(np.float32(gi_gain)) >= 0.0:
+        raise ValueError("gi_gain must be a number not below 0, not %r" % (gi_gain,))
+    if not isinstance(gi_shadows, (bool, np.bool_)):
+        raise ValueError("gi_shadows must be True or False, not %r" % (gi_shadows,))
+    sets = _check_sets_filter("gi", "the indirect light's rays and its gather", gi, gi_sets, gi_filter, gi_filter_cos,
+                              gi_filter_plane)
+    if gi == 0:
+        if gi_radius is not None or float(gi_gain) != 1.0 or not gi_shadows:
+            raise ValueError("gi_radius, gi_gain and gi_shadows need gi > 0: they shape the indirect light")
+        return None
+    if lights is not None or reflect_lights:
+        raise ValueError("gi needs a single-light frame: the indirect light under setup.lights is not built")
+    if two_streams:
+        raise ValueError("gi needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
+                         "side context")
+    radius = float("inf") if gi_radius is None else float(np.float32(gi_radius))
+    return (int(gi), radius, float(np.float32(gi_gain)), bool(gi_shadows)) + sets
+
+
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
 # BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
@@ -384,6 +420,29 @@ def ao_shade(c, f, dirs, radius, sets=None):
         c.shade_ao(f.image, f.ao_mask, len(dirs))
 
 
+def gi_pass(c, f, cam_pos, gi, shadow_light, have_rays):
+    """The indirect light's gather: {origin, normal} of every primary hit (ao_rays, into the AO
+    buffers, unless area_pass or ao_pass of this frame wrote them: have_rays), then the closest-hit hemisphere walk through
+    c's uniform grid into f.gi_sum.  gi: Renderer._gi_stage's (S, (set_w, set_h), table, radius, gain, gather, shadows);
+    shadow_light: the point the hits are shadowed from, or None.  Runs behind the uniform grid's build and before the
+    shading call that rewrites the ids."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    if not have_rays:
+        c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    c.gi_gather(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, gi[0], gi[1][0], gi[1][1], gi[2], gi[3],
+                f.d_matidx, f.d_matlist, f.num_materials, shadow_light, f.reflect_eps, f.gi_sum)
+
+
+def gi_shade(c, f, gi):
+    """The indirect light onto the image, behind the frame's own shading (gi_pass' gi): with a gather ((radius, cos,
+    plane)) gi_filter over f.gi_sum into f.gi_acc, then gi_apply."""
+    acc = f.gi_sum
+    if gi[5] is not None:
+        c.gi_filter(f.gi_sum, f.ao_rays, f.ao_active, gi[5][0], gi[5][1], gi[5][2], f.gi_acc)
+        acc = f.gi_acc
+    c.gi_apply(f.image, acc, gi[0], gi[4], f.intersect_id, f.d_matlist, f.num_materials)
+
+
 def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
     """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
@@ -505,6 +564,10 @@ class _Frame:
         # ao_filter: the gather's two sums per pixel (_ensure_ao_filter_buffers); ao_sets: the uploaded tables (_ao_stage)
         self.ao_vis = None
         self._ao_set_tables = {}
+        # gi: the byte sums of the indirect light's samples and the gather's sums, four words per pixel
+        # (_ensure_gi_buffers; the origins share ao_rays); the uploaded direction tables by (gi, gi_sets) (_gi_stage)
+        self.gi_sum = self.gi_acc = None
+        self._gi_set_tables = {}
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -721,7 +784,8 @@ class Renderer(_Frame, _Band):
     def display(self, setup, frame_cnt=1, shadows=True, reflect=False, shade=True, bounces=1, reflect_shadows=False,
                 reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1,
                 area_filter=0, area_filter_cos=0.9, area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9,
-                ao_filter_plane=None):
+                ao_filter_plane=None, gi=0, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0,
+                gi_filter_cos=0.9, gi_filter_plane=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -752,7 +816,16 @@ class Renderer(_Frame, _Band):
         ao_sets (needs ao > 0; 1, 4 or 16): the pixels of a 1 x 1, 2 x 2 or 4 x 4 tile walk along different sets of `ao`
         directions (scenes.ao_direction_sets; the table is uploaded once per (ao, ao_sets)) in the pixel-major walk.
         ao_filter (needs ao > 0; 0: off): area_filter's gather, with ao_filter_cos and ao_filter_plane, over ao_mask
-        before the image is scaled; ao_vis holds its sums."""
+        before the image is scaled; ao_vis holds its sums.
+        gi (one-stream renderer, single-light frames, plain or reflect, with or without refract; ao and area compose; 0:
+        off): one bounce of indirect diffuse light -- every primary hit sends gi = 1..32 hemisphere rays
+        (scenes.ao_direction_sets(gi, gi_sets), uploaded once per (gi, gi_sets)) to their first hit within gi_radius (None:
+        the whole grid), the hits are shaded under the light and, with gi_shadows, shadowed from the light camera's eye;
+        gi_sum holds the bytes' sums, gi_filter (0: off) gathers them over the pixels of the same surface with
+        gi_filter_cos and gi_filter_plane into gi_acc, and Kd * gi_gain of the mean is added to the image behind the
+        frame's own shading and before ambient occlusion scales it."""
+        gi = check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
+                      getattr(setup, "lights", None), reflect_lights, self.aux is not None)
         area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
         area_sets, area_filter, area_filter_cos, area_filter_plane = check_area_filter(area, area_sets, area_filter,
                                                                                        area_filter_cos, area_filter_plane)
@@ -770,6 +843,8 @@ class Renderer(_Frame, _Band):
             lights = check_lights(setup.lights, reflect, self.aux is not None)
             return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more))
         ao = self._ao_stage(ao, ao_radius, shade, ao_more)
+        if gi:
+            gi = self._gi_stage(gi, shade)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
@@ -791,7 +866,7 @@ class Renderer(_Frame, _Band):
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
-        elif ao or area:
+        elif ao or area or gi:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         if area:
             thru = see_through(self)
@@ -802,6 +877,8 @@ class Renderer(_Frame, _Band):
                 area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru)
         if ao:
             ao_pass(ctx, self, self.cam_pos, *ao)
+        if gi:
+            gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area))
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
         if area and area_filter:
             self._ensure_area_filter_buffers()
@@ -811,8 +888,40 @@ class Renderer(_Frame, _Band):
             ctx.shade_area_vis(self.image, self.area_vis, area)
         elif area:
             ctx.shade_area(self.image, self.area_mask, area)
+        if gi:
+            gi_shade(ctx, self, gi)
         if ao:
             ao_shade(ctx, self, *ao)
+
+    def _gi_stage(self, gi, shade):
+        """(S, (set_w, set_h), table, radius, gain, gather, shadows) for gi_pass and gi_shade from what check_gi returned,
+        with the buffers in place; None: nothing is shaded.  table: scenes.ao_direction_sets(S, gi_sets) on the device,
+        uploaded once per (S, gi_sets) and kept; gather: (radius, cos, plane), or None without one."""
+        if not shade:
+            return None
+        S, radius, gain, shadows, sets, filt, cos, plane = gi
+        self._ensure_gi_buffers(bool(filt))
+        tables = self._gi_set_tables
+        if (S, sets) not in tables:
+            from .scenes import ao_direction_sets
+
+            tables[(S, sets)] = self._upload_ao_sets(ao_direction_sets(S, sets))
+        gather = None
+        if filt:
+            gather = (filt, cos, default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane)
+        return (S, AREA_SET_TILES[sets], tables[(S, sets)], radius, gain, gather, shadows)
+
+    def _ensure_gi_buffers(self, gather):
+        """gi_sum [4 W*H] and, with a gather, gi_acc [4 W*H] (uint32 words in int32 tensors), and the origins' buffers
+        ao_rays / ao_active, allocated on first use."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.ao_rays is None:
+            self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+        if self.gi_sum is None:
+            self.gi_sum = t.zeros(4 * N, dtype=t.int32, device=dev)
+        if gather and self.gi_acc is None:
+            self.gi_acc = t.zeros(4 * N, dtype=t.int32, device=dev)
 
     def _ao_stage(self, ao, ao_radius, shade, sets=(1, 0, None, None)):
         """(directions, radius) for ao_pass and ao_shade, with the buffers in place; None: the frame has no ambient
@@ -1120,7 +1229,10 @@ class BandedRenderer(_Frame):
 
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
                 ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
-                area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None):
+                area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None, gi=0, gi_radius=None,
+                gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None):
+        check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
+                 getattr(setup, "lights", None), False, True)  # raises with gi > 0, as ao and area do
         check_area(area, area_radius, shadows, getattr(setup, "lights", None), True)  # raises with area > 0, as ao does
         check_area_filter(0, area_sets, area_filter, area_filter_cos, area_filter_plane)  # raises unless at the defaults
         check_ao_filter(0, ao_sets, ao_filter, ao_filter_cos, ao_filter_plane)  # the same
