@@ -5,6 +5,8 @@ each stage's inputs and what the run reported (shared-memory overrun, schedule d
 stored whole, larger ones as a SHA-256 and a seeded sample.  tests/test_reference_kernels.py compares the oracle and the product with these records, and the
 live binary where it is built.
 "shadowsyn" is case A of tests/test_shadow_synthetic.py (synthetic rays and triangles): the stages of the shadow pass alone.
+"buildsyn" is the perspective and the spherical boundary family of tests/test_grid_build_synthetic.py: the count, slab and
+fill kernels of the two grid builds alone.
 Usage: python tests/golden/make_ref_kernels.py [case ...]"""
 import os
 import sys
@@ -18,6 +20,7 @@ import oracle_lib as O  # noqa: E402
 import test_reference_kernels as T  # noqa: E402
 
 SHADOWSYN = "shadowsyn"  # = test_shadow_synthetic.RECORD (imported only when that record is written)
+BUILDSYN = "buildsyn"  # = test_grid_build_synthetic.RECORD (likewise)
 
 if not O.ref_kernels_live():
     sys.exit("oracle/_ref/ref_kernels is not built from the driver in the tree (make -C oracle ref)")
@@ -39,8 +42,16 @@ def write_record(name, ins, outs, stages, reported):
           {k.split("/")[0]: int(v) for k, v in rec.items() if "/report/" in k and "overrun_bytes" in k})
 
 
-for name in (sys.argv[1:] or sorted(T.CASES) + [SHADOWSYN]):
-    if name == SHADOWSYN:
+for name in (sys.argv[1:] or sorted(T.CASES) + [SHADOWSYN, BUILDSYN]):
+    if name == BUILDSYN:
+        import test_grid_build_synthetic as B
+
+        assert B.RECORD == BUILDSYN
+        ins = B.ref_stage_inputs(O)
+        raw = {st: T.run_reference(name, st, ins[st]) for st in B.REF_STAGES}
+        outs = {st: dict(raw[st], **B.pinned(O, st, raw[st])) for st in B.REF_STAGES}
+        write_record(name, ins, outs, B.REF_STAGES, B.REF_STAGES)
+    elif name == SHADOWSYN:
         import test_shadow_synthetic as S
 
         assert S.RECORD == SHADOWSYN
