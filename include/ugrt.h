@@ -215,7 +215,11 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * (default: nearest triangles first), "primary_chunk" jobs between two looks at the rays' closest hits;
  * "shadow_beam", "shadow_xseg", "shadow_sizebits", "shadow_itemsort", "shadow_mbits", "shadow_key64", "shadow_sieve" shape the
  * shadow tracer's private regrouping; "sort_library" 1 = rocPRIM's radix sort instead of the built-in
- * one, "sort_items" 8 / 16 pairs per thread of a radix pass (default: by size), "sort_rank" 0 = the passes rank by
+ * one; "shadow_pairs" 0 = the shadow tracer sorts the cull pass's (beam, triangle) candidate pairs by (beam, size class)
+ * with the radix sort, 1 / default = it counts them per (beam, size class) bucket in the cull pass, scans the counts
+ * and places the triangle ids - no sort (the pairs are sorted whatever the option with "sort_library" 1 and where the
+ * bucket table, beams x 2^"shadow_sizebits" words, would exceed 4 Mi words);
+ * "sort_items" 8 / 16 pairs per thread of a radix pass (default: by size), "sort_rank" 0 = the passes rank by
  * ballots instead of LDS atomics, "ray_sort" 1 = the deferred ugrt_sort_rays sorts at once also where nothing needs it
  * (see there); "dda_blocks", "primary_waves",
  * "any_rays_per_wave", "any_coop": ugrt_trace_dda_any (see there);
@@ -241,6 +245,7 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * "radix_launches" histogram + pass kernels of the built-in radix sort enqueued so far, "sort_rank_atomic" 1 = the radix passes rank by LDS
  * atomics (the context's self-test found them served in lane order on this device), 0 = by ballots, -1 = no sort
  * has run yet; "shadow_key_bits" key bits the last ugrt_trace_shadow sorted its rays on (0 = no pass has sorted yet);
+ * "shadow_pairs_counted" 1 = the last ugrt_trace_shadow bucketed its candidate pairs by counting, 0 = it sorted them (option "shadow_pairs");
  * "uniform_builds_reused" ugrt_grid_build_uniform calls so far that kept the grid the context held instead of building;
  * "light_builds_reused" the same for ugrt_grid_build_spherical;
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and

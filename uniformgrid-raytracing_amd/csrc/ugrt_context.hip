@@ -169,6 +169,7 @@ extern "C" void ugrt_ctx_destroy(ugrt_ctx *ctx)
 	buf_free(ctx->sitem);
 	buf_free(ctx->citem);
 	buf_free(ctx->pseg);
+	buf_free(ctx->pbkt);
 	buf_free(ctx->sray);
 	if (ctx->h_pinned)
 		(void)hipHostFree(ctx->h_pinned);
@@ -201,7 +202,7 @@ static const struct {
 	{ "dda_split", 0, 4 }, { "dda_split_load", 50, 100000 }, { "dda_split_segments", 1, 4 }, { "primary_xcd_run", 0, 4096 }, { "shadow_xcd_run", 0, 4096 },
 	{ "primary_centre", 0, 1 }, { "sort_rank", 0, 1 }, { "ray_sort", 0, 1 }, { "shadow_sieve", 0, 64 },
 	{ "any_rays_per_wave", 0, 64 }, { "any_coop", 1, 1 << 30 }, { "uniform_reuse", 0, 1 },
-	{ "light_reuse", 0, 1 },
+	{ "light_reuse", 0, 1 }, { "shadow_pairs", 0, 1 },
 };
 
 extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *value)
@@ -214,6 +215,8 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = ctx->rs_atomic_rank < 0 ? -1 : (ctx->rs_atomic_rank == 1 && ctx->opt[UGRT_OPT_SORT_RANK] != 0 ? 1 : 0);
 	else if (strcmp(key, "shadow_key_bits") == 0)
 		*value = (long long)ctx->shadow_key_bits;
+	else if (strcmp(key, "shadow_pairs_counted") == 0)
+		*value = ctx->shadow_pairs_counted ? 1 : 0;
 	else if (strcmp(key, "primary_deferred_merges") == 0)
 		*value = (long long)ctx->merges_deferred;
 	else if (strcmp(key, "primary_completed_merges") == 0)

@@ -55,6 +55,7 @@ enum {
 	UGRT_OPT_ANY_COOP,         // "any_coop": ugrt_trace_dda_any: list length from which a ray's cell is tested by the whole wave
 	UGRT_OPT_UNIFORM_REUSE,    // "uniform_reuse": 0 = ugrt_grid_build_uniform builds every time (default 1: the grid is kept while its inputs stand)
 	UGRT_OPT_LIGHT_REUSE,      // "light_reuse": 0 = ugrt_grid_build_spherical builds every time (default 1: the grid is kept while the light and the geometry stand)
+	UGRT_OPT_SHADOW_PAIRS,     // "shadow_pairs": shadow tracer: 0 = the cull pass's candidate pairs are sorted by (beam, size class), 1 / default = counted into their buckets and placed (no sort); sorted anyway with "sort_library" 1 or where the bucket table would exceed SHADOW_BUCKET_WORDS (ugrt_trace_shadow.hip)
 	UGRT_OPT_COUNT
 };
 
@@ -220,6 +221,8 @@ struct ugrt_ctx {
 	DevBuf sray;                                         // shadow tracer: rebuilt rays {direction, distance}, beam order
 	DevBuf citem;                                        // shadow tracer: the cull items (CullItem table)
 	DevBuf pseg;                                         // shadow tracer: cursors of the cull pass's output segments
+	DevBuf pbkt;                                         // shadow tracer: candidates per (beam, size class) bucket, then their inclusive sums
+	bool shadow_pairs_counted = false; // the last shadow pass bucketed its candidate pairs by counting (ugrt_ctx_get_state "shadow_pairs_counted")
 	DevBuf sitem;                                        // shadow tracer: exact-pass item list (segment, beam|sub) x2
 	u32 *h_pinned = nullptr; // pinned host words for small read-backs (UGRT_PIN_*)
 	u32 *d_small = nullptr;  // device scratch words (UGRT_DSMALL_*)

@@ -164,16 +164,17 @@ __global__ __launch_bounds__(SC_THREADS) void k_scan_tiles(LOAD load, u32 *__res
 	d_scan_tile<INCLUSIVE>(load, out, n, state, ctrl, epoch, vec, tail, store, gridDim.x);
 }
 
-// two scans of n words each in ONE launch (their inputs must not depend on each other): the first `tiles` workgroups
-// serve scan A, the others scan B, each with its own ticket and state words
+// two scans in ONE launch (their inputs must not depend on each other; n_a and n_b words): the first `tiles_a`
+// workgroups serve scan A, the others scan B, each with its own ticket and state words
 template <bool INCLUSIVE, typename LOAD>
-__global__ __launch_bounds__(SC_THREADS) void k_scan_pair(LOAD load_a, u32 *__restrict__ out_a, LOAD load_b, u32 *__restrict__ out_b, u32 n,
-							   unsigned long long *state, u32 *ctrl, u32 epoch, u32 vec, u32 tiles)
+__global__ __launch_bounds__(SC_THREADS) void k_scan_pair(LOAD load_a, u32 *__restrict__ out_a, u32 n_a, LOAD load_b, u32 *__restrict__ out_b,
+							   u32 n_b, unsigned long long *state, u32 *ctrl, u32 epoch, u32 vec, u32 tiles_a)
 {
-	if (blockIdx.x < tiles)
-		d_scan_tile<INCLUSIVE>(load_a, out_a, n, state, ctrl, epoch, vec, ScanTailNone(), ScanStoreNone(), tiles);
+	if (blockIdx.x < tiles_a)
+		d_scan_tile<INCLUSIVE>(load_a, out_a, n_a, state, ctrl, epoch, vec, ScanTailNone(), ScanStoreNone(), tiles_a);
 	else
-		d_scan_tile<INCLUSIVE>(load_b, out_b, n, state + tiles, ctrl + 2, epoch, vec, ScanTailNone(), ScanStoreNone(), tiles);
+		d_scan_tile<INCLUSIVE>(load_b, out_b, n_b, state + tiles_a, ctrl + 2, epoch, vec, ScanTailNone(), ScanStoreNone(),
+				       gridDim.x - tiles_a);
 }
 
 // enqueues the scan on ctx->stream; out must be 16-byte aligned for `vec_out`
@@ -207,19 +208,21 @@ static int ugrt_scan_launch(ugrt_ctx *ctx, const LOAD &load, u32 *out, size_t n,
 	return UGRT_OK;
 }
 
-// two scans of n words in one launch (k_scan_pair)
+// two scans in one launch (k_scan_pair): n words each, or n_b words for the second where it is given
 template <bool INCLUSIVE, typename LOAD>
-static int ugrt_scan_launch_pair(ugrt_ctx *ctx, const LOAD &load_a, u32 *out_a, const LOAD &load_b, u32 *out_b, size_t n)
+static int ugrt_scan_launch_pair(ugrt_ctx *ctx, const LOAD &load_a, u32 *out_a, const LOAD &load_b, u32 *out_b, size_t n, size_t n_b = 0)
 {
+	if (n_b == 0)
+		n_b = n;
 	if (n == 0)
 		return UGRT_OK;
-	if (n > 0x7FFFFFF0ull)
-		return ugrt_fail(UGRT_EINVAL, "scan: %zu words exceed the 32-bit index", n);
+	if (n > 0x7FFFFFF0ull || n_b > 0x7FFFFFF0ull)
+		return ugrt_fail(UGRT_EINVAL, "scan: %zu words exceed the 32-bit index", n > n_b ? n : n_b);
 	hipStream_t st = ctx->stream;
 	const u32 vec = ((((uintptr_t)out_a) | ((uintptr_t)out_b)) & 15u) == 0 ? 1u : 0u;
-	const u32 tiles = (u32)((n + SC_TILE - 1) / SC_TILE);
+	const u32 tiles = (u32)((n + SC_TILE - 1) / SC_TILE), tiles_b = (u32)((n_b + SC_TILE - 1) / SC_TILE);
 	const void *before = ctx->scan_state.p;
-	int rc = ugrt_buf_reserve(ctx, ctx->scan_state, (size_t)tiles * 16 + 64);
+	int rc = ugrt_buf_reserve(ctx, ctx->scan_state, ((size_t)tiles + tiles_b) * 8 + 64);
 	if (rc)
 		return rc;
 	if (ctx->scan_state.p != before) {
@@ -232,8 +235,8 @@ static int ugrt_scan_launch_pair(ugrt_ctx *ctx, const LOAD &load_a, u32 *out_a, 
 	}
 	u32 *ctrl = (u32 *)ctx->scan_state.p;
 	unsigned long long *state = (unsigned long long *)((char *)ctx->scan_state.p + 64);
-	hipLaunchKernelGGL((k_scan_pair<INCLUSIVE, LOAD>), dim3(2u * tiles), dim3(SC_THREADS), 0, st, load_a, out_a, load_b, out_b, (u32)n,
-			   state, ctrl, ctx->scan_epoch, vec, tiles);
+	hipLaunchKernelGGL((k_scan_pair<INCLUSIVE, LOAD>), dim3(tiles + tiles_b), dim3(SC_THREADS), 0, st, load_a, out_a, (u32)n, load_b, out_b,
+			   (u32)n_b, state, ctrl, ctx->scan_epoch, vec, tiles);
 	UGRT_HIP(hipGetLastError());
 	return UGRT_OK;
 }

@@ -14,7 +14,9 @@
 //      ray-independent halves of the interval test) and streams the cell's beam boxes past them;
 //      the (beam, triangle) pairs that cannot be ruled out are appended to a list.  Triangles are
 //      read once per cell instead of once per chunk;
-//   3. the pair list is sorted by beam (the project's radix sort, ugrt_sort.hip; option "sort_library" 1: rocPRIM), and
+//   3. the pairs are brought beam by beam, large apparent size first: counted per (beam, size class) bucket in the cull
+//      pass, the counts scanned, the triangle ids placed (COUNTED BUCKETS below; option "shadow_pairs" 0: sorted by the
+//      project's radix sort, ugrt_sort.hip; option "sort_library" 1: by rocPRIM's), and
 //   4. EXACT pass, lane = ray: each beam runs the reference's per-ray test on its own short list.  One wave per
 //      item of that list by default; option "shadow_xcd_run" 0 restores persistent waves.
 // The cull is conservative with margins far above fp32 rounding, so the flags do not change.
@@ -270,7 +272,8 @@ __global__ __launch_bounds__(64 * BOX_WAVES) void k_shadow_boxes(CamBlock cam, c
 						     const float *__restrict__ cmPt, GBox *__restrict__ boxes, u32 beam,
 						     u32 *__restrict__ zero, u32 nzero, float4 *__restrict__ sray,
 						     const u32 *__restrict__ iincl, const u32 *__restrict__ span,
-						     const u32 *__restrict__ offset, CullItem *__restrict__ citems)
+						     const u32 *__restrict__ offset, CullItem *__restrict__ citems,
+						     u32 *__restrict__ bkt, u32 bkt_words, u32 sbits)
 {
 	__shared__ float s_box[BOX_WAVES][6];
 	for (u32 z = blockIdx.x * (64u * BOX_WAVES) + threadIdx.x; z < nzero; z += gridDim.x * (64u * BOX_WAVES))
@@ -278,6 +281,12 @@ __global__ __launch_bounds__(64 * BOX_WAVES) void k_shadow_boxes(CamBlock cam, c
 	// (the cull pass's items depend on the same two scans as the boxes: listed here instead of by a launch of their own)
 	d_cull_items_fill(iincl, gincl, span, offset, C, citems, blockIdx.x * (64u * BOX_WAVES) + threadIdx.x, gridDim.x * (64u * BOX_WAVES));
 	const u32 total = gincl[C - 1];
+	if (bkt) { // counted candidate buckets: the (beam, size class) counters the cull pass adds to, for the beams there are
+		const unsigned long long used = (unsigned long long)total << sbits;
+		const u32 nb = used < bkt_words ? (u32)used : bkt_words;
+		for (u32 z = blockIdx.x * (64u * BOX_WAVES) + threadIdx.x; z < nb; z += gridDim.x * (64u * BOX_WAVES))
+			bkt[z] = 0;
+	}
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const float cm[3] = { cmPt[0], cmPt[1], cmPt[2] };
 	const float inf = __builtin_huge_valf();
@@ -483,7 +492,7 @@ __global__ __launch_bounds__(64) void k_shadow_cull(CamBlock cam, const u32 *__r
 						    const float *__restrict__ verts, const int *__restrict__ tris,
 						    const GBox *__restrict__ boxes, u32 *__restrict__ pair_count, u32 pair_cap,
 						    u32 *__restrict__ pair_beam, u32 *__restrict__ pair_tri, u32 sbits,
-						    const CullItem *__restrict__ table)
+						    const CullItem *__restrict__ table, u32 *__restrict__ bkt, u32 gbound)
 {
 #pragma clang fp contract(fast) // cull arithmetic only (conservative by margin); no exact test in this kernel
 	// candidate pairs are staged in LDS and flushed PAIR_BUF at a time: one atomic on the shared
@@ -573,6 +582,8 @@ __global__ __launch_bounds__(64) void k_shadow_cull(CamBlock cam, const u32 *__r
 		const float mC = mA + mB + mD;
 		const u32 g0 = d_cur.gfirst, g1 = d_cur.gfirst + d_cur.gcount;
 		GBox nxt = boxes[g0]; // wave-uniform address: scalar loads
+		unsigned long long cls = 0ull; // counted buckets: the lanes of this lane's size class, and whether it is their first
+		bool cls_first = false, cls_ready = false;
 		for (u32 g = g0; g < g1; g++) {
 			const GBox bx = nxt;
 			// the next beam's box is requested before this one is used: its latency hides behind the test
@@ -597,6 +608,32 @@ __global__ __launch_bounds__(64) void k_shadow_cull(CamBlock cam, const u32 *__r
 					buf_tri[pos] = face;
 				}
 				nbuf += (u32)__popcll(mask);
+				// counted buckets (bkt): the kept lanes of each size class present, added to the beam's counter of that class
+				// by the class's first lane -- nothing comes back, the wave does not wait.  (beams past the bound the table
+				// was made for, asynchronous form: the pass is reported as overflowed and nothing is placed)
+				if (bkt && g < gbound) {
+					// (a lane's class is the same for every beam of the item: the lanes are sorted into their classes once
+					// per item, at its first kept pair -- a scalar loop of 1-3 rounds -- and a beam then costs the classes'
+					// first lanes a population count and an add)
+					if (!cls_ready) {
+						cls_ready = true;
+						unsigned long long left = __ballot(have);
+						while (left != 0ull) {
+							const u32 lc = (u32)__builtin_amdgcn_readlane((int)code, (int)__builtin_ctzll(left));
+							const unsigned long long same = __ballot(have && code == lc);
+							if (have && code == lc) {
+								cls = same;
+								cls_first = lane == (int)__builtin_ctzll(same);
+							}
+							left &= ~same;
+						}
+					}
+					if (cls_first) {
+						const u32 kept = (u32)__popcll(mask & cls);
+						if (kept)
+							atomicAdd(&bkt[(g << sbits) | code], kept);
+					}
+				}
 				if (nbuf > PAIR_BUF - 64u) {
 					d_flush_pairs(buf_beam, buf_tri, nbuf, lane, pair_count, pair_cap, pair_beam, pair_tri);
 					nbuf = 0;
@@ -672,26 +709,29 @@ struct PairItemLoad {
 // and ordered by SEGMENT first: all beams' first segments run before any second segment, so by the time a
 // later segment of a beam is picked up its rays have mostly been flagged by the earlier ones and the item
 // ends at its first ballot.  key = segment, value = beam << 7 | sub-group.
-__global__ __launch_bounds__(WL_THREADS) void k_pair_items(const u32 *__restrict__ xincl, u32 G, u32 cap,
-							    const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
-							    const GBox *__restrict__ boxes, u32 XSEG,
-							    u32 *__restrict__ item_seg, u32 *__restrict__ item_sub,
-							    u32 *__restrict__ status, RsFirst hs)
+// (runs as k_pair_items behind the pair sort, or as the workgroups [first, first + blocks) of k_pair_place: there the
+// beams' candidate runs are not written yet and are taken from the buckets' inclusive sums `bincl`)
+__device__ __forceinline__ void d_pair_items(u32 block, u32 blocks, const u32 *__restrict__ xincl, u32 G, u32 cap,
+					     const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
+					     const u32 *__restrict__ bincl, u32 sbits, const GBox *__restrict__ boxes, u32 XSEG,
+					     u32 *__restrict__ item_seg, u32 *__restrict__ item_sub, u32 *__restrict__ status,
+					     RsFirst hs)
 {
 	// (grid-stride; the workgroups also count the items' 8-bit keys for the sort that follows -- ugrt_rs_hist.h)
 	__shared__ u32 s_rsh[RS_BINS * RS_PRIV];
 	d_rs_zero(s_rsh, hs);
 	__syncthreads();
 	const u32 nitems = xincl[G - 1];
-	if (status && blockIdx.x == 0 && threadIdx.x == 0 && nitems > cap)
+	if (status && block == 0 && threadIdx.x == 0 && nitems > cap)
 		atomicOr(status, UGRT_STATUS_ITEM_OVERFLOW); // asynchronous form: the list was sized by an estimate
-	for (u32 i0 = blockIdx.x * WL_THREADS; i0 < cap; i0 += gridDim.x * WL_THREADS) {
+	for (u32 i0 = block * WL_THREADS; i0 < cap; i0 += blocks * WL_THREADS) {
 		const u32 it = i0 + threadIdx.x;
 		const bool ok = it < cap;
 		u32 seg = XSEG_LAST + 1u, sub = 0u; // the list is sorted at its capacity: padding goes last
 		if (ok && it < nitems) {
 			const u32 g = d_find_cell(xincl, G, it);
-			u32 nseg = (pend[g] - pstart[g] + XSEG - 1) / XSEG;
+			const u32 cand = bincl ? bincl[((g + 1u) << sbits) - 1u] - (g ? bincl[(g << sbits) - 1u] : 0u) : pend[g] - pstart[g];
+			u32 nseg = (cand + XSEG - 1) / XSEG;
 			nseg = nseg < XSEG_LAST + 1u ? nseg : XSEG_LAST + 1u;
 			const u32 nsub = (boxes[g].ray_count + 63u) / 64u;
 			const u32 local = it - (xincl[g] - nseg * nsub);
@@ -707,6 +747,221 @@ __global__ __launch_bounds__(WL_THREADS) void k_pair_items(const u32 *__restrict
 	}
 	__syncthreads();
 	d_rs_flush(s_rsh, hs);
+}
+
+__global__ __launch_bounds__(WL_THREADS) void k_pair_items(const u32 *__restrict__ xincl, u32 G, u32 cap,
+							    const u32 *__restrict__ pstart, const u32 *__restrict__ pend,
+							    const GBox *__restrict__ boxes, u32 XSEG,
+							    u32 *__restrict__ item_seg, u32 *__restrict__ item_sub,
+							    u32 *__restrict__ status, RsFirst hs)
+{
+	d_pair_items(blockIdx.x, gridDim.x, xincl, G, cap, pstart, pend, nullptr, 0u, boxes, XSEG, item_seg, item_sub, status, hs);
+}
+
+// COUNTED BUCKETS (option "shadow_pairs", the default).  A ray's flag is 1 iff any triangle of its cell occludes it, and
+// the exact pass wants a beam's candidates next to each other, large apparent size first: a bucketing by (beam, size
+// class), in which the order inside a bucket is free -- no sort.  The cull pass counts its kept pairs per bucket
+// (`bkt`, cleared by k_shadow_boxes), one launch scans the counts (`bincl`, inclusive: bucket k's run ends at bincl[k])
+// beside the exact pass's items per beam, and k_pair_place moves every staged triangle id to its bucket's run, taking
+// its place from the bucket's counter, which it counts down to zero again.  What k_pair_compact checked is checked
+// where the scan loads its input: every wave of the scan forms the pass's {pairs, beams} from the 64 staging cursors
+// and the beam count itself (no workgroup waits for another), the launch's first workgroup reports them.
+static_assert(PAIR_SEGS == 64u, "a wave sums the staging cursors, one per lane");
+#define SHADOW_BUCKET_WORDS (1u << 22) // (beam bound << size bits) up to which the pairs are counted: 16 MB of counters, as much of sums
+
+// {pairs, beams} of the pass and whether they fit what the launches behind the cull pass were made for (cap pairs,
+// gbound beams).  A staging segment that ran over makes a total that no buffer holds.  (whole waves only)
+__device__ __forceinline__ bool d_pair_totals(const u32 *__restrict__ segcnt, u32 segcap, const u32 *__restrict__ gcount,
+					      u32 cap, u32 gbound, u32 *P, u32 *G)
+{
+	const u32 c = segcnt[(threadIdx.x & 63u) * PAIR_SEG_STRIDE];
+	u32 sum = c < segcap ? c : segcap, over = c > segcap ? c : 0u;
+#pragma unroll
+	for (int m = 32; m >= 1; m >>= 1) {
+		sum += (u32)__shfl_xor((int)sum, m);
+		const u32 o = (u32)__shfl_xor((int)over, m);
+		over = o > over ? o : over;
+	}
+	const unsigned long long worst = (unsigned long long)over * PAIR_SEGS;
+	*P = over ? (worst > 0xFFFFFFF0ull ? 0xFFFFFFF0u : (u32)worst) : sum;
+	*G = *gcount;
+	return *P <= cap && *G <= gbound;
+}
+
+// input of the two scans behind the cull pass (ugrt_scan.h): ITEMS = false the buckets' counts (n = the table's words),
+// ITEMS = true the exact-pass items per beam as PairItemLoad forms them, from the counts of the beam's buckets
+struct PairBucketLoad {
+	const u32 *bkt, *segcnt;
+	u32 segcap;
+	const u32 *gcount;
+	u32 cap, gbound, sbits;
+	const GBox *boxes;
+	unsigned long long *staged;
+	u32 XSEG;
+	u32 *pair_count; // the pass's pairs, for the waiting form's read-back
+	PairCheck chk;   // asynchronous form (pg != nullptr): where the checked counts and the report go
+	bool ITEMS;
+	__device__ __forceinline__ void operator()(u32 base, u32 n, u32 (&v)[SC_ITEMS]) const
+	{
+		// (the counts are requested before the pass's totals are formed, for every bucket and beam the table has: what the
+		// totals rule out is dropped afterwards -- one round trip instead of two in front of the look-back)
+		u32 P, G;
+		if (!ITEMS) {
+			if (base + SC_ITEMS <= n) { // (the table is 16-byte aligned, base a multiple of 16)
+#pragma unroll
+				for (int q = 0; q < SC_ITEMS / 4; q++) {
+					const uint4 x = reinterpret_cast<const uint4 *>(bkt + base)[q];
+					v[4 * q] = x.x, v[4 * q + 1] = x.y, v[4 * q + 2] = x.z, v[4 * q + 3] = x.w;
+				}
+			} else {
+#pragma unroll
+				for (int k = 0; k < SC_ITEMS; k++)
+					v[k] = base + (u32)k < n ? bkt[base + k] : 0u;
+			}
+			const bool fits = d_pair_totals(segcnt, segcap, gcount, cap, gbound, &P, &G);
+			if (blockIdx.x == 0 && threadIdx.x == 0) { // (what k_pair_compact's first workgroup did)
+				pair_count[0] = P;
+				if (chk.pg) {
+					chk.report[0] = P;
+					chk.report[1] = G;
+					if (!fits)
+						atomicOr(chk.status, UGRT_STATUS_PAIR_OVERFLOW);
+					chk.pg[0] = fits ? P : 0u; // nothing is traced: the frame is reported as incomplete
+					chk.pg[1] = G;
+				}
+			}
+			const unsigned long long used = fits ? (unsigned long long)G << sbits : 0ull;
+#pragma unroll
+			for (int k = 0; k < SC_ITEMS; k++)
+				v[k] = base + (u32)k < used ? v[k] : 0u; // (beyond the pass's beams the table is not cleared)
+			return;
+		}
+		// a beam's candidates: the sum of its buckets.  The thread's 16 beams are loaded side by side, 16 bytes of each
+		// per round (the sums of 16 beams x 16 classes one after the other were 256 dependent round trips: 56 us)
+		u32 cands[SC_ITEMS], nsubs[SC_ITEMS];
+#pragma unroll
+		for (int k = 0; k < SC_ITEMS; k++)
+			cands[k] = nsubs[k] = 0u;
+		const u32 have = gbound < n ? gbound : n; // beams the table has
+		if (base < have) {
+#pragma unroll
+			for (int k = 0; k < SC_ITEMS; k++)
+				nsubs[k] = (boxes[base + (u32)k < have ? base + (u32)k : have - 1u].ray_count + 63u) / 64u;
+			if (sbits >= 2u) {
+				for (u32 q = 0; q < (1u << (sbits - 2u)); q++) {
+#pragma unroll
+					for (int k = 0; k < SC_ITEMS; k++) {
+						const u32 g = base + (u32)k < have ? base + (u32)k : have - 1u; // (clamped: no branch around the loads)
+						const uint4 x = reinterpret_cast<const uint4 *>(bkt + ((size_t)g << sbits))[q];
+						cands[k] += x.x + x.y + x.z + x.w;
+					}
+				}
+			} else {
+				for (u32 c = 0; c < (1u << sbits); c++) {
+#pragma unroll
+					for (int k = 0; k < SC_ITEMS; k++) {
+						const u32 g = base + (u32)k < have ? base + (u32)k : have - 1u;
+						cands[k] += bkt[(g << sbits) + c];
+					}
+				}
+			}
+		}
+		const bool fits = d_pair_totals(segcnt, segcap, gcount, cap, gbound, &P, &G);
+		const u32 Gn = fits && P ? G : 0u; // (no pairs: no items)
+		const u32 lim = Gn < n ? Gn : n;
+		unsigned long long mine = 0;
+#pragma unroll
+		for (int k = 0; k < SC_ITEMS; k++) {
+			const u32 g = base + (u32)k;
+			u32 x = 0;
+			if (g < lim) {
+				const u32 cand = cands[k], nsub = nsubs[k];
+				const u32 nseg = (cand + XSEG - 1) / XSEG;
+				x = (nseg < XSEG_LAST + 1u ? nseg : XSEG_LAST + 1u) * nsub;
+				mine += (unsigned long long)cand * nsub;
+			}
+			v[k] = x;
+		}
+		// candidates staged by the exact pass (work accounting): one atomic per wave
+#pragma unroll
+		for (int m = 32; m >= 1; m >>= 1)
+			mine += __shfl_xor(mine, m);
+		if ((threadIdx.x & 63) == 0 && mine)
+			atomicAdd(staged, mine);
+	}
+};
+
+// PLACE: the workgroups behind the first `nitemb` (a multiple of PAIR_SEGS of them) read the staging segments as the
+// cull pass left them and write each pair's triangle id to bincl[key] - (what is left of the bucket's counter) + (rank
+// among the wave's pairs of that key): the lanes of a wave are sorted into groups of equal keys first (scalar loop, no
+// memory), then the groups' first lanes take their places with ONE returning atomic each, all in flight together.  The
+// same workgroups write the beams' candidate runs for the exact pass.  The first `nitemb` workgroups list the exact
+// pass's items (d_pair_items), which depend on the scan alone: chains of dependent loads, started first so that they
+// run beside the placement, not behind it.
+__global__ __launch_bounds__(WL_THREADS) void k_pair_place(const u32 *__restrict__ segcnt, u32 segcap,
+							    const u32 *__restrict__ sbeam, const u32 *__restrict__ stri,
+							    u32 *__restrict__ pair_tri, u32 out_cap, u32 *__restrict__ bkt,
+							    const u32 *__restrict__ bincl, u32 bkt_words, u32 sbits,
+							    const u32 *__restrict__ pg, const u32 *__restrict__ gcount,
+							    u32 *__restrict__ pstart, u32 *__restrict__ pend, u32 nitemb,
+							    const u32 *__restrict__ xincl, u32 Gcap, u32 xcap,
+							    const GBox *__restrict__ boxes, u32 XSEG, u32 *__restrict__ item_seg,
+							    u32 *__restrict__ item_sub, u32 *__restrict__ status, RsFirst hs)
+{
+	if (blockIdx.x < nitemb) {
+		d_pair_items(blockIdx.x, nitemb, xincl, Gcap, xcap, nullptr, nullptr, bincl, sbits, boxes, XSEG, item_seg, item_sub, status, hs);
+		return;
+	}
+	const u32 block = blockIdx.x - nitemb, nplace = gridDim.x - nitemb;
+	if (pg && pg[0] == 0u) // asynchronous form: no pairs, or counts beyond what the pass was made for
+		return;
+	const u32 G = *gcount; // (<= the bound the table was made for: checked by the scan)
+	for (u32 g = block * WL_THREADS + threadIdx.x; g < G && ((g + 1u) << sbits) <= bkt_words; g += nplace * WL_THREADS) {
+		pstart[g] = g ? bincl[(g << sbits) - 1u] : 0u;
+		pend[g] = bincl[((g + 1u) << sbits) - 1u];
+	}
+	const int lane = threadIdx.x & 63;
+	const u32 seg = block % PAIR_SEGS, part = block / PAIR_SEGS, parts = nplace / PAIR_SEGS;
+	const u32 c = segcnt[seg * PAIR_SEG_STRIDE], n = c < segcap ? c : segcap;
+	const size_t src = (size_t)seg * segcap;
+	// (a round is three dependent round trips -- pair, place, store -- so the next round's pair is requested first)
+	u32 key_n = 0xFFFFFFFFu, tri_n = 0u;
+	if (part * WL_THREADS + threadIdx.x < n) {
+		key_n = sbeam[src + part * WL_THREADS + threadIdx.x];
+		tri_n = stri[src + part * WL_THREADS + threadIdx.x];
+	}
+	for (u32 i0 = part * WL_THREADS; i0 < n; i0 += parts * WL_THREADS) {
+		const u32 key = key_n, tri = tri_n, in = i0 + parts * WL_THREADS + threadIdx.x;
+		key_n = 0xFFFFFFFFu;
+		if (in < n) {
+			key_n = sbeam[src + in];
+			tri_n = stri[src + in];
+		}
+		const bool ok = key < bkt_words;
+		const u32 end = bincl[ok ? key : 0u]; // (requested beside the place, not behind it)
+		u32 leader = 0u, rank = 0u, cnt = 0u;
+		unsigned long long left = __ballot(ok);
+		while (left != 0ull) {
+			const int l = (int)__builtin_ctzll(left);
+			const u32 lk = (u32)__builtin_amdgcn_readlane((int)key, l);
+			const unsigned long long same = __ballot(ok && key == lk);
+			if (ok && key == lk) {
+				leader = (u32)l;
+				rank = d_rank_in_mask(same);
+				cnt = (u32)__popcll(same);
+			}
+			left &= ~same;
+		}
+		u32 old = 0u;
+		if (ok && (u32)lane == leader)
+			old = atomicSub(&bkt[key], cnt);
+		old = (u32)__shfl((int)old, (int)leader);
+		if (ok) {
+			const u32 pos = end - old + rank;
+			if (pos < out_cap)
+				pair_tri[pos] = tri;
+		}
+	}
 }
 
 // EXACT pass: item -> (beam, segment of its candidate list, 64-ray sub-group); lane = ray, the reference's test
@@ -943,8 +1198,14 @@ struct ShadowPass {
 	const u32 *pgp;        // device counts (asynchronous form; null otherwise)
 	u32 *status, *report;  // the status word on the device; the pinned host words of the pass's report
 	u32 *xincl, *iseg1, *isub1; // the exact pass's item list
+	// candidate pairs bucketed by counting (option "shadow_pairs") instead of sorted: the beam bound the bucket table is
+	// made for, its words, the counts and their inclusive sums; the cursors of the staging segments and a segment's room
+	bool counted;
+	u32 gbound, bkt_words, *bkt, *bincl, *segcnt, segcap;
+	const u32 *pair_tri; // the candidates' triangle ids in beam order, as the exact pass reads them
 	int traced_chunks(unsigned num_chunks);
 	int reserve();
+	int plan();       // 0. waiting or asynchronous, candidate pairs sorted or counted
 	int beams();      // 1. rays in (cell, direction code) order, runs per cell, beams and their boxes
 	int cull();       // 2. cull pass -> (beam, triangle) candidate pairs
 	int candidates(); // 3. candidates by beam, cut into the exact pass's items
@@ -1017,6 +1278,49 @@ int ShadowPass::reserve()
 	return UGRT_OK;
 }
 
+// 0. The form of the pass.  Synchronous form: the pair count is read back behind the cull pass (it sizes the
+// launches that follow), and the pass is repeated with a larger buffer if it was too small.  Asynchronous form
+// (option "async_build", once a synchronous pass has left estimates): no read-back; the launches are sized by
+// the previous pass's counts plus a quarter, the kernels take the real counts from the device, and counts
+// beyond the capacities raise a status bit instead (UGRT_EOVERFLOW at the next synchronisation).
+// The candidate pairs are counted into their (beam, size class) buckets unless "shadow_pairs" is 0, the library sorts,
+// or the table -- beam bound << size bits words, where the bound is every beam the rays could form in the waiting form
+// (the cull pass runs before the count is read back) and the power of two above the estimate in the asynchronous one --
+// would exceed SHADOW_BUCKET_WORDS: "shadow_sizebits" 8 on a huge light grid cannot ask for an unbounded table.
+int ShadowPass::plan()
+{
+	int rc;
+	own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1;
+	sbits = ctx->opt[UGRT_OPT_SHADOW_SIZEBITS] >= 0 ? (u32)ctx->opt[UGRT_OPT_SHADOW_SIZEBITS] : 4u;
+	sbits = sbits > 8u ? 8u : sbits;
+	if (ctx->shadow_async_pending) { // what the last asynchronous pass needed (possibly a frame old)
+		ctx->est_pairs = ctx->h_pinned[UGRT_PIN_SHADOW];
+		ctx->est_beams = ctx->h_pinned[UGRT_PIN_SHADOW + 1];
+	}
+	async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && ctx->have_shadow_est && ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen &&
+		!ctx->overflow_repair;
+	if (!async && ugrt_reported_status(ctx) != 0u)
+		ctx->overflow_seen = true;
+	gbound = (u32)maxg;
+	if (async) {
+		// beams: a power of two above the estimate keeps the sort at the key width the real count needs
+		u32 gb = 1;
+		while (gb < ctx->est_beams + ctx->est_beams / 4u + 1u)
+			gb <<= 1;
+		gbound = gb < gbound ? gb : gbound;
+	}
+	counted = ctx->opt[UGRT_OPT_SHADOW_PAIRS] != 0 && own_sort && ((unsigned long long)gbound << sbits) <= SHADOW_BUCKET_WORDS;
+	ctx->shadow_pairs_counted = counted;
+	if (counted) {
+		bkt_words = gbound << sbits;
+		const size_t half = ((size_t)bkt_words + 3u) / 4u * 4u; // (both halves 16-byte aligned)
+		if ((rc = ugrt_buf_reserve(ctx, ctx->pbkt, 2 * half * 4)))
+			return rc;
+		bkt = (u32 *)ctx->pbkt.p, bincl = bkt + half;
+	}
+	return UGRT_OK;
+}
+
 // 1. rays: (cell, direction code) order, runs per cell, beams
 int ShadowPass::beams()
 {
@@ -1031,7 +1335,6 @@ int ShadowPass::beams()
 	if (ctx->opt[UGRT_OPT_SHADOW_MBITS] > 0 && (u32)ctx->opt[UGRT_OPT_SHADOW_MBITS] < mbits)
 		mbits = (u32)ctx->opt[UGRT_OPT_SHADOW_MBITS];
 	mbits = mbits > 24u ? 24u : mbits;
-	own_sort = ctx->opt[UGRT_OPT_SORT_LIBRARY] != 1;
 	ctx->shadow_key_bits = (key64 ? 30u : mbits) + cellbits;
 	const u32 kblocks = (u32)((n + WL_THREADS - 1) / WL_THREADS) < 768u ? (u32)((n + WL_THREADS - 1) / WL_THREADS) : 768u;
 	// (the kernels that write this pass's sort keys count their first digit: no histogram kernel before the sorts;
@@ -1078,34 +1381,24 @@ int ShadowPass::beams()
 	hipLaunchKernelGGL(k_shadow_boxes, dim3(launch_blocks_for((u32)maxg)), dim3(64 * BOX_WAVES), 0, st, ctx->cam,
 			   (const u32 *)gincl, C, (const u32 *)rstart, (const u32 *)rend, (const u32 *)v1, d_t_value,
 			   d_ray_dir, d_cam_position, boxes, beam, pstart, (u32)(2 * maxg + maxg * (beam / 64u)),
-			   (float4 *)ctx->sray.p, (const u32 *)iincl, d_span, d_offset, (CullItem *)ctx->citem.p);
+			   (float4 *)ctx->sray.p, (const u32 *)iincl, d_span, d_offset, (CullItem *)ctx->citem.p,
+			   counted ? bkt : (u32 *)nullptr, bkt_words, sbits);
 	UGRT_HIP(hipGetLastError());
 	ugrt_prof_end(ctx, UGRT_ST_SHADOW_PREP);
 	return UGRT_OK;
 }
 
-// 2. cull pass -> (beam, triangle) candidate pairs.  Synchronous form: the pair count is read back (it sizes the
-// launches that follow), and the pass is repeated with a larger buffer if it was too small.  Asynchronous form
-// (option "async_build", once a synchronous pass has left estimates): no read-back; the launches are sized by
-// the previous pass's counts plus a quarter, the kernels take the real counts from the device, and counts
-// beyond the capacities raise a status bit instead (UGRT_EOVERFLOW at the next synchronisation).
+// 2. cull pass -> (beam, triangle) candidate pairs in the staging segments, and either their compaction (with the first
+// digit of the pair sort counted) or, counted buckets, the scan of the buckets' counts and of the exact pass's items per
+// beam.  The launch behind the cull pass makes the pass's checks and leaves the pair count for the waiting form.
 int ShadowPass::cull()
 {
 	int rc;
-	sbits = ctx->opt[UGRT_OPT_SHADOW_SIZEBITS] >= 0 ? (u32)ctx->opt[UGRT_OPT_SHADOW_SIZEBITS] : 4u;
-	sbits = sbits > 8u ? 8u : sbits;
 	u32 *pcount = ctx->d_small + UGRT_DSMALL_PAIRS; // right behind the work counters: cleared with them
 	// (the report is written by the kernels straight into the pinned host words: no copy behind the pass)
 	u32 *pg = ctx->d_small + UGRT_DSMALL_SHADOW;
 	status = ctx->d_small + UGRT_DSMALL_STATUS, report = ctx->h_pinned + UGRT_PIN_SHADOW;
-	if (ctx->shadow_async_pending) { // what the last asynchronous pass needed (possibly a frame old)
-		ctx->est_pairs = ctx->h_pinned[UGRT_PIN_SHADOW];
-		ctx->est_beams = ctx->h_pinned[UGRT_PIN_SHADOW + 1];
-	}
-	async = ctx->opt[UGRT_OPT_ASYNC_BUILD] == 1 && ctx->have_shadow_est && ugrt_reported_status(ctx) == 0u && !ctx->overflow_seen &&
-		!ctx->overflow_repair;
-	if (!async && ugrt_reported_status(ctx) != 0u)
-		ctx->overflow_seen = true;
+	xincl = (u32 *)ctx->witems.p;
 	size_t cap, want = (size_t)4 << 22; // bytes per candidate buffer
 	if (async && ((size_t)ctx->est_pairs + ctx->est_pairs / 2 + 65536) * 4 > want)
 		want = ((size_t)ctx->est_pairs + ctx->est_pairs / 2 + 65536) * 4;
@@ -1116,38 +1409,51 @@ int ShadowPass::cull()
 			return rc;
 		cap = std::min(std::min(ctx->tkey[0].cap, ctx->tkey[1].cap), std::min(ctx->tval[0].cap, ctx->tval[1].cap)) / 4;
 		cap = cap > 0xFFFFFFF0u ? 0xFFFFFFF0u : cap; // pairs that fit each of the four buffers
-		u32 *segcnt = (u32 *)ctx->pseg.p;
-		const u32 segcap = (u32)(cap / PAIR_SEGS);
-		if (attempt > 0) // (the first attempt's cursors were cleared by the keys kernel)
+		segcnt = (u32 *)ctx->pseg.p;
+		segcap = (u32)(cap / PAIR_SEGS);
+		if (attempt > 0) { // (the first attempt's cursors were cleared by the keys kernel, its buckets by the box kernel)
 			UGRT_HIP(hipMemsetAsync(segcnt, 0, (size_t)PAIR_SEGS * PAIR_SEG_STRIDE * 4, st));
+			if (counted)
+				UGRT_HIP(hipMemsetAsync(bkt, 0, (size_t)bkt_words * 4, st));
+		}
 		PairCheck chk = { nullptr, 0u, 0u, nullptr, nullptr, nullptr };
 		if (async) {
-			// beams: a power of two above the estimate keeps the sort at the key width the real count needs
-			u32 gb = 1;
-			while (gb < ctx->est_beams + ctx->est_beams / 4u + 1u)
-				gb <<= 1;
-			Gcap = (u32)maxg;
-			G = gb < Gcap ? gb : Gcap; // only its bit width is used below
+			// (counted buckets: no beam beyond the bound has items, the items' scan and the searches in it end there)
+			Gcap = counted ? gbound : (u32)maxg;
+			G = gbound; // only its bit width is used below
 			// launch size of the per-pair kernels; the check is made against it, not against the (larger) buffers:
 			// the sort and the run kernel work on P pairs, so a count between the two would lose candidates
 			const size_t lp = (size_t)ctx->est_pairs + ctx->est_pairs / 4 + 65536;
 			P = (u32)(lp < cap ? lp : cap);
-			chk = PairCheck{ (const u32 *)(gincl + (C - 1)), P, G, pg, status, report }; // (made by the compaction's first workgroup)
+			chk = PairCheck{ (const u32 *)(gincl + (C - 1)), P, G, pg, status, report }; // (made by the first workgroup behind the cull pass)
 		}
 		RsFirst hsp = { nullptr };
-		if (own_sort && (rc = ugrt_sort_first_digit(ctx, &hsp)))
+		if (!counted && own_sort && (rc = ugrt_sort_first_digit(ctx, &hsp)))
 			return rc;
 		ugrt_prof_begin(ctx, UGRT_ST_SHADOW_CULL);
 		hipLaunchKernelGGL(use_rec ? k_shadow_cull<true> : k_shadow_cull<false>,
 				   dim3(launch_blocks_for(0xFFFFFFFFu, ctx->opt[UGRT_OPT_SHADOW_WAVES])), dim3(64), 0, st, ctx->cam, (const u32 *)iincl,
 				   (const u32 *)gincl, C, d_span, d_offset, d_value_list, rec, d_vertlist, d_trilist,
 				   (const GBox *)boxes, segcnt, segcap, (u32 *)ctx->tkey[1].p, (u32 *)ctx->tval[1].p, sbits,
-				   (const CullItem *)ctx->citem.p);
-		hipLaunchKernelGGL(k_pair_compact, dim3(PAIR_SEGS * 16u), dim3(256), 0, st, (const u32 *)segcnt, segcap,
-				   (const u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[1].p, (u32 *)ctx->tkey[0].p,
-				   (u32 *)ctx->tval[0].p, pcount, chk, hsp);
+				   (const CullItem *)ctx->citem.p, counted ? bkt : (u32 *)nullptr, gbound);
+		if (!counted)
+			hipLaunchKernelGGL(k_pair_compact, dim3(PAIR_SEGS * 16u), dim3(256), 0, st, (const u32 *)segcnt, segcap,
+					   (const u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[1].p, (u32 *)ctx->tkey[0].p,
+					   (u32 *)ctx->tval[0].p, pcount, chk, hsp);
 		ugrt_prof_end(ctx, UGRT_ST_SHADOW_CULL);
 		UGRT_HIP(hipGetLastError());
+		if (counted) {
+			// (the pairs a segment holds, the beams the table was made for: what the waiting form's launches can take)
+			PairBucketLoad la = { bkt, segcnt, segcap, (const u32 *)(gincl + (C - 1)), async ? P : segcap * PAIR_SEGS, gbound, sbits, boxes,
+					      wcnt + 1, XSEG, pcount, chk, false };
+			PairBucketLoad lb = la;
+			lb.ITEMS = true;
+			ugrt_prof_begin(ctx, UGRT_ST_SHADOW_PREP);
+			rc = ugrt_scan_launch_pair<true>(ctx, la, bincl, lb, xincl, bkt_words, async ? (size_t)gbound : maxg);
+			ugrt_prof_end(ctx, UGRT_ST_SHADOW_PREP);
+			if (rc)
+				return rc;
+		}
 		if (async) {
 			pgp = pg; // (the report travels to the host with the copy behind the exact pass)
 			xcap = (ctx->est_beams + ctx->est_beams / 4u + 64u + P / XSEG) * (beam / 64u);
@@ -1179,24 +1485,24 @@ int ShadowPass::cull()
 	return UGRT_OK;
 }
 
-// 3. candidates by beam
+// 3. candidates by beam, cut into the exact pass's items
 int ShadowPass::candidates()
 {
 	int rc;
 	ugrt_prof_begin(ctx, UGRT_ST_SHADOW_PREP);
-	if ((rc = own_sort ? ugrt_sort_pairs_u32(ctx, (const u32 *)ctx->tkey[0].p, (u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[0].p,
-						 (u32 *)ctx->tval[1].p, P, bits_of(G) + (int)sbits, pgp, true)
-			   : ugrt_prim_sort_pairs(ctx, (const u32 *)ctx->tkey[0].p, (u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[0].p,
-						  (u32 *)ctx->tval[1].p, P, bits_of(G) + (int)sbits, pgp)))
-		return rc;
-	{
-		u32 pb = (P + WL_THREADS - 1) / WL_THREADS;
-		hipLaunchKernelGGL(k_pair_runs, dim3(pb ? pb : 1u), dim3(WL_THREADS), 0, st, (const u32 *)ctx->tkey[1].p, P, sbits,
-				   pstart, pend, pgp);
-	}
-	UGRT_HIP(hipGetLastError());
-	xincl = (u32 *)ctx->witems.p;
-	{
+	if (!counted) {
+		if ((rc = own_sort ? ugrt_sort_pairs_u32(ctx, (const u32 *)ctx->tkey[0].p, (u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[0].p,
+							 (u32 *)ctx->tval[1].p, P, bits_of(G) + (int)sbits, pgp, true)
+				   : ugrt_prim_sort_pairs(ctx, (const u32 *)ctx->tkey[0].p, (u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[0].p,
+							  (u32 *)ctx->tval[1].p, P, bits_of(G) + (int)sbits, pgp)))
+			return rc;
+		pair_tri = (const u32 *)ctx->tval[1].p;
+		{
+			u32 pb = (P + WL_THREADS - 1) / WL_THREADS;
+			hipLaunchKernelGGL(k_pair_runs, dim3(pb ? pb : 1u), dim3(WL_THREADS), 0, st, (const u32 *)ctx->tkey[1].p, P, sbits,
+					   pstart, pend, pgp);
+		}
+		UGRT_HIP(hipGetLastError());
 		const PairItemLoad load = { pstart, pend, boxes, G, wcnt + 1, XSEG, pgp };
 		if ((rc = ugrt_scan_launch<true>(ctx, load, xincl, Gcap, ScanTailNone())))
 			return rc;
@@ -1209,9 +1515,18 @@ int ShadowPass::candidates()
 	RsFirst hsi = { nullptr };
 	if (item_sort && own_sort && (rc = ugrt_sort_first_digit(ctx, &hsi)))
 		return rc;
-	{
-		const u32 ib = (xcap + WL_THREADS - 1) / WL_THREADS;
-		hipLaunchKernelGGL(k_pair_items, dim3(ib < 512u ? (ib ? ib : 1u) : 512u), dim3(WL_THREADS), 0, st,
+	const u32 ib = (xcap + WL_THREADS - 1) / WL_THREADS, iblocks = ib < 512u ? (ib ? ib : 1u) : 512u;
+	if (counted) {
+		// the staged ids (tval[1], keys tkey[1]) go to their buckets' runs in tval[0]; the items are listed by the same launch
+		const u32 nplace = PAIR_SEGS * 32u; // (8192 waves: what the device holds at once)
+		pair_tri = (const u32 *)ctx->tval[0].p;
+		hipLaunchKernelGGL(k_pair_place, dim3(nplace + iblocks), dim3(WL_THREADS), 0, st, (const u32 *)segcnt, segcap,
+				   (const u32 *)ctx->tkey[1].p, (const u32 *)ctx->tval[1].p, (u32 *)ctx->tval[0].p,
+				   (u32)std::min(ctx->tval[0].cap / 4, (size_t)0xFFFFFFF0u), bkt, (const u32 *)bincl, bkt_words, sbits, pgp,
+				   (const u32 *)(gincl + (C - 1)), pstart, pend, iblocks, (const u32 *)xincl, Gcap, xcap, (const GBox *)boxes,
+				   XSEG, iseg0, isub0, async ? status : (u32 *)nullptr, hsi);
+	} else {
+		hipLaunchKernelGGL(k_pair_items, dim3(iblocks), dim3(WL_THREADS), 0, st,
 				   (const u32 *)xincl, Gcap, xcap, (const u32 *)pstart, (const u32 *)pend, (const GBox *)boxes, XSEG,
 				   iseg0, isub0, async ? status : (u32 *)nullptr, hsi);
 	}
@@ -1286,7 +1601,7 @@ int ShadowPass::exact()
 #endif
 	hipLaunchKernelGGL(use_rec ? k_trace_shadow<true> : k_trace_shadow<false>, dim3(xwaves), dim3(64), 0, st, ctx->cam,
 			   (const u32 *)xincl, Gcap, (const u32 *)iseg1, (const u32 *)isub1, (const GBox *)boxes, (const u32 *)pstart, (const u32 *)pend,
-			   (const u32 *)ctx->tval[1].p, d_vertlist, d_trilist, rec, d_t_value, d_ray_dir, d_is_shadowed,
+			   pair_tri, d_vertlist, d_trilist, rec, d_t_value, d_ray_dir, d_is_shadowed,
 			   (const u32 *)v1, d_cam_position, XSEG, pend + maxg, beam / 64u,
 			   (const float4 *)ctx->sray.p, xcap, report, (const u32 *)status, (const unsigned long long *)wcnt, xslices, xw0,
 			   x_sieve > 64u ? 64u : x_sieve, xnsieve);
@@ -1324,7 +1639,7 @@ extern "C" int ugrt_trace_shadow(ugrt_ctx *ctx, const unsigned *d_value_list, co
 		return UGRT_OK;
 	s.rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
 	s.use_rec = s.rec != nullptr;
-	if ((rc = s.reserve()) || (rc = s.beams()) || (rc = s.cull()))
+	if ((rc = s.reserve()) || (rc = s.plan()) || (rc = s.beams()) || (rc = s.cull()))
 		return rc;
 	if (!s.async && (s.P == 0 || s.G == 0))
 		return UGRT_OK;
