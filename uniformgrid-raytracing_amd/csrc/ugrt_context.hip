@@ -106,6 +106,16 @@ extern "C" int ugrt_ctx_create(ugrt_ctx **out, int device, const ugrt_config *cf
 		if (e != hipSuccess)
 			rc = ugrt_fail(UGRT_EHIP, "ctx_create: %s", hipGetErrorString(e));
 	}
+	// per cell of the screen grid (indexed like the spans; a band uses its own cells' words): how many of a split
+	// cell's segment waves have yet to merge their hits (the last one finishes the tile); zero between traces
+	const size_t ncell = (size_t)nbx * (size_t)nby;
+	if (!rc)
+		rc = ugrt_buf_reserve(ctx, ctx->pdone, ncell * sizeof(u32));
+	if (!rc) {
+		e = hipMemset(ctx->pdone.p, 0, ncell * sizeof(u32));
+		if (e != hipSuccess)
+			rc = ugrt_fail(UGRT_EHIP, "ctx_create: %s", hipGetErrorString(e));
+	}
 	if (rc) {
 		ugrt_ctx_destroy(ctx);
 		return rc;
@@ -150,6 +160,7 @@ extern "C" void ugrt_ctx_destroy(ugrt_ctx *ctx)
 	buf_free(ctx->dsort);
 	buf_free(ctx->dsplit);
 	buf_free(ctx->best);
+	buf_free(ctx->pdone);
 	buf_free(ctx->rmap[0]);
 	buf_free(ctx->rmap[1]);
 	buf_free(ctx->rstart);
@@ -227,7 +238,23 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = (long long)ctx->uniform_reused;
 	else if (strcmp(key, "light_builds_reused") == 0)
 		*value = (long long)ctx->light_reused;
-	else if (strcmp(key, "recip_mismatches") == 0) {
+	else if (strcmp(key, "primary_slots_unarmed") == 0) {
+		// (tests) merge slots of the primary pass that are not all ones + segment counters that are not zero: between
+		// traces there is none, the wave that finishes a split cell's tile leaves both so
+		const size_t ncell = (size_t)ctx->nbx * (size_t)ctx->nby;
+		std::vector<u64> b((size_t)ctx->npix);
+		std::vector<u32> d(ncell);
+		UGRT_HIP(hipSetDevice(ctx->device));
+		UGRT_HIP(hipStreamSynchronize(ctx->stream));
+		UGRT_HIP(hipMemcpy(b.data(), ctx->best.p, b.size() * sizeof(u64), hipMemcpyDeviceToHost));
+		UGRT_HIP(hipMemcpy(d.data(), ctx->pdone.p, d.size() * sizeof(u32), hipMemcpyDeviceToHost));
+		long long bad = 0;
+		for (u64 v : b)
+			bad += v != ~0ull;
+		for (u32 v : d)
+			bad += v != 0u;
+		*value = bad;
+	} else if (strcmp(key, "recip_mismatches") == 0) {
 		// exhaustive: every float through the tracers' short reciprocal against the division (ugrt_dev.h d_recip_det)
 		unsigned long long bad = 0;
 		const int rc = ugrt_recip_selftest(ctx, &bad);

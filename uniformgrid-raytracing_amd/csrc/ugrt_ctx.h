@@ -214,6 +214,7 @@ struct ugrt_ctx {
 	// without the split-walk history (it neither reads nor replaces the history of the level-1 launches: DESIGN.md 6.1)
 	bool dda_deeper_level = false;
 	DevBuf best;                  // u64 per pixel: (t bits << 32 | ref) for split cells
+	DevBuf pdone;                 // u32 per cell of the screen grid: segment waves of a split cell that have yet to merge their hits (0 between traces)
 	DevBuf rmap[2];               // ray sort ping-pong (2n u32 each)
 	DevBuf rstart, cbase; // ray runs per light cell (sort_rays)
 	DevBuf skey[2], sval[2], sdesc, sstart, sbase; // shadow tracer: re-grouped rays, beams, counts

@@ -68,6 +68,7 @@ struct WlPrimaryStoreT {
 	const u32 *span, *offset;
 	u32 nby, gy_lo, rows, SEG;
 	WItem *items;
+	u32 *left; // per cell: segment waves of a split cell that have not merged their hits yet (k_trace_primary counts it down)
 	__device__ __forceinline__ void operator()(u32 base, u32 n, const u32 (&v)[SC_ITEMS], const u32 (&incl)[SC_ITEMS]) const
 	{
 		for (int k = 0; k < SC_ITEMS; k++) {
@@ -78,6 +79,8 @@ struct WlPrimaryStoreT {
 			const u32 cell = cx * nby + cy;
 			const u32 sp = span[cell], off = REL ? 0u : offset[cell], cnt = v[k];
 			const u32 first = incl[k] - cnt;
+			if (cnt > 1)
+				left[cell] = cnt;
 			for (u32 s = 0; s < cnt; s++) {
 				WItem w;
 				w.cell = cell;
@@ -191,15 +194,22 @@ static_assert(PS_END <= UGRT_PRIMARY_STATS, "primary work counters");
 // order), so "the first of the list wins" and "the smaller id wins" are the same rule -- and a minimum over ids does
 // not care in which order the stream delivers them, which is what lets the wide triangles come last and unordered.
 // The position-keyed instantiations stay for lists a caller supplies, which need not be ascending.
+// Registers: launch bounds of FIVE waves per SIMD, 96 registers, although a CU's LDS holds 16 of these one-wave
+// workgroups = four per SIMD either way.  In the frame the waves of other streams' kernels share the SIMDs with these, and
+// what four waves leave of the 512 registers is what those get: 32 at 120 (113 to 120 registers are allocated as 120),
+// 64 at 112, 128 at 96.  Measured on the bench frame, four frames in flight (profiles/primary_finish_bench.txt): 113
+// registers 0.7444 ms, 109 registers 0.7331, 96 registers 0.7204, each against 0.735 to 0.738 of the build before.  So
+// nothing may be held across the flushes that can be had again: the ray's direction is read back from s_dir, the pixel's
+// index is formed at the end, the all-ones word per item.  tools/kernel_resources.py shows the count; 97 would spill.
 template <bool REC, bool WIDE, bool COUNT>
-__global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const float *__restrict__ tex,
+__global__ __launch_bounds__(64, 5) void k_trace_primary(CamBlock cam, const float *__restrict__ tex,
 						       const WItem *__restrict__ items,
 						       const u32 *__restrict__ nitems_p,
 						       const u32 *__restrict__ value_list,
 						       const float *__restrict__ verts, const int *__restrict__ tris,
 						       const float4 *__restrict__ rec, PrimaryOut out,
 						       u64 *__restrict__ best, int p0, unsigned long long *__restrict__ counters,
-						       u32 ORDER, u32 CHUNK, u32 SLICES, WideSrc ws)
+						       u32 ORDER, u32 CHUNK, u32 SLICES, WideSrc ws, u32 *__restrict__ left)
 {
 	__shared__ __attribute__((aligned(16))) float lds[SURV_CAP * TRI_STRIDE];
 	__shared__ unsigned short jobs[JOB_CAP]; // survivor slot | lane offset of the quadrant << 7
@@ -270,9 +280,8 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 			id_next = fetch(min((u32)lane, last));
 		const int bx = (int)(w.multi >> 16), by = (int)((w.multi >> 1) & 0x7FFFu);
 		const int col = bx * 8 + (lane & 7), row = by * 8 + (lane >> 3);
-		const int pixelID = row * cam.W + col;
-		float dir[3];
-		d_ray_dir(cam, tex, col, row, dir);
+		float dir0[3];
+		d_ray_dir(cam, tex, col, row, dir0);
 		if (REC && w.count) {
 			ra = rec[id_next * 3u + 0u];
 			rb = rec[id_next * 3u + 1u];
@@ -289,7 +298,7 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 #pragma unroll
 		for (int k = 0; k < 3; k++) {
 			// (through the order-preserving int images of the floats: integer min / max fold into the DPP instruction)
-			const int ilo = d_quadrant_reduce<DOpMin>(d_ordered(dir[k])), ihi = d_quadrant_reduce<DOpMax>(d_ordered(dir[k]));
+			const int ilo = d_quadrant_reduce<DOpMin>(d_ordered(dir0[k])), ihi = d_quadrant_reduce<DOpMax>(d_ordered(dir0[k]));
 			float lo = d_unordered(ilo), hi = d_unordered(ihi);
 			const float qc = 0.5f * (lo + hi);
 			const float qr = 0.5f * (hi - lo) * 1.0001f + 1e-6f; // far more than the rounding of c and r
@@ -305,10 +314,15 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 				qb[q].r[k] = d_readlane(qr, src);
 			}
 		}
-		s_dir[lane * 3 + 0] = dir[0];
-		s_dir[lane * 3 + 1] = dir[1];
-		s_dir[lane * 3 + 2] = dir[2];
-		s_best[lane] = ~0ull;
+		s_dir[lane * 3 + 0] = dir0[0];
+		s_dir[lane * 3 + 1] = dir0[1];
+		s_dir[lane * 3 + 2] = dir0[2];
+		{
+			// (the all-ones word is made here: as a constant the compiler keeps it in two registers across every flush)
+			u32 ones;
+			asm volatile("v_mov_b32 %0, -1" : "=v"(ones));
+			s_best[lane] = ((unsigned long long)ones << 32) | ones;
+		}
 		u32 nsurv = 0, njobs = 0;
 		// per quadrant: the farthest of its 16 rays' closest hits so far (NaN while a ray has none)
 		float qfar[4] = { __uint_as_float(~0u), __uint_as_float(~0u), __uint_as_float(~0u), __uint_as_float(~0u) };
@@ -516,12 +530,38 @@ __global__ __launch_bounds__(64, 4) void k_trace_primary(CamBlock cam, const flo
 			njobs = 0;
 		}
 		const unsigned long long mine = s_best[lane];
+		const int pixelID = (by * 8 + (lane >> 3)) * cam.W + bx * 8 + (lane & 7);
+		// (the ray's direction is read back from where the rounds read it: three registers less across the flushes)
+		const float dir[3] = { s_dir[lane * 3 + 0], s_dir[lane * 3 + 1], s_dir[lane * 3 + 2] };
 		if (!(w.multi & 1u)) {
 			const bool hit = mine != ~0ull;
 			d_finish_pixel<REC, WIDE>(cam, out, pixelID, dir, hit ? __uint_as_float((u32)(mine >> 32)) : 99999999.9f,
 					    hit ? (u32)mine : 0xFFFFFFFFu, value_list, verts, tris, rec);
-		} else if (mine != ~0ull) {
-			atomicMin(reinterpret_cast<unsigned long long *>(&best[pixelID - p0]), mine);
+		} else {
+			// A split cell: the segments' waves merge their hits in best[], and the one that arrives last finishes the
+			// tile.  left[cell] holds the number of the cell's segments (the work list's scan wrote it with the items).  Every
+			// wave waits until its atomics have been acknowledged, then takes 1 off; the wave whose subtraction returns 1
+			// knows that all others have subtracted, so that their minima are in: it takes each pixel's merged word with an
+			// exchange against ~0 (which re-arms the slot) and finishes the pixel.  The counter is then 0, as it is between
+			// traces.  Nobody waits for anybody, and the order of the waves does not matter.
+			// What is handed over are device-scope atomics on both sides, performed in L2 and beyond, so no cache has to be
+			// written back (as for the scans' last tile, ugrt_scan.h): a release fence here writes back every dirty line of
+			// the XCD's L2, the finished pixels of all other tiles, once per split item, and the frame was 1 % slower for it.
+			unsigned long long *slot = reinterpret_cast<unsigned long long *>(&best[pixelID - p0]);
+			if (mine != ~0ull)
+				atomicMin(slot, mine);
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+			u32 before = 0;
+			if (lane == 0)
+				before = __hip_atomic_fetch_sub(left + w.cell, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			before = (u32)__builtin_amdgcn_readfirstlane((int)before);
+			if (before == 1u) {
+				__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+				const unsigned long long m = __hip_atomic_exchange(slot, ~0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				const bool hit = m != ~0ull;
+				d_finish_pixel<REC, WIDE>(cam, out, pixelID, dir, hit ? __uint_as_float((u32)(m >> 32)) : 99999999.9f,
+						    hit ? (u32)m : 0xFFFFFFFFu, value_list, verts, tris, rec);
+			}
 		}
 	}
 	if (COUNT && lane == 0)
@@ -638,34 +678,6 @@ __global__ __launch_bounds__(64) void k_trace_primary_slabs(CamBlock cam, const 
 	}
 }
 
-// pixels of split cells: take the merged (t, ref), finish, re-arm the slot (WIDE: ref is the triangle itself)
-template <bool REC, bool WIDE>
-__global__ __launch_bounds__(256) void k_resolve_primary(CamBlock cam, const float *__restrict__ tex,
-							  const u32 *__restrict__ span,
-							  const u32 *__restrict__ value_list,
-							  const float *__restrict__ verts, const int *__restrict__ tris,
-							  const float4 *__restrict__ rec, PrimaryOut out,
-							  u64 *__restrict__ best, int p0, int npix, u32 SEG)
-{
-	int i = blockIdx.x * 256 + threadIdx.x;
-	if (i >= npix)
-		return;
-	int pixelID = p0 + i;
-	int col = pixelID % cam.W, row = pixelID / cam.W;
-	u32 cell = (u32)(col >> 3) * (u32)cam.nby + (u32)(row >> 3);
-	if (span[cell] <= SEG)
-		return;
-	u64 b = best[i];
-	best[i] = ~0ull;
-	float dir[3];
-	d_ray_dir(cam, tex, col, row, dir);
-	u32 ref = (u32)(b & 0xFFFFFFFFull);
-	float oldt = (b == ~0ull) ? 99999999.9f : __uint_as_float((u32)(b >> 32));
-	if (b == ~0ull)
-		ref = 0xFFFFFFFFu;
-	d_finish_pixel<REC, WIDE>(cam, out, pixelID, dir, oldt, ref, value_list, verts, tris, rec);
-}
-
 // total refs behind a span/offset pair: known for the context's own grids,
 // read back (one 8-byte copy) for arrays that came from elsewhere
 static int refs_of(ugrt_ctx *ctx, const u32 *d_span, const u32 *d_offset, u32 C, u32 *R)
@@ -683,11 +695,9 @@ static int refs_of(ugrt_ctx *ctx, const u32 *d_span, const u32 *d_offset, u32 C,
 	return UGRT_OK;
 }
 
-// the two kernels of a trace, in their position-keyed or id-keyed (WideSrc) instantiations
+// the kernel of a trace, in its position-keyed or id-keyed (WideSrc) instantiations
 typedef void (*TraceKernel)(CamBlock, const float *, const WItem *, const u32 *, const u32 *, const float *, const int *,
-			    const float4 *, PrimaryOut, u64 *, int, unsigned long long *, u32, u32, u32, WideSrc);
-typedef void (*ResolveKernel)(CamBlock, const float *, const u32 *, const u32 *, const float *, const int *, const float4 *,
-			      PrimaryOut, u64 *, int, int, u32);
+			    const float4 *, PrimaryOut, u64 *, int, unsigned long long *, u32, u32, u32, WideSrc, u32 *);
 template <bool WIDE>
 static TraceKernel trace_kernel_of(bool use_rec, bool counting)
 {
@@ -726,7 +736,7 @@ static int trace_primary_run(ugrt_ctx *ctx, const unsigned *d_value_list, const 
 	if (rc)
 		return rc;
 	// triangles per work item: long cells are cut into segments that run on different waves and are
-	// merged with atomicMin + a resolve pass; cells up to SEG triangles finish inside their one wave.
+	// merged with atomicMin, the last of them to arrive finishes the tile; cells up to SEG triangles finish inside their one wave.
 	// Every cell of a closed scene carries the few hundred eye-plane-straddling triangles (Q9), so the
 	// cut-off sits above that baseline.
 	u32 SEG = ctx->opt[UGRT_OPT_PRIMARY_SEG] > 0 ? (u32)ctx->opt[UGRT_OPT_PRIMARY_SEG] : 1024u;
@@ -742,8 +752,8 @@ static int trace_primary_run(ugrt_ctx *ctx, const unsigned *d_value_list, const 
 	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
 	{
 		const WlPrimaryLoad load = { d_span, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG };
-		const WlPrimaryStore store = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items };
-		const WlPrimaryStoreT<true> store_rel = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items };
+		const WlPrimaryStore store = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items, (u32 *)ctx->pdone.p };
+		const WlPrimaryStoreT<true> store_rel = { d_span, d_offset, (u32)ctx->nby, (u32)ctx->cfg.row_begin, (u32)rows, SEG, items, (u32 *)ctx->pdone.p };
 		if ((rc = wide ? ugrt_scan_launch<true>(ctx, load, incl, ncell, ScanTailNone(), store_rel)
 			       : ugrt_scan_launch<true>(ctx, load, incl, ncell, ScanTailNone(), store)))
 			return rc;
@@ -783,18 +793,11 @@ static int trace_primary_run(ugrt_ctx *ctx, const unsigned *d_value_list, const 
 	hipLaunchKernelGGL(kernel, dim3(pwaves), dim3(64), 0, st, ctx->cam, tex, (const WItem *)items,
 			   (const u32 *)(incl + (ncell - 1)), d_value_list, d_vertlist, d_trilist, rec, out, (u64 *)ctx->best.p,
 			   ctx->p0, pc, p_order, p_chunk,
-			   p_slices ? 1u : (p_run ? ((p_run_log2 + 1u) << 1) | (ctx->opt[UGRT_OPT_PRIMARY_CENTRE] != 0 ? 1u : 0u) : 0u), ws);
+			   p_slices ? 1u : (p_run ? ((p_run_log2 + 1u) << 1) | (ctx->opt[UGRT_OPT_PRIMARY_CENTRE] != 0 ? 1u : 0u) : 0u), ws,
+			   (u32 *)ctx->pdone.p);
 	if (counting)
 		UGRT_HIP(hipMemcpyAsync(ctx->primary_stats, pc, UGRT_PRIMARY_STATS * 8, hipMemcpyDeviceToHost, st));
 	ugrt_prof_end(ctx, UGRT_ST_TRACE_PRIMARY);
-	UGRT_HIP(hipGetLastError());
-	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const ResolveKernel resolve = wide ? (use_rec ? k_resolve_primary<true, true> : k_resolve_primary<false, true>)
-					   : (use_rec ? k_resolve_primary<true, false> : k_resolve_primary<false, false>);
-	hipLaunchKernelGGL(resolve, dim3((ctx->npix + 255) / 256),
-			   dim3(256), 0, st, ctx->cam, tex, d_span, d_value_list, d_vertlist, d_trilist, rec, out,
-			   (u64 *)ctx->best.p, ctx->p0, ctx->npix, SEG);
-	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
 	UGRT_HIP(hipGetLastError());
 	ctx->stats[0] = cap; // upper bound of primary work items
 	return UGRT_OK;
