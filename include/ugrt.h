@@ -811,6 +811,61 @@ int ugrt_gi_filter(ugrt_ctx *ctx, const unsigned *d_sum, const float *d_orays, c
 int ugrt_gi_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_dirs, float gain,
 		  const int *d_intersect_id, const float *d_mat_list, int num_materials);
 
+/* ---- device: adaptive anti-aliasing, sub-pixel eye rays on edge pixels ----
+ * The frame takes one eye ray per pixel, through the pixel's corner.  ugrt_aa_edges finds the pixels that lie on an edge,
+ * ugrt_aa_gather sends num_samples sub-pixel eye rays through each of them and through the uniform grid and shades every
+ * sample as the frame shades a primary hit, ugrt_aa_resolve puts the mean into the image.  A sample with the offset (0, 0)
+ * IS the pixel's primary hit, so supersampled and untouched pixels join without a seam.  Per frame: the primary pass and
+ * the shadow stage, ugrt_aa_edges, the uniform grid, ugrt_aa_gather, the shading calls, ugrt_aa_resolve.  All arithmetic
+ * is fp32 without contraction or unsigned 32-bit integer. */
+#define UGRT_MAX_AA_SAMPLES 32
+#define UGRT_MAX_AA_SET_TILE 4 /* set_w, set_h */
+/* The edge flags, for the context's band; called BEFORE the frame's shading call, while d_intersect_id holds triangle ids.
+ * With hit(x) = d_t_value[x] > 0 && d_intersect_id[x] >= 0, P_x = d_cam_position + d_t_value[x] * d_ray_dir[3x ..] per
+ * component and n_x = d_normal[3x ..] as stored (component-wise absolute): d_edge[p] = 1 when for one of the up to eight
+ * neighbours q of p inside the image (rows outside the band are read)
+ *   hit(p) != hit(q), or
+ *   both hit, the triangle ids differ and one of: d_mat_idx of the two ids differs;
+ *     (n_p0*n_q0 + n_p1*n_q1) + n_p2*n_q2 < normal_cos;
+ *     fabsf((n_p0*(P_q0-P_p0) + n_p1*(P_q1-P_p1)) + n_p2*(P_q2-P_p2)) > plane_tol, or
+ *   d_is_shadowed (may be NULL) is given and d_is_shadowed[p] != d_is_shadowed[q];
+ * otherwise d_edge[p] = 0 (a miss among misses gets 0).  Pixels outside the band are not written.  Stage UGRT_ST_SHADE.
+ * A tolerance that is a NaN or a null argument other than d_is_shadowed: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_aa_edges(ugrt_ctx *ctx, const float *d_normal, const float *d_t_value, const float *d_ray_dir,
+		  const int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx, const int *d_is_shadowed,
+		  float normal_cos, float plane_tol, int *d_edge);
+/* The sub-pixel eye rays of the pixels of the band with d_edge[p] != 0.  eye_camcoords is the EYE's camera block (host
+ * memory, float[64]): when a frame shades, the context's current block is the light camera's, which the shading below
+ * reads; the directions and the depth gate need the eye's.  Sample s of pixel p = (col, row) = (p % width, p / width):
+ * the origin is eye_camcoords[0..2]; the direction is the primary pass's (the 5x5 node table of
+ * ugrt_camera_direction_table(eye_camcoords), UGRT_FLAG_STRICT_TEXTURE included) with (float)col + sx and (float)row + sy
+ * in the place of (float)col and (float)row, (sx, sy) = d_offsets[2 * (k(p) * num_samples + s) ..], k(p) =
+ * (row % set_h) * set_w + (col % set_w); d_offsets is DEVICE memory, [set_w * set_h][num_samples][2] floats in
+ * [-0.5, 0.5) (a value outside [-0.5, 0.5] is clamped to it, a NaN counts as -0.5).  The hit is ugrt_trace_dda's -- the same cells, list order, a test accepted with 0 < t < best, the same end
+ * of the walk -- and counts only where the primary epilogue's depth gate passes under the eye's MVP.  A miss, or a hit
+ * whose material d_mat_idx[hit] is outside 0..num_materials-1, has the colour 0; otherwise the bytes are what
+ * ugrt_shade_simple gives a primary hit of that triangle at {eye, direction, t}: the normal as ugrt_trace_primary stores it,
+ * the point eye + t * direction, the Lambert term under the context's CURRENT camera block and ugrt_set_light_position's
+ * light, clamped.  With shadow_light (host float[3]; NULL: no shadow phase) each byte b becomes b / 3 where
+ * ugrt_trace_dda_any(t_max = 1) flags the ray ugrt_occlusion_rays forms from {eye, direction}, t, the triangle,
+ * shadow_light and eps.  d_sum, unsigned [4 * width * height], 16-byte aligned: for a flagged pixel d_sum[4p + k],
+ * k = 0..2, is the sum over s of byte k and d_sum[4p + 3] = 1; the other pixels of the band get four zeros, pixels outside
+ * the band are not written.  The index space, the prepare launch, the ray list, the store, the options
+ * ("any_rays_per_wave", "any_coop", "dda_blocks": no word changes), the stages and leaving the split-walk history alone
+ * are ugrt_gi_gather's.  num_samples outside 1..UGRT_MAX_AA_SAMPLES, set_w or set_h outside 1..UGRT_MAX_AA_SET_TILE, eps
+ * NaN, num_materials < 1, a d_sum that is not 16-byte aligned, or a null argument other than shadow_light: UGRT_EINVAL
+ * (the message names the argument) and nothing is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_aa_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+		   const float *d_vertlist, const int *d_trilist, const float *eye_camcoords, const int *d_edge,
+		   int num_samples, int set_w, int set_h, const float *d_offsets, const int *d_mat_idx,
+		   const float *d_mat_list, int num_materials, const float *shadow_light, float eps, unsigned *d_sum);
+/* The supersampled pixels onto the image, behind the frame's shading calls (and ugrt_shade_add_shadows) and before
+ * ambient occlusion scales the image: for a pixel of the band with d_sum[4p + 3] != 0 byte k becomes
+ * (d_sum[4p + k] + num_samples / 2) / num_samples in unsigned integers; every other pixel is left as it is.  Stage
+ * UGRT_ST_SHADE.  num_samples outside 1..UGRT_MAX_AA_SAMPLES, a d_sum that is not 16-byte aligned or a null argument:
+ * UGRT_EINVAL and nothing is enqueued. */
+int ugrt_aa_resolve(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_sum, int num_samples);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

@@ -62,6 +62,7 @@ MAX_AREA_SET_POINTS = 512  # UGRT_MAX_AREA_SET_POINTS
 MAX_FILTER_RADIUS = 8  # UGRT_MAX_FILTER_RADIUS
 MAX_AO_SET_TILE = 4  # UGRT_MAX_AO_SET_TILE
 MAX_AO_SET_DIRS = 512  # UGRT_MAX_AO_SET_DIRS
+MAX_AA_SAMPLES = 32  # UGRT_MAX_AA_SAMPLES
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -192,6 +193,9 @@ PROTOTYPES = {
     "ugrt_gi_gather": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_gi_filter": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P]),
     "ugrt_gi_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int]),
+    "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
+    "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
+    "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

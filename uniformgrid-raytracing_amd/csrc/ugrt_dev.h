@@ -126,11 +126,13 @@ __device__ __forceinline__ unsigned d_effective_y(const CamBlock &cam, const flo
 // trace_kernel.cu:96-114: ray through the CORNER of pixel (col,row), x flipped.
 // The 5x5 texture fetch is the exact float bilinear interpolation of the node
 // table `tex` (DESIGN.md "ray set-up").
-__device__ __forceinline__ void d_ray_dir(const CamBlock &cam, const float *__restrict__ tex, int col, int row,
-					  float *ray_direction)
+// d_ray_dir_at is the arithmetic at the image position (fcol, frow) -- it reads cam.cc[0..2], W, H and strict_tex --: the
+// primary pass asks it at ((float)col, (float)row), the sub-pixel eye rays (ugrt_aa.hip) at ((float)col + sx, (float)row + sy).
+__device__ __forceinline__ void d_ray_dir_at(const CamBlock &cam, const float *__restrict__ tex, float fcol, float frow,
+					     float *ray_direction)
 {
-	float ftx = (float)col / (float)cam.W;
-	float fty = (float)row / (float)cam.H;
+	float ftx = fcol / (float)cam.W;
+	float fty = frow / (float)cam.H;
 	ftx = 1 - ftx;
 	float xs = ftx * 4.0f, ys = fty * 4.0f;
 	int i = ugrt_f2i(xs), j = ugrt_f2i(ys);
@@ -153,6 +155,11 @@ __device__ __forceinline__ void d_ray_dir(const CamBlock &cam, const float *__re
 		ray_direction[k] = T - cam.cc[k];
 	}
 	D_NORMALIZE(ray_direction);
+}
+__device__ __forceinline__ void d_ray_dir(const CamBlock &cam, const float *__restrict__ tex, int col, int row,
+					  float *ray_direction)
+{
+	d_ray_dir_at(cam, tex, (float)col, (float)row, ray_direction);
 }
 
 // inv_det = 1.0f / det of the Moller-Trumbore tests, for a det that has passed |det| >= D_EPSILON.

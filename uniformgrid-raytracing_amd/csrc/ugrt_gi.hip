@@ -10,15 +10,14 @@
 // registers of one lane and only 16 bytes per pixel are written.
 //   * the index space is ugrt_trace_dda_any_area's (pixel group, sample): the S rays of a pixel in neighbouring lanes;
 //   * phase A is k_trace_dda_ray's loop -- d_dda_clip, d_dda_axes, d_dda_step, the dims-sum guard, list order, strict
-//     acceptance, the 64-bit wave minimum of the cooperative rounds -- planned GI_AHEAD cells at a time with the any-hit
+//     acceptance, the 64-bit wave minimum of the cooperative rounds -- planned WALK_AHEAD cells at a time with the any-hit
 //     kernel's bitmap look-up in front of the headers; best_t starts at min(3.0e38f, radius) and the walk also ends behind
-//     a cell whose exit parameter is not below radius;
+//     a cell whose exit parameter is not below radius (d_closest_walk<., true> of ugrt_walks.h, shared with ugrt_aa.hip);
 //   * behind it a lane forms what the later phases need from {o, D, t, id} (the occlusion origin, the colour) and lets
-//     those go: phase B, k_trace_dda_any's loop with t_max = 1, holds its own ray only;
+//     those go: phase B, k_trace_dda_any's loop with t_max = 1 (d_any_walk of ugrt_walks.h), holds its own ray only;
 //   * the three byte sums are added across the pixel's S lanes and stored with the count word by the pixel's first lane.
-#include "ugrt_dda.h"
+#include "ugrt_walks.h"
 
-#define GI_AHEAD 8 // steps planned (and looked up in the bitmap) per window
 // words staged in LDS behind the table, which only the code between and behind the walks reads: cc[16..27], the
 // context's light, the shadow light, eps; then (GI_LATE_F on) the material arrays, their count, `sum` and the ticket as 32-bit halves
 #define GI_LATE_F 19
@@ -43,95 +42,6 @@ struct GiArg {
 
 // (dynamic LDS, its base 16-byte aligned: the direction table)
 extern __shared__ __attribute__((aligned(16))) float s_gi_dirs[];
-
-// k_trace_dda_any's loop for one ray per lane: true = some triangle of a visited cell passes the exact test with
-// 0 < t < t_max.  Every lane of the wave calls it (walking false: the lane only serves the cooperative rounds).
-template <bool REC>
-__device__ __forceinline__ bool d_gi_any_walk(const DGrid &g, const u32 *__restrict__ value_list, const u32 *__restrict__ span,
-					      const u32 *__restrict__ offset, const u32 *__restrict__ bitmap,
-					      const float *__restrict__ verts, const int *__restrict__ tris,
-					      const float4 *__restrict__ rec, const float *o, const float *d, float t_max,
-					      bool walking, u32 COOP, int lane)
-{
-	float tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
-	int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
-	bool occ = false;
-	if (walking) {
-		float tenter;
-		walking = false;
-		if (d_dda_clip(g, o, d, tenter)) {
-			walking = tenter < t_max;
-			d_dda_axes(g, o, d, tenter, c, step, tmax, tdelta);
-		}
-	}
-	int guard = g.dims[0] + g.dims[1] + g.dims[2] + 3;
-	while (__ballot(walking) != 0ull) {
-		u32 pcell[GI_AHEAD], pvalid = 0u;
-		bool planning = walking;
-#pragma unroll
-		for (int q = 0; q < GI_AHEAD; q++) {
-			pcell[q] = 0u;
-			if (planning) {
-				pvalid |= 1u << q;
-				pcell[q] = (u32)((c[0] * g.dims[1] + c[1]) * g.dims[2] + c[2]);
-				float tnext;
-				const bool outside = d_dda_step(g, c, step, tmax, tdelta, tnext);
-				if (outside || --guard <= 0 || !(tnext < t_max))
-					planning = false;
-			}
-		}
-		u32 pword[GI_AHEAD], psp[GI_AHEAD], poff[GI_AHEAD];
-#pragma unroll
-		for (int q = 0; q < GI_AHEAD; q++)
-			pword[q] = ((pvalid >> q) & 1u) ? bitmap[pcell[q] >> 5] : 0u;
-#pragma unroll
-		for (int q = 0; q < GI_AHEAD; q++) {
-			const bool full = (pword[q] >> (pcell[q] & 31u)) & 1u;
-			psp[q] = full ? span[pcell[q]] : 0u;
-			poff[q] = full ? offset[pcell[q]] : 0u;
-		}
-#pragma unroll
-		for (int q = 0; q < GI_AHEAD; q++) {
-			const u32 sp = walking ? psp[q] : 0u, off = poff[q];
-			if (__ballot(sp != 0u) == 0ull)
-				continue;
-			if (sp < COOP) {
-				for (u32 r = 0; r < sp; r++) {
-					float t9[9], t;
-					d_load_triangle<REC>(rec, verts, tris, value_list[off + r], o[0], o[1], o[2], t9);
-					if (d_mt_core(&t9[0], &t9[3], &t9[6], d, &t) && t > 0.0f && t < t_max) {
-						occ = true;
-						break;
-					}
-				}
-			}
-			unsigned long long heavy = __ballot(sp >= COOP);
-			while (heavy != 0ull) {
-				const int l = (int)__builtin_ctzll(heavy);
-				heavy &= heavy - 1ull;
-				const float ox = d_readlane(o[0], l), oy = d_readlane(o[1], l), oz = d_readlane(o[2], l);
-				const float dl[3] = { d_readlane(d[0], l), d_readlane(d[1], l), d_readlane(d[2], l) };
-				const u32 spl = (u32)__builtin_amdgcn_readlane((int)sp, l), offl = (u32)__builtin_amdgcn_readlane((int)off, l);
-				bool hit = false;
-				for (u32 base = 0; base < spl && !hit; base += 64u) {
-					const u32 r = base + (u32)lane;
-					bool acc = false;
-					if (r < spl) {
-						float t9[9], t;
-						d_load_triangle<REC>(rec, verts, tris, value_list[offl + r], ox, oy, oz, t9);
-						acc = d_mt_core(&t9[0], &t9[3], &t9[6], dl, &t) && t > 0.0f && t < t_max;
-					}
-					hit = __ballot(acc) != 0ull;
-				}
-				if (hit && lane == l)
-					occ = true;
-			}
-			walking = walking && !occ;
-		}
-		walking = walking && planning;
-	}
-	return occ;
-}
 
 // `sum` of the band was cleared in stream order before the launch: only the words of active pixels are written
 template <bool REC, bool SHADOW>
@@ -197,11 +107,8 @@ __global__ __launch_bounds__(64) void k_gi_gather(DGrid g, const u32 *__restrict
 			asmp += ((y % set_h) * set_w + x % set_w) * S;
 		}
 		// ---- phase A: the closest hit of {o, D} below radius (k_trace_dda_ray's loop) ----
-		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
-		int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
-		float best_t = a.radius < 3.0e38f ? a.radius : 3.0e38f, res_t = -1.0f;
-		int best_id = -2, res_id = -2;
-		bool walking = false;
+		float o[3] = { 0, 0, 0 }, d[3] = { 0, 0, 0 }, res_t;
+		int res_id;
 		if (inb) {
 			float nrm[3];
 #pragma unroll
@@ -210,102 +117,9 @@ __global__ __launch_bounds__(64) void k_gi_gather(DGrid g, const u32 *__restrict
 				nrm[k] = rays[p * 6 + 3 + k];
 			}
 			d_hemi_dir(nrm, s_gi_dirs[3u * asmp], s_gi_dirs[3u * asmp + 1u], s_gi_dirs[3u * asmp + 2u], d);
-			float tenter;
-			if (d_dda_clip(g, o, d, tenter)) {
-				walking = tenter < a.radius; // the entry cell's entry parameter
-				d_dda_axes(g, o, d, tenter, c, step, tmax, tdelta);
-			}
 		}
-		int guard = g.dims[0] + g.dims[1] + g.dims[2] + 3;
-		while (__ballot(walking) != 0ull) {
-			// 1. the window's cells and their exit parameters.  pend: the walk ends behind the cell -- the ray leaves the
-			// grid there, the guard runs out, or the exit parameter is not below radius
-			u32 pcell[GI_AHEAD], pvalid = 0u, pend = 0u;
-			float ptnext[GI_AHEAD];
-			bool planning = walking;
-#pragma unroll
-			for (int q = 0; q < GI_AHEAD; q++) {
-				pcell[q] = 0u;
-				ptnext[q] = 0.0f;
-				if (planning) {
-					pvalid |= 1u << q;
-					pcell[q] = (u32)((c[0] * g.dims[1] + c[1]) * g.dims[2] + c[2]);
-					const bool outside = d_dda_step(g, c, step, tmax, tdelta, ptnext[q]);
-					if (outside || --guard <= 0 || !(ptnext[q] < a.radius)) {
-						pend |= 1u << q;
-						planning = false;
-					}
-				}
-			}
-			// 2. which of them hold a triangle: one bitmap word per step, then the headers of the occupied cells only
-			u32 pword[GI_AHEAD], psp[GI_AHEAD], poff[GI_AHEAD];
-#pragma unroll
-			for (int q = 0; q < GI_AHEAD; q++)
-				pword[q] = ((pvalid >> q) & 1u) ? bitmap[pcell[q] >> 5] : 0u;
-#pragma unroll
-			for (int q = 0; q < GI_AHEAD; q++) {
-				const bool full = (pword[q] >> (pcell[q] & 31u)) & 1u;
-				psp[q] = full ? span[pcell[q]] : 0u;
-				poff[q] = full ? offset[pcell[q]] : 0u;
-			}
-			// 3. the tests, cell by cell, and behind each cell the question whether the walk ends there
-#pragma unroll
-			for (int q = 0; q < GI_AHEAD; q++) {
-				const bool here = walking && ((pvalid >> q) & 1u);
-				const u32 sp = here ? psp[q] : 0u, off = poff[q];
-				if (__ballot(sp != 0u) != 0ull) {
-					// short lists: the owning lane, in list order
-					if (sp < COOP) {
-						for (u32 r = 0; r < sp; r++) {
-							const u32 f = value_list[off + r];
-							float t9[9], t;
-							d_load_triangle<REC>(rec, verts, tris, f, o[0], o[1], o[2], t9);
-							if (d_mt_core(&t9[0], &t9[3], &t9[6], d, &t) && t > 0.0f && t < best_t) {
-								best_t = t;
-								best_id = (int)f;
-							}
-						}
-					}
-					// long lists: one owner at a time, 64 triangles per round, the first r of the smallest t by a 64-bit minimum
-					unsigned long long heavy = __ballot(sp >= COOP);
-					while (heavy != 0ull) {
-						const int l = (int)__builtin_ctzll(heavy);
-						heavy &= heavy - 1ull;
-						const float ox = d_readlane(o[0], l), oy = d_readlane(o[1], l), oz = d_readlane(o[2], l);
-						const float dl[3] = { d_readlane(d[0], l), d_readlane(d[1], l), d_readlane(d[2], l) };
-						const float bt = d_readlane(best_t, l);
-						const u32 spl = (u32)__builtin_amdgcn_readlane((int)sp, l),
-							  offl = (u32)__builtin_amdgcn_readlane((int)off, l);
-						unsigned long long kbest = ~0ull;
-						for (u32 base = 0; base < spl; base += 64u) {
-							const u32 r = base + (u32)lane;
-							unsigned long long key = ~0ull;
-							if (r < spl) {
-								float t9[9], t;
-								d_load_triangle<REC>(rec, verts, tris, value_list[offl + r], ox, oy, oz, t9);
-								if (d_mt_core(&t9[0], &t9[3], &t9[6], dl, &t) && t > 0.0f && t < bt)
-									key = ((unsigned long long)__float_as_uint(t) << 32) | (unsigned long long)r;
-							}
-							key = d_wave_min_u64(key);
-							kbest = key < kbest ? key : kbest;
-						}
-						if (lane == l && kbest != ~0ull) {
-							best_t = __uint_as_float((u32)(kbest >> 32));
-							best_id = (int)value_list[off + (u32)(kbest & 0xFFFFFFFFull)];
-						}
-					}
-				}
-				if (here) {
-					if (best_id >= 0 && best_t <= ptnext[q]) {
-						res_t = best_t;
-						res_id = best_id;
-						walking = false;
-					} else if ((pend >> q) & 1u) {
-						walking = false;
-					}
-				}
-			}
-		}
+		d_closest_walk<REC, true>(g, value_list, span, offset, bitmap, verts, tris, rec, o, d, a.radius, inb, COOP, lane, res_t,
+					  res_id);
 		// ---- the hit's colour and its occlusion ray, formed here so that phase B holds neither o nor D ----
 		float L[3] = { 0.0f, 0.0f, 0.0f }, o2[3] = { 0.0f, 0.0f, 0.0f }, d2[3] = { 0.0f, 0.0f, 0.0f };
 		bool lit_hit = false; // a hit with a colour: a miss and a material out of range stay 0, occluded or not
@@ -341,7 +155,7 @@ __global__ __launch_bounds__(64) void k_gi_gather(DGrid g, const u32 *__restrict
 		}
 		// ---- phase B: is the shadow light hidden from the hit (k_trace_dda_any's loop, the light at t = 1) ----
 		if constexpr (SHADOW) {
-			const bool occ = d_gi_any_walk<REC>(g, value_list, span, offset, bitmap, verts, tris, rec, o2, d2, 1.0f, lit_hit,
+			const bool occ = d_any_walk<REC>(g, value_list, span, offset, bitmap, verts, tris, rec, o2, d2, 1.0f, lit_hit,
 							    COOP, lane);
 			if (occ) {
 #pragma unroll

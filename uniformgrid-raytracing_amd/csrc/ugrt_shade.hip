@@ -539,6 +539,34 @@ extern "C" int ugrt_gi_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned
 				  d_mat_list, num_materials);
 }
 
+// Anti-aliasing, behind the frame's shading and shadow calls: a pixel ugrt_aa_gather has
+// supersampled (count word != 0) takes the rounded mean of its samples' bytes, every other pixel stays as it is.
+__global__ __launch_bounds__(PX_THREADS) void k_aa_resolve(unsigned char *__restrict__ d_img, const u32 *__restrict__ sum,
+							    u32 num_samples, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	const size_t pixelID = (size_t)(p0 + i);
+	const uint4 sums = *(const uint4 *)(sum + 4 * pixelID);
+	if (sums.w == 0u)
+		return;
+	d_img[pixelID * 3 + 0] = (unsigned char)((sums.x + num_samples / 2u) / num_samples);
+	d_img[pixelID * 3 + 1] = (unsigned char)((sums.y + num_samples / 2u) / num_samples);
+	d_img[pixelID * 3 + 2] = (unsigned char)((sums.z + num_samples / 2u) / num_samples);
+}
+
+extern "C" int ugrt_aa_resolve(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_sum, int num_samples)
+{
+	if (!ctx || !d_img || !d_sum)
+		return ugrt_fail(UGRT_EINVAL, "aa_resolve: null argument");
+	if (num_samples < 1 || num_samples > UGRT_MAX_AA_SAMPLES)
+		return ugrt_fail(UGRT_EINVAL, "aa_resolve: num_samples %d is not in 1..%d", num_samples, UGRT_MAX_AA_SAMPLES);
+	if (((size_t)d_sum & 15u) != 0u)
+		return ugrt_fail(UGRT_EINVAL, "aa_resolve: d_sum is not 16-byte aligned");
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_aa_resolve, d_img, (const u32 *)d_sum, (u32)num_samples);
+}
+
 // ---------------------------------------------------------------------------
 // several lights (the reference's loop over h_numLights, main.cu:148-203, runs with one and
 // its shading kernels index light 0): k_shade<false> and k_add_shadows once per light and the mean of the bytes, in

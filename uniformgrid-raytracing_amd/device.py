@@ -484,6 +484,34 @@ class Context:
         check(lib.ugrt_gi_apply(self._h, _ptr(img), _ptr(acc), int(num_dirs), gain, _ptr(ids), _ptr(mat_list),
                                 int(num_materials)))
 
+    # -- anti-aliasing --------------------------------
+    def aa_edges(self, normal, t, dirs, ids, cam_pos, mat_idx, is_shadowed, normal_cos, plane_tol, edge):
+        """Before the shading call (ids holds triangle ids): edge[p] = 1 where one of the up to eight neighbours of p
+        differs from it in hit or miss, in material, in its normal by more than normal_cos, in its plane by more than
+        plane_tol (the last three between different triangles), or, with is_shadowed (None: not looked at), in its
+        shadow flag; 0 elsewhere.  edge: int32 [W * H]."""
+        check(lib.ugrt_aa_edges(self._h, _ptr(normal), _ptr(t), _ptr(dirs), _ptr(ids), _ptr(cam_pos), _ptr(mat_idx),
+                                _ptr(is_shadowed), normal_cos, plane_tol, _ptr(edge)))
+
+    def aa_gather(self, value, span, offset, verts, faces, eye_camcoords, edge, num_samples, set_w, set_h, offsets, mat_idx,
+                  mat_list, num_materials, shadow_light, eps, sums):
+        """The sub-pixel eye rays of the pixels with edge[p] != 0: num_samples rays from the eye of eye_camcoords (64 host
+        floats: the EYE's block, whatever block the context holds) through (col + sx, row + sy), (sx, sy) from offsets (the
+        DEVICE table [set_w * set_h, num_samples, 2]: scenes.aa_offset_sets, uploaded), each to its closest hit, shaded as
+        the frame shades a primary hit under the context's current camera block, each byte b / 3 where the hit does not see
+        shadow_light (three host floats, or None: no shadow phase); sums[4p + k] for k < 3 holds the bytes' sums and
+        sums[4p + 3] = 1; sums: uint32 words [4 * W * H] (an int32 tensor serves)."""
+        light = None if shadow_light is None else _points([shadow_light])[1]
+        check(lib.ugrt_aa_gather(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                 None if eye_camcoords is None else _f3(eye_camcoords), _ptr(edge), int(num_samples), int(set_w),
+                                 int(set_h), _ptr(offsets), _ptr(mat_idx), _ptr(mat_list), int(num_materials), light, eps,
+                                 _ptr(sums)))
+
+    def aa_resolve(self, img, sums, num_samples):
+        """Behind the shading calls: each byte of a pixel with sums[4p + 3] != 0 becomes
+        (sums[4p + k] + num_samples // 2) // num_samples; every other pixel stays."""
+        check(lib.ugrt_aa_resolve(self._h, _ptr(img), _ptr(sums), int(num_samples)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

@@ -30,7 +30,9 @@ the pixels of a tile aim at different sets of S points, and with ``area_filter``
 surface averages their shares before that pass; ``ao_sets`` and ``ao_filter`` do the same for the
 hemisphere rays of ``ao``, in a walk that keeps a pixel's rays side by side in a wave.  With
 ``gi=S`` the one-stream single-light frame adds one bounce of indirect diffuse light: S hemisphere rays per primary hit to
-their first hit, which is shaded and shadowed, and a pass that adds the mean to the image.
+their first hit, which is shaded and shadowed, and a pass that adds the mean to the image.  With
+``aa=S`` the one-stream single-light plain frame is anti-aliased where it needs it: the pixels on an edge send S sub-pixel
+eye rays through the uniform grid and take the mean of their colours.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -40,7 +42,7 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS, MAX_REFLECT_DEPTH
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -246,6 +248,46 @@ def check_gi(gi, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_fil
     return (int(gi), radius, float(np.float32(gi_gain)), bool(gi_shadows)) + sets
 
 
+def check_aa(aa, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True, reflect=False, frame_cnt=1, lights=None, area=0,
+             gi=0, reflect_lights=False, two_streams=False):
+    """The keywords of the adaptive anti-aliasing.  aa: an integer 0..MAX_AA_SAMPLES (0: off, and
+    every other aa_* keyword must be at its default); aa_sets: 1, 4 or 16; aa_cos: a number (no NaN); aa_plane: None
+    (default_filter_plane) or a number (no NaN); aa_shadows: a bool.  aa > 0 needs the one-stream Renderer's single-light
+    plain frame: reflect=False, frame_cnt < 2, no setup.lights, no area, no gi (ao composes).  ValueError before anything
+    is enqueued.  Returns None (off) or (aa, aa_sets, cos, plane or None, shadows)."""
+    if isinstance(aa, (bool, np.bool_)) or not isinstance(aa, (int, np.integer)) or not 0 <= aa <= MAX_AA_SAMPLES:
+        raise ValueError("aa must be an integer in 0..%d, not %r" % (MAX_AA_SAMPLES, aa))
+    if isinstance(aa_sets, (bool, np.bool_)) or not isinstance(aa_sets, (int, np.integer)) or int(aa_sets) not in AREA_SET_TILES:
+        raise ValueError("aa_sets must be 1, 4 or 16, not %r" % (aa_sets,))
+    number = (int, float, np.integer, np.floating)
+    if isinstance(aa_cos, (bool, np.bool_)) or not isinstance(aa_cos, number) or np.isnan(np.float32(aa_cos)):
+        raise ValueError("aa_cos must be a number, not %r" % (aa_cos,))
+    if aa_plane is not None:
+        if isinstance(aa_plane, (bool, np.bool_)) or not isinstance(aa_plane, number) or np.isnan(np.float32(aa_plane)):
+            raise ValueError("aa_plane must be None or a number, not %r" % (aa_plane,))
+        aa_plane = float(np.float32(aa_plane))
+    if not isinstance(aa_shadows, (bool, np.bool_)):
+        raise ValueError("aa_shadows must be True or False, not %r" % (aa_shadows,))
+    if aa == 0:
+        if aa_sets != 1 or float(np.float32(aa_cos)) != float(np.float32(0.9)) or aa_plane is not None or not aa_shadows:
+            raise ValueError("aa_sets, aa_cos, aa_plane and aa_shadows need aa > 0: they shape the anti-aliasing")
+        return None
+    if reflect or reflect_lights:
+        raise ValueError("aa needs reflect=False: edges seen in mirrors are not supersampled")
+    if isinstance(frame_cnt, (bool, np.bool_)) or not isinstance(frame_cnt, (int, np.integer)) or frame_cnt >= 2:
+        raise ValueError("aa needs frame_cnt < 2: the samples are shaded as the plain frame shades, not under the spot light")
+    if lights is not None:
+        raise ValueError("aa needs a single-light frame: the samples under setup.lights are not built")
+    if area:
+        raise ValueError("aa needs area=0: the samples are not shaded under an area light")
+    if gi:
+        raise ValueError("aa needs gi=0: the samples gather no indirect light")
+    if two_streams:
+        raise ValueError("aa needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
+                         "side context")
+    return int(aa), int(aa_sets), float(np.float32(aa_cos)), aa_plane, bool(aa_shadows)
+
+
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
 # BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
@@ -443,6 +485,23 @@ def gi_shade(c, f, gi):
     c.gi_apply(f.image, acc, gi[0], gi[4], f.intersect_id, f.d_matlist, f.num_materials)
 
 
+def aa_edges(c, f, cam_pos, aa, shadows):
+    """The anti-aliasing's edge flags into f.aa_edge, behind the shadow stage and before the
+    shading call that rewrites the ids.  aa: Renderer._aa_stage's (S, (set_w, set_h), table, cos, plane, shadows); shadows:
+    the frame has a shadow stage and the edges of its shadows count."""
+    c.aa_edges(f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.is_shadowed if shadows else None, aa[3], aa[4],
+               f.aa_edge)
+
+
+def aa_pass(c, f, eye_camcoords, aa, shadow_light):
+    """The sub-pixel eye rays of the flagged pixels through c's uniform grid into f.aa_sum (aa_edges' aa); eye_camcoords:
+    the eye's block (the context holds the light camera's by now); shadow_light: the point the samples are shadowed
+    from, or None."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.aa_gather(uvalue, uspan, uoffset, f.d_verts, f.d_faces, eye_camcoords, f.aa_edge, aa[0], aa[1][0], aa[1][1], aa[2],
+                f.d_matidx, f.d_matlist, f.num_materials, shadow_light, f.reflect_eps, f.aa_sum)
+
+
 def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
     """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
@@ -568,6 +627,10 @@ class _Frame:
         # (_ensure_gi_buffers; the origins share ao_rays); the uploaded direction tables by (gi, gi_sets) (_gi_stage)
         self.gi_sum = self.gi_acc = None
         self._gi_set_tables = {}
+        # aa: the edge flags and the byte sums of the supersampled pixels, four words per pixel (_aa_stage); the uploaded
+        # offset tables by (aa, aa_sets)
+        self.aa_edge = self.aa_sum = None
+        self._aa_set_tables = {}
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -785,7 +848,7 @@ class Renderer(_Frame, _Band):
                 reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1,
                 area_filter=0, area_filter_cos=0.9, area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9,
                 ao_filter_plane=None, gi=0, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0,
-                gi_filter_cos=0.9, gi_filter_plane=None):
+                gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -823,7 +886,17 @@ class Renderer(_Frame, _Band):
         the whole grid), the hits are shaded under the light and, with gi_shadows, shadowed from the light camera's eye;
         gi_sum holds the bytes' sums, gi_filter (0: off) gathers them over the pixels of the same surface with
         gi_filter_cos and gi_filter_plane into gi_acc, and Kd * gi_gain of the mean is added to the image behind the
-        frame's own shading and before ambient occlusion scales it."""
+        frame's own shading and before ambient occlusion scales it.
+        aa (one-stream renderer, the single-light plain frame: reflect=False, frame_cnt < 2, no setup.lights, area or gi;
+        ao composes; 0: off): adaptive anti-aliasing -- the pixels on an edge (aa_edge: a silhouette, a material border, a
+        crease sharper than aa_cos, a step off the neighbour's plane by more than aa_plane (None: 1 % of the scene's
+        largest extent) or, with aa_shadows, a shadow edge) send aa = 1..32 sub-pixel eye rays
+        (scenes.aa_offset_sets(aa, aa_sets), uploaded once per (aa, aa_sets)) through the uniform grid, each shaded as
+        the frame shades a primary hit and, with shadows and aa_shadows, shadowed from the light camera's eye; aa_sum
+        holds the bytes' sums and their mean replaces the pixel behind the frame's own shading and before ambient
+        occlusion scales it."""
+        aa = check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), area, gi,
+                      reflect_lights, self.aux is not None)
         gi = check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
                       getattr(setup, "lights", None), reflect_lights, self.aux is not None)
         area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
@@ -845,13 +918,16 @@ class Renderer(_Frame, _Band):
         ao = self._ao_stage(ao, ao_radius, shade, ao_more)
         if gi:
             gi = self._gi_stage(gi, shade)
+        if aa:
+            aa = self._aa_stage(aa, shade)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
             two_streams = self._display_two_streams_inline if self._inline else self._display_overlapped
             return two_streams(setup, frame_cnt, shadows, reflect, bounces, reflect_shadows)
         ctx = self.ctx
-        camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
+        cam = make_camera(setup.camera, setup.fovy, self.aspect)
+        camera_pass(ctx, self, self, setup, cam)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         use_light_camera(ctx, lcam)
         if shadows and not area:
@@ -862,11 +938,13 @@ class Renderer(_Frame, _Band):
             trace_shadows(ctx, self, self, light_grid)
         if not shade:
             return
+        if aa:
+            aa_edges(ctx, self, self.cam_pos, aa, shadows and aa[5])
         if reflect:
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
-        elif ao or area or gi:
+        elif ao or area or gi or aa:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         if area:
             thru = see_through(self)
@@ -879,6 +957,8 @@ class Renderer(_Frame, _Band):
             ao_pass(ctx, self, self.cam_pos, *ao)
         if gi:
             gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area))
+        if aa:
+            aa_pass(ctx, self, cam.camcoords, aa, lcam.worldori[:3] if shadows and aa[5] else None)
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
         if area and area_filter:
             self._ensure_area_filter_buffers()
@@ -890,8 +970,33 @@ class Renderer(_Frame, _Band):
             ctx.shade_area(self.image, self.area_mask, area)
         if gi:
             gi_shade(ctx, self, gi)
+        if aa:
+            ctx.aa_resolve(self.image, self.aa_sum, aa[0])
         if ao:
             ao_shade(ctx, self, *ao)
+
+    def _aa_stage(self, aa, shade):
+        """(S, (set_w, set_h), table, cos, plane, shadows) for aa_edges and aa_pass from what check_aa returned, with the
+        buffers aa_edge [W*H] and aa_sum [4 W*H] (uint32 words in an int32 tensor) in place; None: nothing is shaded.
+        table: scenes.aa_offset_sets(S, aa_sets) on the device, uploaded once per (S, aa_sets) and kept."""
+        if not shade:
+            return None
+        S, sets, cos, plane, shadows = aa
+        self._ensure_aa_buffers()
+        tables = self._aa_set_tables
+        if (S, sets) not in tables:
+            from .scenes import aa_offset_sets
+
+            tables[(S, sets)] = self._upload_ao_sets(aa_offset_sets(S, sets))
+        return (S, AREA_SET_TILES[sets], tables[(S, sets)], cos, default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane,
+                shadows)
+
+    def _ensure_aa_buffers(self):
+        """aa_edge [W*H] and aa_sum [4 W*H] (uint32 words in an int32 tensor), allocated on first use."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.aa_edge is None:
+            self.aa_edge = t.zeros(N, dtype=t.int32, device=dev)
+            self.aa_sum = t.zeros(4 * N, dtype=t.int32, device=dev)
 
     def _gi_stage(self, gi, shade):
         """(S, (set_w, set_h), table, radius, gain, gather, shadows) for gi_pass and gi_shade from what check_gi returned,
@@ -1230,7 +1335,10 @@ class BandedRenderer(_Frame):
     def display(self, setup, frame_cnt=1, shadows=True, reflect=True, bounces=1, reflect_shadows=False, ao=0,
                 ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
                 area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None, gi=0, gi_radius=None,
-                gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None):
+                gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
+                aa_cos=0.9, aa_plane=None, aa_shadows=True):
+        check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), 0, gi, False,
+                 True)  # raises with aa > 0, as gi does
         check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
                  getattr(setup, "lights", None), False, True)  # raises with gi > 0, as ao and area do
         check_area(area, area_radius, shadows, getattr(setup, "lights", None), True)  # raises with area > 0, as ao does

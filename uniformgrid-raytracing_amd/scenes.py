@@ -477,3 +477,41 @@ def area_samples(S, centre, axis, radius):
     centre + r cos phi * T + r sin phi * B.  Computed in float64 and returned as float32 [S, 3]: the library only ever
     sees these floats as data."""
     return _disk_points(S, centre, axis, radius, 0.0)  # (phi + 0.0 is phi: the floats are what they were)
+
+
+def _aa_points(S, shift_x, shift_y):
+    """aa_offsets' points moved by (shift_x, shift_y) of a pixel and wrapped back into it."""
+    S = int(S)
+    s = np.arange(S, dtype=np.int64)
+    inverse = np.zeros(S, np.float64)  # the radical inverse of s in base 2 (van der Corput)
+    digit, rest = 0.5, s.copy()
+    while rest.any():
+        inverse += digit * (rest & 1)
+        rest >>= 1
+        digit *= 0.5
+    u = np.stack([(s + 0.5) / float(S) + shift_x, inverse + 0.5 / float(S) + shift_y], 1)
+    out = ((u % 1.0) - 0.5).astype(np.float32)
+    return np.clip(out, np.float32(-0.5), np.nextafter(np.float32(0.5), np.float32(0.0)))
+
+
+def aa_offsets(S):
+    """The S sub-pixel offsets of the anti-aliasing's eye rays, in [-0.5, 0.5) around the point
+    the pixel's own ray goes through: sample s lies at ((s + 1/2) / S, vdc(s) + 1 / (2 S)) - 1/2, vdc the radical inverse in
+    base 2 (the Hammersley set): every one of the S column strata holds one point, and for S a power of two every one of
+    the S row strata does.  S = 1 gives (0, 0), the pixel's own ray.  Computed in float64 and returned as float32 [S, 2]:
+    the library only ever sees these floats as data."""
+    return _aa_points(S, 0.0, 0.0)
+
+
+def aa_offset_sets(S, sets):
+    """The interleaved offset sets of the anti-aliasing: sets = 1, 4 or 16 for a tile of 1 x 1,
+    2 x 2 or 4 x 4 pixels; set k (row-major in the tile) is aa_offsets' set moved by rank[k] / (sets + 1) of a column
+    stratum and by rank[sets - 1 - k] / (sets + 1) of one S-th of the pixel's height and wrapped back into the pixel, rank =
+    AREA_SET_RANK[sets] as area_sample_sets turns the disk: the sets of a tile together hold sets * S different columns,
+    every set keeps one point per column stratum, and no point lies on a stratum's edge (sets + 1 is odd).
+    float32 [sets, S, 2]; set 0 is aa_offsets bit for bit."""
+    if sets not in AREA_SET_RANK:
+        raise ValueError("sets must be 1, 4 or 16, not %r" % (sets,))
+    rank = AREA_SET_RANK[sets]
+    step = 1.0 / (float(sets + 1) * float(int(S)))
+    return np.stack([_aa_points(S, rank[k] * step, (rank[sets - 1 - k] * step) if k else 0.0) for k in range(sets)])
