@@ -400,7 +400,20 @@ int ugrt_trace_shadow(ugrt_ctx *ctx, const unsigned *d_value_list, const float *
 		      const float *d_t_value, const float *d_ray_dir, int *d_is_shadowed, const unsigned *d_map,
 		      const unsigned *d_prefix_map, const float *d_cam_position, unsigned num_chunks);
 
-/* ---- device: shading (shader.h:20-24) ---------------------------------- */
+/* ---- device: shading (shader.h:20-24) ----------------------------------
+ * What every float shading call below does with inputs that no traced frame holds (tests/test_shade_synthetic.py runs
+ * them all; fp32 denormals are kept in every operation, the comparisons, the square roots and the divisions included):
+ * - the id of a pixel is a triangle id or negative.  A negative id is written back as it is, any other as
+ *   d_mat_idx[id]; a material index outside 0..num_materials-1 (INT_MAX too) reads no material and is black.
+ * - ugrt_shade_spotlight looks at no t; every other call shades a primary hit only where t > 0, which a positive
+ *   denormal and +inf are and -0, a negative value and NaN are not.
+ * - a colour is Kd/2 + Kd |L.N| where |L.N| > 0, clamped to 1 from above only.  A NaN dot product (the point on the
+ *   light, a zero, tiny or NaN normal, a degenerate triangle, a NaN or infinite t) is not > 0: the colour is Kd/2.
+ * - a byte is the low 8 bits of ugrt_f2u(colour * 255): 0 for a NaN and for a negative colour.
+ * - a level is active where its d_active entry is not 0 (2, -1 and INT_MIN are); only a flag == 1 darkens.
+ * - a level that misses (hit id < 0) or whose material is out of range has the colour 0 and leaves k where it was: if
+ *   the next level is active all the same, the weight goes on with the k of the last level that had a material.
+ * - reflect values are taken as they are (1.5, -0.5, a denormal, NaN); nothing is clamped but the colours. */
 int ugrt_shade_simple(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
 		      const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
 		      const int *d_mat_idx, const float *d_mat_list, int num_materials);

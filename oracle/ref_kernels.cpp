@@ -32,7 +32,7 @@
 // Reference behaviours that read out of bounds are given defined values, as the oracle defines them:
 // the light grid's sentinel cell (Q11) gets span = offset = 0 (NUM_SLABS extra entries: the kernel reads
 // blockcnt[C * NUM_SLABS + p] for every p), and the material index of a miss,
-// mat_idx[-2] (Q17, shader_kernel.cu:170), is -2 (two entries in front of the list).
+// mat_idx[-2] (Q17, shader_kernel.cu:170), is -2, that of an id of -1 is -1 (two entries in front of the list).
 //
 // I/O: one binary input file (named arrays; "stage" names the stage) -> one binary output file in the same format
 // (tests/oracle_lib.py: write_ref_io / read_ref_io):
@@ -621,6 +621,7 @@ static void stage_shade()
 	size_t N = (size_t)g_W * g_H;
 	Arr &mi = in("mat_idx");
 	std::vector<int> mat_idx(mi.n() + 2, -2); // Q17: mat_idx[-2] of a miss
+	mat_idx[1] = -1;                          // ... and mat_idx[-1] of an id of -1: a miss keeps its id
 	memcpy(&mat_idx[2], mi.p<int>(), sizeof(int) * mi.n());
 	Arr &ml = in("mat_list");
 	int nmat = ml.n() / MATERIAL_SIZE;
@@ -682,6 +683,7 @@ static void stage_spot()
 	size_t N = (size_t)g_W * g_H;
 	Arr &mi = in("mat_idx");
 	std::vector<int> mat_idx(mi.n() + 2, -2); // Q17: mat_idx[-2] of a miss
+	mat_idx[1] = -1;                          // ... and mat_idx[-1] of an id of -1: a miss keeps its id
 	memcpy(&mat_idx[2], mi.p<int>(), sizeof(int) * mi.n());
 	Arr &ml = in("mat_list");
 	int nmat = ml.n() / MATERIAL_SIZE;

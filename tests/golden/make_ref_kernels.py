@@ -7,6 +7,8 @@ live binary where it is built.
 "shadowsyn" is case A of tests/test_shadow_synthetic.py (synthetic rays and triangles): the stages of the shadow pass alone.
 "buildsyn" is the perspective and the spherical boundary family of tests/test_grid_build_synthetic.py: the count, slab and
 fill kernels of the two grid builds alone.
+"shadesyn" is the synthetic g-buffer of tests/test_shade_synthetic.py: lambertian_shade + shadow_kernel and spot_shade alone,
+on every pixel in front of its undefined-cast rows.
 Usage: python tests/golden/make_ref_kernels.py [case ...]"""
 import os
 import sys
@@ -21,6 +23,7 @@ import test_reference_kernels as T  # noqa: E402
 
 SHADOWSYN = "shadowsyn"  # = test_shadow_synthetic.RECORD (imported only when that record is written)
 BUILDSYN = "buildsyn"  # = test_grid_build_synthetic.RECORD (likewise)
+SHADESYN = "shadesyn"  # = test_shade_synthetic.RECORD (likewise)
 
 if not O.ref_kernels_live():
     sys.exit("oracle/_ref/ref_kernels is not built from the driver in the tree (make -C oracle ref)")
@@ -42,7 +45,7 @@ def write_record(name, ins, outs, stages, reported):
           {k.split("/")[0]: int(v) for k, v in rec.items() if "/report/" in k and "overrun_bytes" in k})
 
 
-for name in (sys.argv[1:] or sorted(T.CASES) + [SHADOWSYN, BUILDSYN]):
+for name in (sys.argv[1:] or sorted(T.CASES) + [SHADOWSYN, BUILDSYN, SHADESYN]):
     if name == BUILDSYN:
         import test_grid_build_synthetic as B
 
@@ -51,6 +54,14 @@ for name in (sys.argv[1:] or sorted(T.CASES) + [SHADOWSYN, BUILDSYN]):
         raw = {st: T.run_reference(name, st, ins[st]) for st in B.REF_STAGES}
         outs = {st: dict(raw[st], **B.pinned(O, st, raw[st])) for st in B.REF_STAGES}
         write_record(name, ins, outs, B.REF_STAGES, B.REF_STAGES)
+    elif name == SHADESYN:
+        import test_shade_synthetic as SH
+
+        assert SH.RECORD == SHADESYN
+        ins = SH.ref_stage_inputs(O)
+        raw = {st: O.run_ref_kernels(st, **ins[st]) for st in SH.REF_STAGES}
+        outs = {st: dict(raw[st], **SH.pinned(st, raw[st])) for st in SH.REF_STAGES}
+        write_record(name, ins, outs, SH.REF_STAGES, SH.REF_STAGES)
     elif name == SHADOWSYN:
         import test_shadow_synthetic as S
 
