@@ -445,6 +445,28 @@ int ugrt_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal
 
 /* ---- device: reflection bounce (not in the reference) ---- */
 /* secondary rays for hit pixels whose material has reflect > 0 */
+/* The domain of the six secondary-ray generators (ugrt_reflect_rays, _reflect_rays_next, _refract_rays,
+ * _refract_rays_next, _occlusion_rays, _ao_rays), as tests/test_secondary_rays_synthetic.py pins it against their CPU
+ * restatements.  Every pixel of the band gets its six floats and its active word written, 1 with a ray, else six +0 and 0.
+ *  - t: a ray leaves only where t > 0.  NaN, +0, -0, negative and -inf t give none; a denormal t gives one; t = +inf
+ *    gives one whose origin words are infinite, or NaN where the direction's component is 0.
+ *  - ids: a triangle id below 0 gives no ray (ids are triangle ids: the calls run before a shading call rewrites them).
+ *    A material index d_mat_idx[id] outside 0..num_materials-1 gives none either, in the calls that ask the material;
+ *    ugrt_occlusion_rays and ugrt_ao_rays do not read d_mat_idx.
+ *  - d_active (the level forms and ugrt_occlusion_rays): a pixel is live where the word is != 0, whatever else it is
+ *    (2, -1, INT_MIN, 0x100); the word written is 0 or 1.
+ *  - coefficients: d_reflect[m] and d_transmit[m] count where they are > 0: NaN, -0 and negative values do not, a
+ *    denormal and +inf do.  A material with both transmits: d_transmit wins over d_reflect.  d_ior[m] <= 0 or NaN counts
+ *    as 1; a denormal index makes 1 / ior infinite (total reflection from the front; from the back eta is next to 0 and
+ *    the ray leaves along -n), an infinite one the reverse.
+ *  - sides: front = !(d.n > 0) for n = normalize(e1 x e2): an edge-on hit (d.n +0, -0 or NaN) counts as front and the
+ *    normal is not turned.  k < 0 alone mirrors: k == 0 exactly refracts.
+ *  - a degenerate triangle (zero area, a cross product that under- or overflows, a NaN vertex) still gives an ACTIVE ray:
+ *    its words are NaN (or infinite; a normal whose squares overflow is a normal of zeros and leaves the ray at
+ *    {P, d}).  So do directions whose squared length is 0 or inf in the refracted ray (u is not finite).  A direction
+ *    need not be a unit vector: the reflected ray keeps its length, the refracted one is a unit vector.
+ *  - words: -0 and +0 are told apart and are as the formulas give them.  A NaN word's sign and payload are NOT pinned:
+ *    two of these calls, or a call and its CPU restatement, agree on which words are NaN and on every other bit. */
 int ugrt_reflect_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value,
 		      const float *d_ray_dir, const int *d_intersect_id, const int *d_mat_idx,
 		      const float *d_reflect, int num_materials, const float *d_vertlist, const int *d_trilist,
@@ -474,7 +496,9 @@ int ugrt_shade_reflect(ugrt_ctx *ctx, unsigned char *d_img, const float *d_norma
 /* The next reflected rays from one level's hits, for the context's band: for a pixel with d_active[p],
  * d_hit_t[p] > 0, d_hit_id[p] >= 0 and d_reflect[d_mat_idx[d_hit_id[p]]] > 0 (material in range), P = o + t*d,
  * n = normalize(e1 x e2) turned so that d.n <= 0, ray {P + eps*n, d - 2(d.n)n} and d_active_next[p] = 1 (the
- * arithmetic of ugrt_reflect_rays with the ray's own origin); every other pixel: six zeros and 0.  Stage
+ * arithmetic of ugrt_reflect_rays with the ray's own origin: fed with rays = {cam, dir}, d_active all ones and the
+ * primary t and ids it writes ugrt_reflect_rays' words); every other pixel: six zeros and 0.  d_active[p] counts where it
+ * is != 0; t, ids, materials, edge-on hits and degenerate triangles as said in front of ugrt_reflect_rays.  Stage
  * UGRT_ST_REFLECT_GEN.  The ugrt_trace_dda that follows on the same context walks without the split-walk history
  * (option "dda_split"), which stays that of the level-1 launches (ugrt_reflect_rays); results do not change. */
 int ugrt_reflect_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
@@ -500,7 +524,9 @@ int ugrt_shade_reflect_depth(ugrt_ctx *ctx, unsigned char *d_img, const float *d
 /* Occlusion rays from one level's hits, for the context's band: for a pixel with d_active[p], d_hit_t[p] > 0 and
  * d_hit_id[p] >= 0 (whatever the hit's material), o' = the origin ugrt_reflect_rays_next gives the next ray
  * (P = o + t*d, n = normalize(e1 x e2) turned so that d.n <= 0, o' = P + eps*n), ray {o', light_pos - o'} (not
- * normalised: the light lies at t = 1) and d_oactive[p] = 1; every other pixel: six zeros and 0.  light_pos is host
+ * normalised: the light lies at t = 1) and d_oactive[p] = 1; every other pixel: six zeros and 0.  d_active[p] counts
+ * where it is != 0; t, ids, edge-on hits and degenerate triangles as said in front of ugrt_reflect_rays.  A light on o'
+ * gives a direction of three +0 words, an infinite light coordinate an infinite direction word.  light_pos is host
  * memory and is passed on by value.  Stage UGRT_ST_REFLECT_GEN.  Unlike ugrt_reflect_rays_next the call says nothing
  * to the ugrt_trace_dda that follows. */
 int ugrt_occlusion_rays(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
@@ -579,8 +605,9 @@ int ugrt_shade_reflect_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *
  * ugrt_reflect_rays reads them (triangle ids: before any shading call).  For a pixel with d_t_value[p] > 0 and
  * d_intersect_id[p] >= 0, whatever its material: d_orays[6 * p ..] = {o', n} and d_oactive[p] = 1, with
  * P = cam + t*d, n = normalize(e1 x e2) turned so that d.n <= 0 and o' = P + eps*n (the origin and the flipped normal of
- * ugrt_reflect_rays); every other pixel: six zeros and 0.  Stage UGRT_ST_REFLECT_GEN.  The call says nothing to the
- * ugrt_trace_dda that follows.  A null argument: UGRT_EINVAL. */
+ * ugrt_reflect_rays with d_reflect all 1); every other pixel: six zeros and 0.  t, ids, edge-on hits (the normal is not
+ * turned) and degenerate triangles (an active pixel with NaN words) as said in front of ugrt_reflect_rays.  Stage
+ * UGRT_ST_REFLECT_GEN.  The call says nothing to the ugrt_trace_dda that follows.  A null argument: UGRT_EINVAL. */
 int ugrt_ao_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
 		 const int *d_intersect_id, const float *d_vertlist, const int *d_trilist, float eps, float *d_orays,
 		 int *d_oactive);
@@ -621,8 +648,9 @@ int ugrt_shade_ao(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_mask, i
  * tracked per ray. */
 /* ugrt_reflect_rays with glass: under ugrt_reflect_rays' conditions on the pixel (d_t_value[p] > 0, d_intersect_id[p] >= 0,
  * material m in range), d_transmit[m] > 0: the refracted ray above from the camera and active 1; else d_reflect[m] > 0:
- * ugrt_reflect_rays' ray and 1; else six zeros and 0.  A material with both transmits.  With d_transmit all zero the
- * call writes ugrt_reflect_rays' bytes.  It tells the context what ugrt_reflect_rays tells it (level 1: the
+ * ugrt_reflect_rays' ray and 1; else six zeros and 0.  A material with both transmits; a NaN in one of the two leaves
+ * the decision to the other.  With d_transmit all zero the call writes ugrt_reflect_rays' words (a NaN word where that
+ * call writes a NaN word; its sign is not pinned).  The domain is said in front of ugrt_reflect_rays.  It tells the context what ugrt_reflect_rays tells it (level 1: the
  * ugrt_trace_dda that follows uses the split-walk history).  Stage UGRT_ST_REFLECT_GEN.  A null argument: UGRT_EINVAL
  * and nothing is enqueued. */
 int ugrt_refract_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d_t_value, const float *d_ray_dir,
@@ -631,7 +659,8 @@ int ugrt_refract_rays(ugrt_ctx *ctx, const float *d_cam_position, const float *d
 		      float *d_rays, int *d_active);
 /* ugrt_reflect_rays_next with glass, in the same way: for a pixel with d_active[p], d_hit_t[p] > 0, d_hit_id[p] >= 0
  * and material m in range, d_transmit[m] > 0 gives the refracted ray from the ray's own origin, else d_reflect[m] > 0
- * the reflected one, else six zeros and 0.  With d_transmit all zero the call writes ugrt_reflect_rays_next's bytes.
+ * the reflected one, else six zeros and 0.  With d_transmit all zero the call writes ugrt_reflect_rays_next's words (NaN
+ * words as NaN words), and fed with rays = {cam, dir} and d_active all ones it writes ugrt_refract_rays' words.
  * It tells the context what ugrt_reflect_rays_next tells it (the ugrt_trace_dda that follows walks without the
  * split-walk history).  Stage UGRT_ST_REFLECT_GEN.  A null argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_refract_rays_next(ugrt_ctx *ctx, const float *d_rays, const int *d_active, const float *d_hit_t,
