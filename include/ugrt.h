@@ -219,6 +219,10 @@ int ugrt_ctx_set_stream(ugrt_ctx *ctx, void *hip_stream);
  * with the radix sort, 1 / default = it counts them per (beam, size class) bucket in the cull pass, scans the counts
  * and places the triangle ids - no sort (the pairs are sorted whatever the option with "sort_library" 1 and where the
  * bucket table, beams x 2^"shadow_sizebits" words, would exceed 4 Mi words);
+ * "shadow_frags" 0 = the shadow tracer keys and sorts every ray, 1 / default = where ugrt_sort_rays put its sort off
+ * (num_chunks NULL under UGRT_FLAG_SHADOW_ALL_CHUNKS) the rays of an 8x8-pixel tile that share a light cell and a block of direction codes
+ * are one sorted item, a fragment (every ray is sorted whatever the option with the sorted map, strict chunks, 64-bit keys,
+ * "sort_library" 1 and a band that is not whole 8x8 tiles);
  * "sort_items" 8 / 16 pairs per thread of a radix pass (default: by size), "sort_rank" 0 = the passes rank by
  * ballots instead of LDS atomics, "ray_sort" 1 = the deferred ugrt_sort_rays sorts at once also where nothing needs it
  * (see there); "dda_blocks", "primary_waves",
@@ -246,6 +250,8 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * atomics (the context's self-test found them served in lane order on this device), 0 = by ballots, -1 = no sort
  * has run yet; "shadow_key_bits" key bits the last ugrt_trace_shadow sorted its rays on (0 = no pass has sorted yet);
  * "shadow_pairs_counted" 1 = the last ugrt_trace_shadow bucketed its candidate pairs by counting, 0 = it sorted them (option "shadow_pairs");
+ * "shadow_fragments" fragments the last ugrt_trace_shadow formed (option "shadow_frags"; 0 = it sorted every ray; current once the
+ * context has been synchronised);
  * "uniform_builds_reused" ugrt_grid_build_uniform calls so far that kept the grid the context held instead of building;
  * "light_builds_reused" the same for ugrt_grid_build_spherical;
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and

@@ -213,7 +213,7 @@ static const struct {
 	{ "dda_split", 0, 4 }, { "dda_split_load", 50, 100000 }, { "dda_split_segments", 1, 4 }, { "primary_xcd_run", 0, 4096 }, { "shadow_xcd_run", 0, 4096 },
 	{ "primary_centre", 0, 1 }, { "sort_rank", 0, 1 }, { "ray_sort", 0, 1 }, { "shadow_sieve", 0, 64 },
 	{ "any_rays_per_wave", 0, 64 }, { "any_coop", 1, 1 << 30 }, { "uniform_reuse", 0, 1 },
-	{ "light_reuse", 0, 1 }, { "shadow_pairs", 0, 1 },
+	{ "light_reuse", 0, 1 }, { "shadow_pairs", 0, 1 }, { "shadow_frags", 0, 1 },
 };
 
 extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *value)
@@ -228,6 +228,8 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = (long long)ctx->shadow_key_bits;
 	else if (strcmp(key, "shadow_pairs_counted") == 0)
 		*value = ctx->shadow_pairs_counted ? 1 : 0;
+	else if (strcmp(key, "shadow_fragments") == 0) // (the pass itself writes the pinned word: current once the stream is waited for)
+		*value = ctx->shadow_frag_ran ? (long long)ctx->h_pinned[UGRT_PIN_SHADOW + 3] : 0;
 	else if (strcmp(key, "primary_deferred_merges") == 0)
 		*value = (long long)ctx->merges_deferred;
 	else if (strcmp(key, "primary_completed_merges") == 0)
@@ -324,9 +326,10 @@ extern "C" int ugrt_ctx_synchronize(ugrt_ctx *ctx)
 		for (int g = 0; g < 3; g++)
 			ctx->grid[g].have_est = false;
 		ctx->have_shadow_est = false;
+		ctx->have_frag_est = false;
 		ctx->overflow_repair = true;
 		return ugrt_fail(UGRT_EOVERFLOW, "an asynchronous call needed more room than its estimate gave it (status %u: "
-						  "1 grid build, 2 shadow candidate pairs, 4 shadow work items): the frames since the last "
+						  "1 grid build, 2 shadow candidate pairs, 4 shadow work items, 8 shadow fragments): the frames since the last "
 						  "synchronisation are incomplete, repeat them", bits);
 	}
 	ctx->overflow_repair = false;

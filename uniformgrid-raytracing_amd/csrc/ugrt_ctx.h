@@ -56,6 +56,7 @@ enum {
 	UGRT_OPT_UNIFORM_REUSE,    // "uniform_reuse": 0 = ugrt_grid_build_uniform builds every time (default 1: the grid is kept while its inputs stand)
 	UGRT_OPT_LIGHT_REUSE,      // "light_reuse": 0 = ugrt_grid_build_spherical builds every time (default 1: the grid is kept while the light and the geometry stand)
 	UGRT_OPT_SHADOW_PAIRS,     // "shadow_pairs": shadow tracer: 0 = the cull pass's candidate pairs are sorted by (beam, size class), 1 / default = counted into their buckets and placed (no sort); sorted anyway with "sort_library" 1 or where the bucket table would exceed SHADOW_BUCKET_WORDS (ugrt_trace_shadow.hip)
+	UGRT_OPT_SHADOW_FRAGS,     // "shadow_frags": shadow tracer, deferred ray sort: 0 = every ray is keyed and sorted, 1 / default = the rays of an 8x8-pixel tile that share a light cell are one sorted item (a fragment); every ray anyway with the sorted map, strict chunks, 64-bit keys, "sort_library" 1 or a band that is not whole tiles (ugrt_trace_shadow.hip)
 	UGRT_OPT_COUNT
 };
 
@@ -121,7 +122,8 @@ struct Grid {
 #define UGRT_DSMALL_SHADOW 254     // [10] shadow tracer: {pairs, beams} as checked, then its report: {pairs, beams} as
                                    // found, status word, pad, the two u64 work counters at the start of the exact pass
 #define UGRT_DSMALL_PRIMARY 264    // u64 [UGRT_PRIMARY_STATS] work counters of the primary tracer (FLAG_COUNT_WORK)
-#define UGRT_DSMALL_WORDS (132 + 104 + 28 + 32)
+#define UGRT_DSMALL_FRAGS 296       // [3] shadow tracer by fragments: cursor, finished workgroups (both zero between passes), checked count
+#define UGRT_DSMALL_WORDS (132 + 104 + 28 + 32 + 4)
 // layout of ugrt_ctx::h_pinned (u32 words of pinned host memory for small read-backs)
 #define UGRT_PIN_RW 0           // {narrow references, wide triangles} of the running (waiting) build
 #define UGRT_PIN_CELLS_USED 4   // [3] per grid
@@ -133,15 +135,17 @@ struct Grid {
 #define UGRT_PIN_REPORT 32      // [3][4] report of a grid's asynchronous build, written by its kernels straight into these
                                 // words: {narrow references, wide triangles} as found (what the next build is sized by),
                                 // cells used, the status word at its end
-#define UGRT_PIN_SHADOW 44      // [8] copy of the shadow tracer's report (UGRT_DSMALL_SHADOW + 2 ...)
+#define UGRT_PIN_SHADOW 44      // [8] copy of the shadow tracer's report (UGRT_DSMALL_SHADOW + 2 ...); word 3: the fragments the
+                                // last fragment pass formed (written by that pass only)
 #define UGRT_PIN_WORDS 64
 #define UGRT_STATUS_BUILD_OVERFLOW 1u
 #define UGRT_STATUS_PAIR_OVERFLOW 2u
 #define UGRT_STATUS_ITEM_OVERFLOW 4u
+#define UGRT_STATUS_FRAG_OVERFLOW 8u
 #define UGRT_DDA_STATS 46
 #define UGRT_PRIMARY_STATS 16
 static_assert(UGRT_DSMALL_DDA + 2 * UGRT_DDA_STATS <= UGRT_DSMALL_RW, "the DDA's counters run into the build counts");
-static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
+static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_FRAGS && UGRT_DSMALL_FRAGS + 3 <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
 
 struct ProfPair {
 	hipEvent_t a, b;
@@ -242,6 +246,10 @@ struct ugrt_ctx {
 	// asynchronous shadow pass: candidate pairs and beams of the last pass
 	u32 est_pairs = 0, est_beams = 0;
 	bool have_shadow_est = false, shadow_async_pending = false;
+	// shadow pass by fragments (option "shadow_frags"): the fragments of the last such pass as an estimate for the next
+	// asynchronous one, and whether the last pass of all was one (ugrt_ctx_get_state "shadow_fragments")
+	u32 est_frags = 0;
+	bool have_frag_est = false, shadow_frag_ran = false;
 	u32 shadow_key_bits = 0; // key bits the last shadow pass sorted its rays on (ugrt_ctx_get_state "shadow_key_bits")
 	unsigned long long stats[8] = { 0 };
 	unsigned long long dda_stats[UGRT_DDA_STATS] = { 0 }; // ugrt_stats_dda

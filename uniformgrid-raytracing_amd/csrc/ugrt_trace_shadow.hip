@@ -9,7 +9,10 @@
 // cell's whole list for every such chunk.  Here, privately to this tracer (d_map / prefix / the
 // light grid's arrays are not modified):
 //   1. the traced rays of a cell are re-grouped by a Z code of their direction from the light (octahedral map, or
-//      the cube's Morton code in 64-bit keys): `beam` rays are a narrow beam, summarised by its direction box (32 B);
+//      the cube's Morton code in 64-bit keys): `beam` rays are a narrow beam, summarised by its direction box (32 B).
+//      Where the ray sort was put off (the map is the unsorted one, every ray is traced) the rays of an 8x8-pixel tile
+//      that share a light cell are keyed, and sorted, as ONE item with the code of its first ray (FRAGMENTS below; option
+//      "shadow_frags" 0, the sorted map, strict chunks, 64-bit keys and "sort_library" 1 key and sort every ray);
 //   2. CULL pass, lane = triangle: a wave keeps 64 triangles of a cell in registers (with the
 //      ray-independent halves of the interval test) and streams the cell's beam boxes past them;
 //      the (beam, triangle) pairs that cannot be ruled out are appended to a list.  Triangles are
@@ -170,6 +173,244 @@ __global__ __launch_bounds__(WL_THREADS) void k_shadow_runs(const K *__restrict_
 		rstart[c] = i;
 	if (i == n - 1 || (u32)(keys[i + 1] >> shift) != c)
 		rend[c] = i + 1;
+}
+
+// FRAGMENTS (option "shadow_frags", the default where the ray sort is deferred and every chunk is traced).  The sort only
+// has to make `beam` consecutive rays of a light cell a narrow beam, and its keys barely tell the rays apart: the rays of
+// an 8x8-pixel tile that share a light cell and a block of direction codes (a fragment: 15 rays on average on the
+// 1 M-triangle frame) lie next to each other on a surface and get ONE key, (cell << mbits) | code of the fragment's first ray.  The fragments are sorted
+// instead of the rays (17 to 90 times fewer items through the same passes), their ray counts scanned, and every fragment
+// then writes its rays' pixel ids to its place and, at a cell's first and last fragment, the cell's run bounds: the
+// arrays behind this step are the per-ray path's (rstart / rend per light cell in ray units, the pixel ids in (cell, beam)
+// order).  Rays that nothing can shadow (sentinel cell, empty list) belong to no fragment and to no run.
+// A wave takes a tile: lane l reads entry (ty * 8 + l / 8) * W + tx * 8 + l % 8 of the band's map -- the pixel as well,
+// so a map in another order only makes the fragments less coherent.  The tile's live lanes are split with ballots.  A workgroup keeps its fragments in LDS and appends them FRAG_BUF at a time: one add on the cursor per flush
+// (10 k adds on one word take 0.12 ms, see PAIR_SEGS).  The flush also counts the first digit of the keys (RsFirst).
+// The order of fragments with equal keys follows the order of the flushes and differs from run to run; a ray's flag does
+// not depend on the grouping of the traced rays.
+// The code is that of the fragment's first ray.  (The normalised mean direction of its rays -- three wave sums per
+// fragment -- was measured: the frame was 1.6 % slower with it)
+#define FRAG_BUF 1024u
+// A light cell is not a compact patch of directions (the reference's cell row multiplies where it should add), so the
+// rays of a tile that share a cell may lie far apart as seen from the light, interleaved pixel by pixel: split by cell
+// alone, a fragment filed under its first ray's code carries strays into a beam and widens its box (the exact pass staged
+// 30 % more candidates on the 1 M-triangle frame; quadrants of the tile did not help).  The tile's rays are therefore
+// split by (cell, top FRAG_SPLIT_BITS bits of the ray's OWN code): 12 bits leave the staged candidates 4 % above the
+// per-ray sort's with 136 k fragments; all 17 bits bring them level with 206 k fragments and a slower frame.
+#ifndef FRAG_SPLIT_BITS
+#define FRAG_SPLIT_BITS 12u
+#endif
+#define FRAG_TILES 2u                                // tiles a wave takes per round
+#define FRAG_ROUND (FRAG_TILES * (WL_THREADS / 64u)) // ... and a workgroup
+struct FragRec { // (16 bytes: one load)
+	u32 tile, mask_lo, mask_hi, pad;
+};
+
+__global__ __launch_bounds__(WL_THREADS) void k_shadow_frags(CamBlock cam, const float *__restrict__ t_value_list,
+							      const float *__restrict__ ray_direction_list,
+							      const u32 *__restrict__ d_map, u32 n, u32 W, u32 C,
+							      const u32 *__restrict__ span, const float *__restrict__ cmPt, u32 mbits,
+							      u32 *__restrict__ keys, u32 *__restrict__ slots, FragRec *__restrict__ recs,
+							      u32 *__restrict__ fw, u32 cap, u32 *__restrict__ status, u32 *__restrict__ report,
+							      u32 *__restrict__ zero, u32 nzero, u32 *__restrict__ zero2, u32 nzero2,
+							      u32 *__restrict__ zero3, u32 nzero3, RsFirst hs)
+{
+	__shared__ u32 s_rsh[RS_BINS * RS_PRIV];
+	__shared__ u32 s_key[FRAG_BUF], s_tile[FRAG_BUF], s_mlo[FRAG_BUF], s_mhi[FRAG_BUF];
+	__shared__ u32 s_cnt, s_base;
+	// (the words k_shadow_keys clears: run bounds per light cell, the pass's counters, the cull pass's cursors)
+	for (u32 z = blockIdx.x * WL_THREADS + threadIdx.x; z < nzero; z += gridDim.x * WL_THREADS)
+		zero[z] = 0;
+	for (u32 z = blockIdx.x * WL_THREADS + threadIdx.x; z < nzero2; z += gridDim.x * WL_THREADS)
+		zero2[z] = 0;
+	for (u32 z = blockIdx.x * WL_THREADS + threadIdx.x; z < nzero3; z += gridDim.x * WL_THREADS)
+		zero3[z] = 0;
+	d_rs_zero(s_rsh, hs);
+	if (threadIdx.x == 0)
+		s_cnt = 0;
+	__syncthreads();
+	const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	const u32 ntiles = n >> 6, tilesx = W >> 3;
+	// FRAG_BUF fragments of the workgroup go out with one add on the cursor (all threads)
+	auto flush = [&]() {
+		const u32 cnt = s_cnt;
+		if (threadIdx.x == 0)
+			s_base = atomicAdd(&fw[0], cnt);
+		__syncthreads();
+		const u32 base = s_base;
+		for (u32 i0 = 0; i0 < cnt; i0 += WL_THREADS) {
+			const u32 i = i0 + threadIdx.x;
+			const bool ok = i < cnt && base + i < n; // (a fragment holds a ray: there are never more than n)
+			u32 key = 0;
+			if (ok) {
+				key = s_key[i];
+				keys[base + i] = key;
+				slots[base + i] = base + i;
+				FragRec r = { s_tile[i], s_mlo[i], s_mhi[i], 0u };
+				recs[base + i] = r;
+			}
+			if (hs.hist)
+				d_rs_count(s_rsh, key & 0xFFu, ok);
+		}
+		__syncthreads();
+		if (threadIdx.x == 0)
+			s_cnt = 0;
+		__syncthreads();
+	};
+	// (a wave takes FRAG_TILES tiles a round, their loads side by side: the round is a chain of three dependent loads)
+	for (u32 t0 = blockIdx.x * FRAG_ROUND; t0 < ntiles; t0 += gridDim.x * FRAG_ROUND) {
+		u32 tile[FRAG_TILES], pixel[FRAG_TILES], cell[FRAG_TILES];
+		bool live[FRAG_TILES];
+		float rd[FRAG_TILES][3];
+#pragma unroll
+		for (u32 u = 0; u < FRAG_TILES; u++) {
+			tile[u] = t0 + u * (WL_THREADS / 64u) + wave;
+			pixel[u] = 0u, cell[u] = C;
+			if (tile[u] < ntiles) { // (wave-uniform)
+				const u32 ty = tile[u] / tilesx, tx = tile[u] - ty * tilesx;
+				const u32 i = (ty * 8u + (lane >> 3)) * W + tx * 8u + (lane & 7u);
+				pixel[u] = d_map[i];
+				cell[u] = d_map[n + i];
+			}
+		}
+#pragma unroll
+		for (u32 u = 0; u < FRAG_TILES; u++)
+			live[u] = cell[u] < C && span[cell[u] < C ? cell[u] : 0u] != 0u;
+#pragma unroll
+		for (u32 u = 0; u < FRAG_TILES; u++) {
+			rd[u][0] = rd[u][1] = rd[u][2] = 0.0f;
+			if (live[u]) {
+				const float tVal = t_value_list[pixel[u]];
+				rd[u][0] = (cmPt[0] + tVal * ray_direction_list[pixel[u] * 3 + 0]) - cam.cc[0];
+				rd[u][1] = (cmPt[1] + tVal * ray_direction_list[pixel[u] * 3 + 1]) - cam.cc[1];
+				rd[u][2] = (cmPt[2] + tVal * ray_direction_list[pixel[u] * 3 + 2]) - cam.cc[2];
+			}
+		}
+#pragma unroll
+		for (u32 u = 0; u < FRAG_TILES; u++) {
+			unsigned long long left = __ballot(live[u]), mine = 0ull;
+			if (left == 0ull) // (wave-uniform: no live ray, or no tile)
+				continue;
+			D_NORMALIZE(rd[u]);
+			u32 nfrag = 0, rank = 0;
+			const u32 code = d_dir_oct(rd[u], (mbits + 1u) / 2u, mbits / 2u);
+			const u32 sb = FRAG_SPLIT_BITS < mbits ? FRAG_SPLIT_BITS : mbits;
+			const u32 part = (cell[u] << sb) | (code >> (mbits - sb)); // (cell, block of the direction code)
+			while (left != 0ull) { // 1 to 64 rounds: a fragment per (cell, code block) of the tile
+				const u32 lead = (u32)__builtin_ctzll(left);
+				const u32 c = (u32)__builtin_amdgcn_readlane((int)part, (int)lead);
+				const unsigned long long same = __ballot(live[u] && part == c);
+				if (lane == lead) {
+					mine = same;
+					rank = nfrag;
+				}
+				nfrag++;
+				left &= ~same;
+			}
+			u32 base = 0;
+			if (lane == 0u)
+				base = atomicAdd(&s_cnt, nfrag);
+			base = (u32)__shfl((int)base, 0);
+			if (mine != 0ull) { // the fragment's first lane
+				const u32 at = base + rank;
+				s_key[at] = (cell[u] << mbits) | code;
+				s_tile[at] = tile[u];
+				s_mlo[at] = (u32)mine;
+				s_mhi[at] = (u32)(mine >> 32);
+			}
+		}
+		__syncthreads();
+		if (s_cnt > FRAG_BUF - 64u * FRAG_ROUND) // (the next round adds up to 64 fragments per tile)
+			flush();
+	}
+	if (s_cnt)
+		flush();
+	d_rs_flush(s_rsh, hs);
+	// The last workgroup to get here checks the count against the capacity the launches behind this kernel were made for
+	// (the sort, the scan, the expansion) and leaves {cursor, finished workgroups} at zero for the next pass.  Waiting
+	// form: the capacity is n, which no count exceeds.  Asynchronous form: an estimate; a count beyond it raises
+	// UGRT_STATUS_FRAG_OVERFLOW and no fragment counts (fw[2] = 0): no run, no beam, nothing is traced, the frame is
+	// repeated.  The count found goes to the pass's report: the next asynchronous pass is sized by it.
+	if (threadIdx.x == 0) {
+		asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // (this thread's adds on the cursor have been acknowledged)
+		if (atomicAdd(&fw[1], 1u) == gridDim.x - 1u) {
+			const u32 F = atomicExch(&fw[0], 0u);
+			fw[1] = 0u;
+			fw[2] = F <= cap ? F : 0u;
+			report[3] = F;
+			if (F > cap)
+				atomicOr(status, UGRT_STATUS_FRAG_OVERFLOW);
+		}
+	}
+}
+
+// rays per sorted fragment, formed where their scan loads them (ugrt_scan.h); count: the checked fragment count
+struct FragCountLoad {
+	const u32 *slots;
+	const FragRec *recs;
+	const u32 *count;
+	__device__ __forceinline__ void operator()(u32 base, u32 n, u32 (&v)[SC_ITEMS]) const
+	{
+		const u32 F = *count;
+		u32 s[SC_ITEMS];
+#pragma unroll
+		for (int k = 0; k < SC_ITEMS; k++)
+			s[k] = base + (u32)k < F && base + (u32)k < n ? slots[base + (u32)k] : 0xFFFFFFFFu;
+#pragma unroll
+		for (int k = 0; k < SC_ITEMS; k++) {
+			u32 x = 0;
+			if (s[k] != 0xFFFFFFFFu) {
+				const FragRec r = recs[s[k]];
+				x = (u32)__popc(r.mask_lo) + (u32)__popc(r.mask_hi);
+			}
+			v[k] = x;
+		}
+	}
+};
+
+// EXPANSION: sorted fragment j writes its rays' pixel ids to ray_pixels[incl[j] - rays(j) ...], in lane order, and the run
+// bounds of its cell where its neighbour's cell differs.  A wave takes FRAG_PER_WAVE fragments: their records are loaded
+// by as many lanes side by side, then the fragments are written out one after the other by all lanes, with nothing
+// between their loads of the map.
+#define FRAG_PER_WAVE 16u
+__global__ __launch_bounds__(WL_THREADS) void k_shadow_expand(const u32 *__restrict__ skeys, const u32 *__restrict__ slots,
+							       const FragRec *__restrict__ recs, const u32 *__restrict__ incl,
+							       const u32 *__restrict__ count, u32 mbits, const u32 *__restrict__ d_map, u32 n, u32 W,
+							       u32 *__restrict__ ray_pixels, u32 *__restrict__ rstart, u32 *__restrict__ rend)
+{
+	const u32 F = *count; // (checked)
+	const u32 lane = threadIdx.x & 63u;
+	const u32 tilesx = W >> 3;
+	const u32 nwaves = gridDim.x * (WL_THREADS / 64u);
+	for (u32 j0 = (blockIdx.x * (WL_THREADS / 64u) + (threadIdx.x >> 6)) * FRAG_PER_WAVE; j0 < F; j0 += nwaves * FRAG_PER_WAVE) {
+		u32 tile = 0, mlo = 0, mhi = 0, first = 0;
+		const u32 j = j0 + lane;
+		if (lane < FRAG_PER_WAVE && j < F) {
+			const FragRec r = recs[slots[j]];
+			const u32 end = incl[j], c = skeys[j] >> mbits;
+			tile = r.tile, mlo = r.mask_lo, mhi = r.mask_hi;
+			first = end - ((u32)__popc(mlo) + (u32)__popc(mhi));
+			if (j == 0u || (skeys[j - 1u] >> mbits) != c)
+				rstart[c] = first;
+			if (j == F - 1u || (skeys[j + 1u] >> mbits) != c)
+				rend[c] = end;
+		}
+#pragma unroll
+		for (u32 k = 0; k < FRAG_PER_WAVE; k++) {
+			// (lanes without a fragment hold an empty mask)
+			const u32 t = (u32)__builtin_amdgcn_readlane((int)tile, (int)k);
+			const u32 lo = (u32)__builtin_amdgcn_readlane((int)mlo, (int)k), hi = (u32)__builtin_amdgcn_readlane((int)mhi, (int)k);
+			const u32 at = (u32)__builtin_amdgcn_readlane((int)first, (int)k);
+			const unsigned long long mask = ((unsigned long long)hi << 32) | lo;
+			if ((mask >> lane) & 1ull) {
+				const u32 ty = t / tilesx, tx = t - ty * tilesx;
+				const u32 i = (ty * 8u + (lane >> 3)) * W + tx * 8u + (lane & 7u);
+				const u32 to = at + (u32)__popcll(mask & ((1ull << lane) - 1ull));
+				if (i < n && to < n)
+					ray_pixels[to] = d_map[i];
+			}
+		}
+	}
 }
 
 // per light cell: number of beams (ITEMS = false), or number of cull items = triangle batches x beam chunks -- formed
@@ -993,7 +1234,6 @@ __global__ __launch_bounds__(64) void k_trace_shadow(CamBlock cam, const u32 *__
 	// every kernel that raises a status bit or counts work has finished: complete the pass's report
 	if (blockIdx.x == 0 && lane == 0) {
 		report[2] = *status;
-		report[3] = 0u;
 		reinterpret_cast<unsigned long long *>(report + 4)[0] = work[0];
 		reinterpret_cast<unsigned long long *>(report + 4)[1] = work[1];
 	}
@@ -1200,6 +1440,7 @@ struct ShadowPass {
 	u32 *xincl, *iseg1, *isub1; // the exact pass's item list
 	// candidate pairs bucketed by counting (option "shadow_pairs") instead of sorted: the beam bound the bucket table is
 	// made for, its words, the counts and their inclusive sums; the cursors of the staging segments and a segment's room
+	bool deferred; // the ray sort was put off: d_map is the map as ugrt_map_rays_to_light left it and every ray is traced
 	bool counted;
 	u32 gbound, bkt_words, *bkt, *bincl, *segcnt, segcap;
 	const u32 *pair_tri; // the candidates' triangle ids in beam order, as the exact pass reads them
@@ -1226,6 +1467,7 @@ int ShadowPass::traced_chunks(unsigned num_chunks)
 			return ugrt_fail(UGRT_EINVAL, "trace_shadow: UGRT_CHUNKS_ON_DEVICE refers to the last ugrt_sort_rays, which "
 						      "sorted other arrays");
 		traced = num_chunks; // the keys kernel applies the launch rule itself
+		deferred = ctx->ray_sort_pending;
 		if (ctx->ray_sort_pending)
 			nchunks_arg = 0u; // every chunk is traced and none was formed: d_map is the unsorted map, all n rays count
 		else
@@ -1342,6 +1584,46 @@ int ShadowPass::beams()
 	RsFirst hs = { nullptr };
 	if (!key64 && own_sort && (rc = ugrt_sort_first_digit(ctx, &hs)))
 		return rc;
+	// by fragments (FRAGMENTS above) where the map is the unsorted one of whole 8x8 tiles and every ray is traced
+	const u32 W = (u32)ctx->cam.W;
+	const bool frags = deferred && !key64 && own_sort && ctx->opt[UGRT_OPT_SHADOW_FRAGS] != 0 && W != 0u && W % 8u == 0u &&
+			   n % (8u * W) == 0u;
+	ctx->shadow_frag_ran = frags;
+	if (frags) {
+		// the launches behind the fragment kernel are made for `fcap` fragments: all there can be (a fragment holds a ray),
+		// or, asynchronous form, the last fragment pass's count plus a quarter, against which the count is checked on the
+		// device by the fragment kernel.  The count travels in the pass's report (word 3 of the pinned words).
+		u32 *fw = ctx->d_small + UGRT_DSMALL_FRAGS; // {cursor, finished workgroups, checked count}
+		u32 fcap = n;
+		if (async) {
+			if (ctx->have_frag_est) {
+				ctx->est_frags = ctx->h_pinned[UGRT_PIN_SHADOW + 3];
+				const unsigned long long want = (unsigned long long)ctx->est_frags + ctx->est_frags / 4u + 1024u;
+				fcap = want < n ? (u32)want : n;
+			} else {
+				// (no fragment pass has reported yet and none is under way: until this one has, the estimate is all there can be)
+				ctx->h_pinned[UGRT_PIN_SHADOW + 3] = n;
+				ctx->have_frag_est = true;
+			}
+		}
+		u32 *fkeys = (u32 *)k0, *fincl = fkeys + n, *skeys = (u32 *)k1, *sslots = skeys + n;
+		FragRec *recs = (FragRec *)ctx->sray.p; // (the rebuilt rays are written behind the expansion, by k_shadow_boxes)
+		const u32 fb = (n / 64u + FRAG_ROUND - 1u) / FRAG_ROUND, fblocks = fb < 768u ? (fb ? fb : 1u) : 768u;
+		hipLaunchKernelGGL(k_shadow_frags, dim3(fblocks), dim3(WL_THREADS), 0, st, ctx->cam, d_t_value, d_ray_dir, d_map, n, W, C, d_span,
+				   d_cam_position, mbits, fkeys, v0, recs, fw, fcap, ctx->d_small + UGRT_DSMALL_STATUS,
+				   ctx->h_pinned + UGRT_PIN_SHADOW, rstart, 2u * ncellk, (u32 *)wcnt, 5u, (u32 *)ctx->pseg.p,
+				   PAIR_SEGS * PAIR_SEG_STRIDE, hs);
+		UGRT_HIP(hipGetLastError());
+		if ((rc = ugrt_sort_pairs_u32(ctx, fkeys, skeys, v0, sslots, fcap, (int)(mbits + cellbits), fw + 2, true)))
+			return rc;
+		const FragCountLoad nrays = { sslots, recs, fw + 2 };
+		if ((rc = ugrt_scan_launch<true>(ctx, nrays, fincl, fcap, ScanTailNone())))
+			return rc;
+		const u32 eb = (fcap + FRAG_PER_WAVE * (WL_THREADS / 64u) - 1u) / (FRAG_PER_WAVE * (WL_THREADS / 64u));
+		hipLaunchKernelGGL(k_shadow_expand, dim3(eb < 8192u ? (eb ? eb : 1u) : 8192u), dim3(WL_THREADS), 0, st, (const u32 *)skeys,
+				   (const u32 *)sslots, (const FragRec *)recs, (const u32 *)fincl, (const u32 *)(fw + 2), mbits, d_map, n, W, v1, rstart, rend);
+		UGRT_HIP(hipGetLastError());
+	} else {
 	hipLaunchKernelGGL(key64 ? k_shadow_keys<true> : k_shadow_keys<false>, dim3(kblocks), dim3(WL_THREADS), 0, st,
 			   ctx->cam, d_t_value, d_ray_dir, d_map, d_prefix_map, nchunks_arg, nchunks_arg ? traced : 0u, n, C, d_span,
 			   d_cam_position, key64 ? 30u : mbits, k0, v0, rstart, 2u * ncellk, nchunks_dev, launch_cap, ctx->chunk_capacity,
@@ -1361,6 +1643,7 @@ int ShadowPass::beams()
 		hipLaunchKernelGGL(k_shadow_runs<u32>, dim3((n + WL_THREADS - 1) / WL_THREADS), dim3(WL_THREADS), 0, st,
 				   (const u32 *)k1, n, mbits, rstart, rend);
 	UGRT_HIP(hipGetLastError());
+	} // every ray
 	// rays per beam: the cull pass costs (triangles of the cell) x (beams of the cell); the exact pass
 	// re-culls the beam's candidates against each 64-ray sub-group, so its cost barely depends on the
 	// beam size.  ~1000 rays per beam is the measured optimum on the 1 M-triangle scene (tools/beam_sweep.py)
@@ -1476,6 +1759,8 @@ int ShadowPass::cull()
 		ctx->est_pairs = P;
 		ctx->est_beams = G;
 		ctx->have_shadow_est = true;
+		if (ctx->shadow_frag_ran) // (the fragment kernel's report is in its pinned word)
+			ctx->have_frag_est = true;
 		// (the slots the asynchronous form reports into: never older than this pass)
 		ctx->h_pinned[UGRT_PIN_SHADOW] = P;
 		ctx->h_pinned[UGRT_PIN_SHADOW + 1] = G;

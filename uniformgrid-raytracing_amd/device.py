@@ -161,12 +161,14 @@ class Context:
 
     def set_option(self, key, value):
         """Launch-shape options (no effect on results), e.g. "dda_rays_per_wave"; "uniform_reuse" 0 makes
-        grid_build_uniform build every time, "light_reuse" 0 grid_build_spherical."""
+        grid_build_uniform build every time, "light_reuse" 0 grid_build_spherical, "shadow_frags" 0 the shadow pass
+        sort every ray where it would sort tile fragments."""
         check(lib.ugrt_ctx_set_option(self._h, key.encode(), int(value)))
 
     def get_state(self, key):
         """Counters and findings of the context: "radix_launches", "sort_rank_atomic", "shadow_key_bits" (key bits the
-        last shadow pass sorted its rays on), "uniform_builds_reused" (grid_build_uniform calls that kept the grid the
+        last shadow pass sorted its rays on), "shadow_fragments" (tile fragments the last shadow pass formed and sorted
+        instead of its rays, option "shadow_frags"; 0 = it sorted every ray), "uniform_builds_reused" (grid_build_uniform calls that kept the grid the
         context held), "light_builds_reused" (the same for grid_build_spherical), "primary_deferred_merges" / "primary_completed_merges" /
         "primary_merge_pending" (screen-grid builds that put their merge off, those merged later after all, one pending), "recip_mismatches" (runs the exhaustive check of the tracers' reciprocal
         on the device), "f2i_mismatches" (the same for the device's float -> integer conversions), "lane_reduce_mismatches"
