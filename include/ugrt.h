@@ -914,6 +914,62 @@ int ugrt_aa_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *
  * UGRT_EINVAL and nothing is enqueued. */
 int ugrt_aa_resolve(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_sum, int num_samples);
 
+/* ---- device: temporal accumulation, DESIGN.md section 6.12 ----
+ * A sequence of frames gives frame f a different sample set and carries a per-pixel running mean of the share of open
+ * rays (ambient occlusion, area light) or of the indirect light's colour from frame to frame: after N frames a pixel has
+ * seen N * S samples for the price of S per frame.  Under a moving camera the mean is fetched where the pixel's surface
+ * point lay in the previous frame, and dropped where the previous frame saw another surface there.  Per frame and effect:
+ * the walk, the gather (radius 0 when no gather is wanted: it forms the pair), ugrt_temporal_visibility or
+ * ugrt_temporal_gi, then the shading call of the gather's output on the temporal output.  All arithmetic is fp32 without
+ * contraction, in the stated order, or 32-bit integer. */
+#define UGRT_MAX_TEMPORAL_FRAMES 64
+#define UGRT_TEMPORAL_DEN 256u
+/* d_vis is what ugrt_filter_visibility wrote for this frame, d_orays / d_oactive this frame's {o, n} per pixel
+ * (ugrt_ao_rays), d_prev_orays / d_prev_oactive the previous frame's, prev_camcoords the EYE's camera block of the previous
+ * frame (host memory, float[64]; its modelview and projection rows are passed on by value), d_hist_in the history the
+ * previous frame's call wrote, float [2 * width * height]: (share, frames) per pixel; zeros start a sequence.  For an
+ * active pixel p = (x, y) of the band with (num, den) = d_vis[2p ..], den != 0 (an active pixel with den == 0 is treated
+ * as inactive), S = num_bits:
+ *   input share  c = (float)num / (float)(S * den), the unsigned product converted once.
+ *   reprojection the reference's vertex transform (MV, divide, P, divide; the arithmetic of the screen-grid binning) of
+ *     o_p = floats 0..2 of d_orays[6p] under prev_camcoords gives (ndc0, ndc1) and the projective w of the second divide;
+ *     fx = ((ndc0 + 1.0f) / 2.0f) * (float)width, fy = ((ndc1 + 1.0f) / 2.0f) * (float)height, the binning's mapping,
+ *     unflipped: it sends the hit point of pixel (col, row) under its own camera to (col, row).  No history when w is not
+ *     > 0, when fx, fy or w is a NaN, or unless -1 < fx < width and -1 < fy < height.
+ *   taps  X = ugrt_floor2i(fx * 16.0f + 0.5f), ix = X >> 4, ax = X & 15, Y, iy, ay likewise; the taps are
+ *     q = (ix + i, iy + j), i, j in {0, 1}, in the order (0,0), (1,0), (0,1), (1,1), with the integer weights
+ *     w = (i ? ax : 16 - ax) * (j ? ay : 16 - ay).  A tap of weight 0 is not read.  A tap counts when q is inside the
+ *     image and inside the band's rows, d_prev_oactive[q] != 0, its stored frames_q >= 1, its stored share h_q is in
+ *     [0, 1] (a NaN rejects), (n_p0*n_q0 + n_p1*n_q1) + n_p2*n_q2 >= normal_cos and
+ *     |(d0*n_p0 + d1*n_p1) + d2*n_p2| <= plane_tol with d = o_q(previous) - o_p: ugrt_filter_visibility's two tests.
+ *   blend  no tap counts: h = c, n = 1.  Otherwise hp = (sum of (float)w * h_q, from 0.0f in tap order) / (float)(sum of
+ *     w), n = min(min over the counted taps of frames_q + 1.0f, (float)max_frames), h = hp + (c - hp) / n; n = 1
+ *     (max_frames = 1) gives h = c itself, not hp + (c - hp), which may miss c by an ulp.
+ *   output  d_hist_out[2p ..] = (h, n); d_vis_out[2p] = min(S * 256, ugrt_floor2i(h * (float)(S * 256u) + 0.5f)),
+ *     d_vis_out[2p + 1] = UGRT_TEMPORAL_DEN.
+ * Inactive pixels of the band get zeros in both outputs (frame count 0), pixels outside the band are not written;
+ * max_frames = 1 gives back the quantised input.  The pair is what ugrt_shade_area_vis and ugrt_ao_shade_vis consume:
+ * with den = 256 and num <= 32 * 256 their largest products are 255 * 3 * 32 * 256 and 255 * 32 * 256, below the
+ * bounds they document for the gather's den <= 6561.  One launch, a 32 x 8 tile per workgroup, no LDS, no atomic
+ * operation.  Stage UGRT_ST_SHADE.  max_frames outside 1..UGRT_MAX_TEMPORAL_FRAMES, num_bits outside 1..32, a plane_tol
+ * that is negative or a NaN, a NaN normal_cos, d_hist_in == d_hist_out, d_vis == d_vis_out (neighbours are read) or a
+ * null argument: UGRT_EINVAL (the message names the argument) and nothing is enqueued. */
+int ugrt_temporal_visibility(ugrt_ctx *ctx, const unsigned *d_vis, int num_bits, const float *d_orays, const int *d_oactive,
+			     const float *prev_camcoords, const float *d_prev_orays, const int *d_prev_oactive,
+			     const float *d_hist_in, int max_frames, float normal_cos, float plane_tol, float *d_hist_out,
+			     unsigned *d_vis_out);
+/* The same over ugrt_gi_filter's sums (radius 0 reproduces ugrt_gi_gather's): d_acc, d_acc_out unsigned and d_hist_in,
+ * d_hist_out float [4 * width * height], all 16-byte aligned; the history is (r, g, b shares, frames) per pixel.  With
+ * den = d_acc[4p + 3] and S = num_dirs: c_k = (float)d_acc[4p + k] / (float)(255u * S * den); a tap counts when all three
+ * stored shares are in [0, 1]; every channel is blended with the same taps, weights and n; d_acc_out[4p + k] =
+ * min(255 * S * 256, ugrt_floor2i(h_k * (float)(255u * S * 256u) + 0.5f)), d_acc_out[4p + 3] = UGRT_TEMPORAL_DEN.  That is
+ * what ugrt_gi_apply consumes: its divisor 255 * num_dirs * den is at most 255 * 32 * 256.  Everything else, the errors
+ * included (num_dirs in the place of num_bits; also a buffer of the four that is not 16-byte aligned), is
+ * ugrt_temporal_visibility's. */
+int ugrt_temporal_gi(ugrt_ctx *ctx, const unsigned *d_acc, int num_dirs, const float *d_orays, const int *d_oactive,
+		     const float *prev_camcoords, const float *d_prev_orays, const int *d_prev_oactive, const float *d_hist_in,
+		     int max_frames, float normal_cos, float plane_tol, float *d_hist_out, unsigned *d_acc_out);
+
 /* ---- device: animation (scene.h:122,336) -------------------------------- */
 /* Model::rotate_bunny(float) -> copy_data_transform, transformation_kernel.cu:4 */
 int ugrt_animate(ugrt_ctx *ctx, float *d_vertlist, const float *d_orig_list, int size, int offset,

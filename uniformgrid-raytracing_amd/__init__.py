@@ -63,6 +63,8 @@ MAX_FILTER_RADIUS = 8  # UGRT_MAX_FILTER_RADIUS
 MAX_AO_SET_TILE = 4  # UGRT_MAX_AO_SET_TILE
 MAX_AO_SET_DIRS = 512  # UGRT_MAX_AO_SET_DIRS
 MAX_AA_SAMPLES = 32  # UGRT_MAX_AA_SAMPLES
+MAX_TEMPORAL_FRAMES = 64  # UGRT_MAX_TEMPORAL_FRAMES
+TEMPORAL_DEN = 256  # UGRT_TEMPORAL_DEN
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -196,6 +198,8 @@ PROTOTYPES = {
     "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
     "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ugrt_temporal_visibility": (C.c_int, [_P, _P, C.c_int, _P, _P, _F3, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "ugrt_temporal_gi": (C.c_int, [_P, _P, C.c_int, _P, _P, _F3, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),
     "ugrt_prof_enable": (C.c_int, [_P, C.c_int]),
     "ugrt_prof_reset": (C.c_int, [_P]),

@@ -514,6 +514,30 @@ class Context:
         (sums[4p + k] + num_samples // 2) // num_samples; every other pixel stays."""
         check(lib.ugrt_aa_resolve(self._h, _ptr(img), _ptr(sums), int(num_samples)))
 
+    # -- temporal accumulation (DESIGN.md section 6.12) -------------------------
+    def temporal_visibility(self, vis, num_bits, orays, oactive, prev_camcoords, prev_orays, prev_oactive, hist_in, max_frames,
+                            normal_cos, plane_tol, hist_out, vis_out):
+        """The running mean of a gathered share: vis is what filter_visibility wrote for this frame, hist_in / hist_out
+        floats [2 * W * H], (share, frames) per pixel.  The share c = vis[2p] / (num_bits * vis[2p + 1]) of an active pixel
+        is blended into the history of the frame before, fetched with four taps in sixteenths of a pixel where the pixel's
+        origin (orays) lay under prev_camcoords (64 host floats: the EYE's block of the previous frame) and kept where
+        prev_orays / prev_oactive hold the same surface (normal_cos, plane_tol): h = hp + (c - hp) / n, n = min(frames of
+        the taps + 1, max_frames); without a tap h = c, n = 1.  vis_out: the pair (round(h * num_bits * 256), 256) that
+        shade_area_vis and shade_ao_vis take; uint32 words [2 * W * H] (an int32 tensor serves)."""
+        check(lib.ugrt_temporal_visibility(self._h, _ptr(vis), int(num_bits), _ptr(orays), _ptr(oactive),
+                                           None if prev_camcoords is None else _f3(prev_camcoords), _ptr(prev_orays),
+                                           _ptr(prev_oactive), _ptr(hist_in), int(max_frames), normal_cos, plane_tol,
+                                           _ptr(hist_out), _ptr(vis_out)))
+
+    def temporal_gi(self, acc, num_dirs, orays, oactive, prev_camcoords, prev_orays, prev_oactive, hist_in, max_frames,
+                    normal_cos, plane_tol, hist_out, acc_out):
+        """temporal_visibility over gi_filter's sums: acc / acc_out uint32 words and hist_in / hist_out floats
+        [4 * W * H], (r, g, b shares, frames) per pixel, c_k = acc[4p + k] / (255 * num_dirs * acc[4p + 3]); acc_out:
+        (round(h_k * 255 * num_dirs * 256) for k < 3, 256), what gi_apply takes."""
+        check(lib.ugrt_temporal_gi(self._h, _ptr(acc), int(num_dirs), _ptr(orays), _ptr(oactive),
+                                   None if prev_camcoords is None else _f3(prev_camcoords), _ptr(prev_orays), _ptr(prev_oactive),
+                                   _ptr(hist_in), int(max_frames), normal_cos, plane_tol, _ptr(hist_out), _ptr(acc_out)))
+
     # -- animation -----------------------------------------------------------
     def animate(self, verts, orig, size, offset, rot):
         check(lib.ugrt_animate(self._h, _ptr(verts), _ptr(orig), size, offset, rot))

@@ -32,7 +32,9 @@ hemisphere rays of ``ao``, in a walk that keeps a pixel's rays side by side in a
 ``gi=S`` the one-stream single-light frame adds one bounce of indirect diffuse light: S hemisphere rays per primary hit to
 their first hit, which is shaded and shadowed, and a pass that adds the mean to the image.  With
 ``aa=S`` the one-stream single-light plain frame is anti-aliased where it needs it: the pixels on an edge send S sub-pixel
-eye rays through the uniform grid and take the mean of their colours.
+eye rays through the uniform grid and take the mean of their colours.  With ``temporal=N`` the
+frames of a sequence give ``ao``, ``area`` and ``gi`` a different sample set each and blend every frame's share into a
+running mean over at most N frames, reprojected through the surface point when the camera moves.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -42,7 +44,8 @@ import contextlib
 
 import numpy as np
 
-from . import GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS, MAX_REFLECT_DEPTH
+from . import (GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS,
+               MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -288,6 +291,38 @@ def check_aa(aa, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True, reflect=
     return int(aa), int(aa_sets), float(np.float32(aa_cos)), aa_plane, bool(aa_shadows)
 
 
+def check_temporal(temporal, temporal_cos=0.9, temporal_plane=None, effects=False, lights=None, reflect_lights=False,
+                   two_streams=False):
+    """The keywords of the temporal accumulation.  temporal: 0 (off, and the other two must be at
+    their defaults) or an integer 2..MAX_TEMPORAL_FRAMES, the most frames a running mean spans; temporal_cos: a number (no
+    NaN); temporal_plane: None (default_filter_plane) or a number not below 0.  temporal > 0 needs one of ao, area and gi
+    (effects), a single-light frame (lights: setup.lights; reflect_lights) and the one-stream Renderer.  ValueError before
+    anything is enqueued.  Returns None (off) or (temporal, cos, plane or None)."""
+    if isinstance(temporal, (bool, np.bool_)) or not isinstance(temporal, (int, np.integer)) \
+            or not (temporal == 0 or 2 <= temporal <= MAX_TEMPORAL_FRAMES):
+        raise ValueError("temporal must be 0 or an integer in 2..%d, not %r" % (MAX_TEMPORAL_FRAMES, temporal))
+    number = (int, float, np.integer, np.floating)
+    if isinstance(temporal_cos, (bool, np.bool_)) or not isinstance(temporal_cos, number) or np.isnan(np.float32(temporal_cos)):
+        raise ValueError("temporal_cos must be a number, not %r" % (temporal_cos,))
+    if temporal_plane is not None:
+        if isinstance(temporal_plane, (bool, np.bool_)) or not isinstance(temporal_plane, number) \
+                or not float(np.float32(temporal_plane)) >= 0.0:
+            raise ValueError("temporal_plane must be None or a number not below 0, not %r" % (temporal_plane,))
+        temporal_plane = float(np.float32(temporal_plane))
+    if temporal == 0:
+        if float(np.float32(temporal_cos)) != float(np.float32(0.9)) or temporal_plane is not None:
+            raise ValueError("temporal_cos and temporal_plane need temporal > 0: they shape the accumulation")
+        return None
+    if not effects:
+        raise ValueError("temporal needs ao, area or gi: it averages their samples over the frames")
+    if lights is not None or reflect_lights:
+        raise ValueError("temporal needs a single-light frame: the accumulation under setup.lights is not built")
+    if two_streams:
+        raise ValueError("temporal needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid "
+                         "on a side context")
+    return int(temporal), float(np.float32(temporal_cos)), temporal_plane
+
+
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
 # BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
@@ -485,6 +520,42 @@ def gi_shade(c, f, gi):
     c.gi_apply(f.image, acc, gi[0], gi[4], f.intersect_id, f.d_matlist, f.num_materials)
 
 
+def temporal_blend(c, f, tp, st, call, sums, S, out):
+    """One effect's temporal call: this frame's gathered sums into the effect's running mean and
+    the pair its shading call takes.  tp: Renderer._temporal_begin's frame record; st: the effect's state, whose two
+    histories change roles here and whose frame counter advances; call: "temporal_visibility" or "temporal_gi"."""
+    turn = st["turn"]
+    getattr(c, call)(sums, S, f.ao_rays, f.ao_active, tp["prev_cam"], f.prev_ao_rays, f.prev_ao_active, st["hist"][turn],
+                     tp["max"], tp["cos"], tp["plane"], st["hist"][1 - turn], out)
+    st["turn"] = 1 - turn
+    st["n"] += 1
+
+
+def ao_shade_temporal(c, f, tp, ao):
+    """ao_shade in a temporal frame (ao: Renderer._temporal_ao's): the gather (radius 0 without ao_filter: it forms the
+    pair), the running mean, and shade_ao_vis from the mean."""
+    dirs, _, sets, st = ao
+    c.filter_visibility(f.ao_mask, len(dirs), f.ao_rays, f.ao_active, sets[2][0], sets[2][1], sets[2][2], f.ao_vis)
+    temporal_blend(c, f, tp, st, "temporal_visibility", f.ao_vis, len(dirs), f.ao_tvis)
+    c.shade_ao_vis(f.image, f.ao_tvis, len(dirs))
+
+
+def area_shade_temporal(c, f, tp, area):
+    """The penumbra of a temporal frame (area: Renderer._temporal_area's): gather, running mean, shade_area_vis."""
+    S, _, _, gather, st = area
+    c.filter_visibility(f.area_mask, S, f.ao_rays, f.ao_active, gather[0], gather[1], gather[2], f.area_vis)
+    temporal_blend(c, f, tp, st, "temporal_visibility", f.area_vis, S, f.area_tvis)
+    c.shade_area_vis(f.image, f.area_tvis, S)
+
+
+def gi_shade_temporal(c, f, tp, gi):
+    """gi_shade in a temporal frame (gi: Renderer._temporal_gi's): gi_filter, the running mean of the three channels,
+    gi_apply from the mean."""
+    c.gi_filter(f.gi_sum, f.ao_rays, f.ao_active, gi[5][0], gi[5][1], gi[5][2], f.gi_acc)
+    temporal_blend(c, f, tp, gi[7], "temporal_gi", f.gi_acc, gi[0], f.gi_tacc)
+    c.gi_apply(f.image, f.gi_tacc, gi[0], gi[4], f.intersect_id, f.d_matlist, f.num_materials)
+
+
 def aa_edges(c, f, cam_pos, aa, shadows):
     """The anti-aliasing's edge flags into f.aa_edge, behind the shadow stage and before the
     shading call that rewrites the ids.  aa: Renderer._aa_stage's (S, (set_w, set_h), table, cos, plane, shadows); shadows:
@@ -631,6 +702,17 @@ class _Frame:
         # offset tables by (aa, aa_sets)
         self.aa_edge = self.aa_sum = None
         self._aa_set_tables = {}
+        # temporal: the previous frame's {o, n} and active flags (they change places with ao_rays / ao_active at the start
+        # of every temporal frame), the temporal calls' outputs, the effects' states by name -- two histories, which of
+        # them is read next, frames since the reset, the parameters they were accumulated under --, the 16 rotated tables
+        # per key, and the eye's block of the frame before (Renderer._temporal_begin)
+        self.prev_ao_rays = self.prev_ao_active = None
+        self.ao_tvis = self.area_tvis = self.gi_tacc = None
+        self._temporal = {}
+        self._temporal_set_tables = {}
+        self._temporal_prev_cam = None
+        self._temporal_live = False
+        self._temporal_serial = 0
         self.reflect_eps = float(reflect_eps)
         self.aspect = float(np.float32(ctx.width) / np.float32(ctx.height))
 
@@ -836,6 +918,34 @@ class Renderer(_Frame, _Band):
         self.ctx.animate(self.d_verts, self.orig, self.orig_size, self.orig_offset, rot)
         if self.aux is not None:
             self.aux.geometry_changed()  # the second context did not see the call
+        self.temporal_reset()
+
+    def geometry_changed(self):
+        """The vertex or face array was rewritten outside rotate_bunny: Context.geometry_changed on every context, and the
+        temporal histories start again."""
+        self.ctx.geometry_changed()
+        if self.aux is not None:
+            self.aux.geometry_changed()
+        self.temporal_reset()
+
+    def temporal_reset(self):
+        """Every effect's running mean starts again with the next temporal frame: the frame
+        counters go back to 0 and the histories are cleared in stream order.  display does this by itself when the
+        geometry changes (rotate_bunny, geometry_changed), when an effect's parameters or, for area, the light change
+        (that effect only), and when the frame before was not a temporal one.  A renderer that never rendered a
+        temporal frame enqueues nothing here."""
+        for st in getattr(self, "_temporal", {}).values():
+            self._temporal_clear(st)
+
+    def _temporal_clear(self, st):
+        st["hist"][st["turn"]].zero_()  # (the one the next call reads; it rewrites the other one whole)
+        st["n"] = 0
+
+    def temporal_history(self, name):
+        """The running mean of effect `name` ("ao", "area": floats [2 W*H], (share, frames) per pixel; "gi": [4 W*H],
+        (r, g, b, frames)) as the last temporal frame left it."""
+        st = self._temporal[name]
+        return st["hist"][st["turn"]]
 
     def close(self):
         """Stops the helper thread of an overlapped renderer."""
@@ -848,7 +958,8 @@ class Renderer(_Frame, _Band):
                 reflect_lights=False, ao=0, ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1,
                 area_filter=0, area_filter_cos=0.9, area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9,
                 ao_filter_plane=None, gi=0, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0,
-                gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True):
+                gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True,
+                temporal=0, temporal_cos=0.9, temporal_plane=None):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -894,7 +1005,15 @@ class Renderer(_Frame, _Band):
         (scenes.aa_offset_sets(aa, aa_sets), uploaded once per (aa, aa_sets)) through the uniform grid, each shaded as
         the frame shades a primary hit and, with shadows and aa_shadows, shadowed from the light camera's eye; aa_sum
         holds the bytes' sums and their mean replaces the pixel behind the frame's own shading and before ambient
-        occlusion scales it."""
+        occlusion scales it.
+        temporal (one-stream renderer, single-light frames, plain, reflect or refract; needs ao, area or gi; 0: off):
+        consecutive display calls are the frames of a sequence -- frame f gives every effect that is on the f-th of 16
+        rotated sample tables (scenes.temporal_sets of the 16-set table; uploaded once per key), the effect's gather (radius
+        0 without *_filter) is blended into its running mean over at most temporal = 2..64 frames, fetched where the
+        pixel's surface point lay under the previous frame's camera and dropped where the previous frame's normal
+        (temporal_cos) or plane (temporal_plane; None: 1 % of the scene's largest extent) differ, and the effect is shaded
+        from the mean (ao_tvis, area_tvis, gi_tacc; temporal_history).  A camera change does not reset the mean;
+        temporal_reset lists what does."""
         aa = check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), area, gi,
                       reflect_lights, self.aux is not None)
         gi = check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
@@ -908,6 +1027,10 @@ class Renderer(_Frame, _Band):
         reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
         ao, ao_radius = check_ao(ao, ao_radius, self.aux is not None)
         ao_more = check_ao_filter(ao, ao_sets, ao_filter, ao_filter_cos, ao_filter_plane)
+        temporal = check_temporal(temporal, temporal_cos, temporal_plane, bool(ao or area or gi), getattr(setup, "lights", None),
+                                  reflect_lights, self.aux is not None)
+        if not (temporal and shade):
+            self._temporal_live = False  # the next temporal frame starts its means again
         if reflect_lights:
             lights = check_lights(setup.lights, reflect, self.aux is not None, True)
             return self._display_reflect_lights(setup, lights, shadows, shade, bounces, reflect_shadows,
@@ -915,9 +1038,12 @@ class Renderer(_Frame, _Band):
         if getattr(setup, "lights", None) is not None:
             lights = check_lights(setup.lights, reflect, self.aux is not None)
             return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more))
-        ao = self._ao_stage(ao, ao_radius, shade, ao_more)
-        if gi:
-            gi = self._gi_stage(gi, shade)
+        if temporal and shade:  # (the effects' stages are made behind _temporal_begin)
+            ao_asked, gi_asked, ao = ao, gi, None
+        else:
+            ao = self._ao_stage(ao, ao_radius, shade, ao_more)
+            if gi:
+                gi = self._gi_stage(gi, shade)
         if aa:
             aa = self._aa_stage(aa, shade)
         if reflect and shade:
@@ -927,6 +1053,14 @@ class Renderer(_Frame, _Band):
             return two_streams(setup, frame_cnt, shadows, reflect, bounces, reflect_shadows)
         ctx = self.ctx
         cam = make_camera(setup.camera, setup.fovy, self.aspect)
+        tp = area_t = None
+        if temporal and shade:
+            tp = self._temporal_begin(temporal, cam)
+            ao = self._temporal_ao(tp, ao_asked, ao_radius, ao_more) if ao_asked else None
+            gi = self._temporal_gi(tp, gi_asked, setup) if gi_asked else None
+            if area:
+                area_t = self._temporal_area(tp, area, area_sets, area_radius, area_filter, area_filter_cos,
+                                             area_filter_plane, setup)
         camera_pass(ctx, self, self, setup, cam)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         use_light_camera(ctx, lcam)
@@ -948,19 +1082,23 @@ class Renderer(_Frame, _Band):
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         if area:
             thru = see_through(self)
-            if area_sets > 1:
+            if tp:
+                area_pass(ctx, self, self.cam_pos, area_t[1], thru, (area,) + area_t[2])
+            elif area_sets > 1:
                 area_pass(ctx, self, self.cam_pos, self._area_sets_stage(area, area_sets, area_radius, setup), thru,
                           (area,) + AREA_SET_TILES[area_sets])
             else:
                 area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru)
         if ao:
-            ao_pass(ctx, self, self.cam_pos, *ao)
+            ao_pass(ctx, self, self.cam_pos, *ao[:3])
         if gi:
             gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area))
         if aa:
             aa_pass(ctx, self, cam.camcoords, aa, lcam.worldori[:3] if shadows and aa[5] else None)
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
-        if area and area_filter:
+        if area and tp:
+            area_shade_temporal(ctx, self, tp, area_t)
+        elif area and area_filter:
             self._ensure_area_filter_buffers()
             plane = default_filter_plane(self.bbmin, self.bbmax) if area_filter_plane is None else area_filter_plane
             ctx.filter_visibility(self.area_mask, area, self.ao_rays, self.ao_active, area_filter, area_filter_cos, plane,
@@ -968,12 +1106,126 @@ class Renderer(_Frame, _Band):
             ctx.shade_area_vis(self.image, self.area_vis, area)
         elif area:
             ctx.shade_area(self.image, self.area_mask, area)
-        if gi:
+        if gi and tp:
+            gi_shade_temporal(ctx, self, tp, gi)
+        elif gi:
             gi_shade(ctx, self, gi)
         if aa:
             ctx.aa_resolve(self.image, self.aa_sum, aa[0])
-        if ao:
+        if ao and tp:
+            ao_shade_temporal(ctx, self, tp, ao)
+        elif ao:
             ao_shade(ctx, self, *ao)
+
+    # -- temporal accumulation
+    def _temporal_begin(self, temporal, cam):
+        """Starts a temporal frame: the G-buffer of the frame before becomes prev_ao_rays / prev_ao_active (the buffers
+        change places: ao_rays keeps naming the frame that is being rendered), and every mean starts again when the frame
+        before was not a temporal one.  Returns the frame's record: the most frames of a mean, the surface tests' bounds,
+        the eye's block of the frame before (this frame's own where there is none: the histories are empty then) and the
+        bounds as part of the effects' keys."""
+        N, cos, plane = temporal
+        plane = default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane
+        self._ensure_temporal_gbuffers()
+        if not self._temporal_live:
+            self.temporal_reset()
+            self._temporal_prev_cam = None
+            self._temporal_live = True
+        self._temporal_serial += 1
+        self.ao_rays, self.prev_ao_rays = self.prev_ao_rays, self.ao_rays
+        self.ao_active, self.prev_ao_active = self.prev_ao_active, self.ao_active
+        now = np.array(cam.camcoords, np.float32)
+        prev, self._temporal_prev_cam = self._temporal_prev_cam, now
+        return {"max": N, "cos": cos, "plane": plane, "prev_cam": now if prev is None else prev, "key": (N, cos, plane)}
+
+    def _ensure_temporal_gbuffers(self):
+        """ao_rays / ao_active and their twins of the frame before, allocated on first use (the twins zeroed: nothing
+        reads them before a frame has written them, the empty histories stand in front)."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.ao_rays is None:
+            self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+        if self.prev_ao_rays is None:
+            self.prev_ao_rays = t.zeros(6 * N, dtype=t.float32, device=dev)
+            self.prev_ao_active = t.zeros(N, dtype=t.int32, device=dev)
+
+    def _temporal_words(self, name, words):
+        """The temporal call's output of an effect, [words W*H] uint32 words in an int32 tensor, allocated on first use."""
+        if getattr(self, name) is None:
+            setattr(self, name, self.torch.zeros(words * self.N, dtype=self.torch.int32, device=self.image.device))
+
+    def _temporal_alloc(self, words):
+        t = self.torch
+        return [t.zeros(words * self.N, dtype=t.float32, device=self.image.device) for _ in range(2)]
+
+    def _temporal_effect(self, name, key, words):
+        """The state of effect `name` for this frame: made on first use, cleared when its parameters `key` are not those
+        it was accumulated under or when it did not run in the temporal frame before."""
+        st = self._temporal.get(name)
+        if st is None:
+            st = self._temporal[name] = {"key": key, "hist": self._temporal_alloc(words), "turn": 0, "n": 0}
+        elif st["key"] != key or st["serial"] != self._temporal_serial - 1:
+            self._temporal_clear(st)
+            st["key"] = key
+        st["serial"] = self._temporal_serial
+        return st
+
+    def _temporal_table(self, key, sets, frame, table16):
+        """Frame `frame`'s device table of the 16-set table table16(): the 16 rotated tables (scenes.temporal_sets) are
+        uploaded once per key and kept."""
+        if key not in self._temporal_set_tables:
+            from .scenes import temporal_sets
+
+            whole = table16()
+            self._temporal_set_tables[key] = [self._upload_ao_sets(temporal_sets(whole, sets, f)) for f in range(16)]
+        return self._temporal_set_tables[key][frame % 16]
+
+    def _temporal_ao(self, tp, ao, ao_radius, sets):
+        """_ao_stage for a temporal frame: (directions, radius, (frame table, (set_w, set_h), gather), state) with the
+        walk over sets and the gather always there (a 1 x 1 tile with ao_sets = 1, radius 0 without ao_filter)."""
+        from .scenes import ao_direction_sets
+
+        ao_sets, ao_filter, cos, plane = sets
+        dirs = self._ensure_ao_buffers(ao)
+        self._ensure_ao_filter_buffers()
+        self._temporal_words("ao_tvis", 2)
+        cos = 0.9 if cos is None else cos
+        plane = default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane
+        st = self._temporal_effect("ao", (ao, ao_radius, ao_sets, ao_filter, cos, plane) + tp["key"], 2)
+        table = self._temporal_table(("ao", ao, ao_sets), ao_sets, st["n"], lambda: ao_direction_sets(ao, 16))
+        return (dirs, ao_radius, (table, AREA_SET_TILES[ao_sets], (ao_filter, cos, plane)), st)
+
+    def _temporal_gi(self, tp, gi, setup):
+        """_gi_stage for a temporal frame: its tuple with the frame's table, the gather always there, and the state behind
+        it.  The light the hits are shaded and shadowed under is part of the key."""
+        from .scenes import ao_direction_sets
+
+        S, radius, gain, shadows, sets, filt, cos, plane = gi
+        self._ensure_gi_buffers(True)
+        self._temporal_words("gi_tacc", 4)
+        cos = 0.9 if cos is None else cos
+        plane = default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane
+        light = tuple(map(float, setup.shading_light)) + tuple(map(float, setup.light_camera["eye"]))
+        st = self._temporal_effect("gi", (S, radius, gain, shadows, sets, filt, cos, plane, light) + tp["key"], 4)
+        table = self._temporal_table(("gi", S, sets), sets, st["n"], lambda: ao_direction_sets(S, 16))
+        return (S, AREA_SET_TILES[sets], table, radius, gain, (filt, cos, plane), shadows, st)
+
+    def _temporal_area(self, tp, area, area_sets, area_radius, area_filter, cos, plane, setup):
+        """(S, frame table, (set_w, set_h), gather, state) of an area light in a temporal frame: _area_sets_stage's disk,
+        16 sets of it.  The light is part of the key."""
+        from .scenes import area_sample_sets
+
+        self._ensure_area_buffers()
+        self._ensure_area_filter_buffers()
+        self._temporal_words("area_tvis", 2)
+        cos = 0.9 if cos is None else cos
+        plane = default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane
+        eye, look = tuple(map(float, setup.light_camera["eye"])), tuple(map(float, setup.light_camera["look"]))
+        st = self._temporal_effect("area", (area, area_sets, area_radius, area_filter, cos, plane, eye, look) + tp["key"], 2)
+        table = self._temporal_table(("area", area, area_sets, area_radius, eye, look), area_sets, st["n"],
+                                     lambda: area_sample_sets(area, 16, np.float64(eye), np.float64(look) - np.float64(eye),
+                                                              area_radius))
+        return (area, table, AREA_SET_TILES[area_sets], (area_filter, cos, plane), st)
 
     def _aa_stage(self, aa, shade):
         """(S, (set_w, set_h), table, cos, plane, shadows) for aa_edges and aa_pass from what check_aa returned, with the
@@ -1336,7 +1588,9 @@ class BandedRenderer(_Frame):
                 ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
                 area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None, gi=0, gi_radius=None,
                 gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
-                aa_cos=0.9, aa_plane=None, aa_shadows=True):
+                aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None):
+        check_temporal(temporal, temporal_cos, temporal_plane, True, getattr(setup, "lights", None), False,
+                       True)  # raises with temporal > 0: the effects it averages are not built here
         check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), 0, gi, False,
                  True)  # raises with aa > 0, as gi does
         check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,

@@ -515,3 +515,17 @@ def aa_offset_sets(S, sets):
     rank = AREA_SET_RANK[sets]
     step = 1.0 / (float(sets + 1) * float(int(S)))
     return np.stack([_aa_points(S, rank[k] * step, (rank[sets - 1 - k] * step) if k else 0.0) for k in range(sets)])
+
+
+def temporal_sets(table16, sets, frame):
+    """Frame `frame`'s table of a temporal sequence, from a table of 16 sets
+    (ao_direction_sets(S, 16), area_sample_sets(S, 16, ...), the indirect light's directions): entry k of the tile of
+    sets = 1, 4 or 16 pixels is set (k * (16 // sets) + frame) % 16.  Over 16 frames every entry goes through all 16 sets,
+    and in any one frame the entries of a tile hold different sets.  [sets, S, c] in table16's type; a copy."""
+    if sets not in AREA_SET_RANK:
+        raise ValueError("sets must be 1, 4 or 16, not %r" % (sets,))
+    table16 = np.asarray(table16)
+    if table16.shape[0] != 16:
+        raise ValueError("a table of 16 sets is expected, not %d" % table16.shape[0])
+    pick = [(k * (16 // sets) + int(frame)) % 16 for k in range(sets)]
+    return np.ascontiguousarray(table16[pick])
