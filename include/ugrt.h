@@ -174,6 +174,10 @@ const float *ugrt_scene_transmitlist(const ugrt_scene *s, int *mtl_count);
 /* (float)obj_material.refract_index of the mtllib (token "Ni", default 1), [mtl_count].  A scene loaded from a cache
  * reports 1 for every material: the cache format does not hold the list. */
 const float *ugrt_scene_iorlist(const ugrt_scene *s, int *mtl_count);
+/* (float)obj_material.glossy of the mtllib (token "sharpness", 0..1000, default 98), raw, [mtl_count]: 1000 is a mirror,
+ * and what a lobe's spread is made of is the caller's business (scenes.spread_from_sharpness).  A scene loaded from a
+ * cache reports 1000 for every material -- the cache format does not hold the list --, so its reflections stay mirrors. */
+const float *ugrt_scene_sharpnesslist(const ugrt_scene *s, int *mtl_count);
 /* Binary cache of a loaded scene (the strtok parser takes seconds on 1 M triangles).
  * Little-endian: "UGRTSCN1", counts, then the flat lists exactly as the accessors return them.
  * load_cache replaces the scene's contents; a truncated or foreign file gives UGRT_EIO. */
@@ -858,6 +862,53 @@ int ugrt_gi_filter(ugrt_ctx *ctx, const unsigned *d_sum, const float *d_orays, c
  * aligned or a null argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_gi_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_dirs, float gain,
 		  const int *d_intersect_id, const float *d_mat_list, int num_materials);
+
+/* ---- device: glossy reflections, a lobe of rays around the mirror direction ----
+ * A reflecting surface whose material is not perfectly sharp averages what a cone of directions around the mirror
+ * direction sees.  Per frame: ugrt_reflect_rays, ugrt_ao_rays, ugrt_glossy_gather, the shading call, ugrt_gi_filter
+ * (optional, over the glossy sums with the glossy active words), ugrt_glossy_apply.  The library sees spreads as data: the
+ * tangent of the lobe's half-angle per material.  All arithmetic is fp32 without contraction or unsigned 32-bit integer,
+ * in the stated order. */
+#define UGRT_MAX_GLOSSY_SAMPLES 32
+#define UGRT_MAX_GLOSSY_SPREAD 1.0f
+/* The lobe's closest-hit gather.  d_rays / d_active are ugrt_reflect_rays' {o, R} and active words; d_orays is
+ * ugrt_ao_rays' {o', n}, of which only n is read; d_intersect_id holds the primary hits' TRIANGLES (the call runs before
+ * the shading call).  For a pixel p of the band with d_active[p] != 0: m = d_mat_idx[d_intersect_id[p]] and
+ * a = d_spread[m] where that is > 0 (NaN, zeros and negative values count as 0, values above UGRT_MAX_GLOSSY_SPREAD as
+ * it; an id below 0 or an m outside 0..num_materials-1: a = 0).  For sample s < num_samples,
+ * (u, v) = d_points[2 * (k(p) * num_samples + s) ..], k(p) = (row % set_h) * set_w + col % set_w (d_points is DEVICE
+ * memory, [set_w * set_h][num_samples][2]), each clamped to [-1, 1], a NaN counting as 0.
+ * r = R * (1 / sqrt((R0*R0 + R1*R1) + R2*R2)); D[k] = ((a*u)*T[k] + (a*v)*B[k]) + 1.0f*r[k] with T, B of the hemisphere
+ * rays' basis rule over r (no special case for a = 0); c = (D0*n0 + D1*n1) + D2*n2, and where c < 0, D[k] becomes
+ * D[k] - (2.0f*c)*n[k]: a sample that would enter the surface is mirrored back over it (c >= 0 or a NaN leaves D alone).
+ * A D that is not finite is traced as ugrt_trace_dda traces such a ray.  The ray is {o, D}, o = d_rays[6p .. 6p + 2].
+ * From there on the call is ugrt_gi_gather: the closest hit below radius (which may be +inf), the colour 0 on a miss or a
+ * hit whose material is out of range, otherwise the clamped Lambert term under the context's camera block and
+ * ugrt_set_light_position's light, divided by 3.0f where ugrt_trace_dda_any(t_max = 1) flags ugrt_occlusion_rays' ray
+ * to shadow_light (host float[3]; NULL: no shadow phase), the bytes, their sums d_sum[4p + k] over s and
+ * d_sum[4p + 3] = 1.  Inactive pixels of the band get four zeros, pixels outside the band are not written.  d_sum has
+ * ugrt_gi_gather's layout, so ugrt_gi_filter gathers over it unchanged (called with d_active in the place of d_oactive:
+ * only pixels that carry a lobe enter a neighbour's mean).  One prepare launch over d_active; the point table and the
+ * words only the code between the walks needs are staged in LDS; groups are drawn from a ticket.  Options
+ * "any_rays_per_wave", "any_coop" and "dda_blocks" shape the launch and change no word.  Stages UGRT_ST_WORKLIST /
+ * UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of ugrt_trace_dda alone.  num_samples outside
+ * 1..UGRT_MAX_GLOSSY_SAMPLES, set_w or set_h outside 1..UGRT_MAX_AO_SET_TILE, radius <= 0 or NaN, eps NaN,
+ * num_materials < 1, a d_sum that is not 16-byte aligned, or a null argument other than shadow_light: UGRT_EINVAL (the
+ * message names the argument) and nothing is enqueued; without a built uniform grid the error of ugrt_trace_dda. */
+int ugrt_glossy_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+		       const float *d_vertlist, const int *d_trilist, const float *d_rays, const int *d_active,
+		       const float *d_orays, const int *d_intersect_id, const int *d_mat_idx, const float *d_spread,
+		       int num_samples, int set_w, int set_h, const float *d_points, float radius, const float *d_mat_list,
+		       int num_materials, const float *shadow_light, float eps, unsigned *d_sum);
+/* The lobe's mean onto the image, directly behind the shading call of the frame (d_intersect_id[p] holds the material index
+ * m by then; it is only read).  d_acc is ugrt_gi_filter's output or ugrt_glossy_gather's sums.  For a pixel of the band
+ * with den = d_acc[4p + 3] != 0, m in 0..num_materials-1 and k = d_reflect[m] > 0 (a k above 1 counts as 1), per
+ * component c: mean = (float)d_acc[4p + c] / (float)(num_samples * den), the unsigned product converted once, and the
+ * byte b becomes min(255, ugrt_floor2i(((1.0f - k) * (float)b + k * mean) + 0.5f)).  Every other pixel is left as it is.
+ * Stage UGRT_ST_SHADE.  num_samples outside 1..UGRT_MAX_GLOSSY_SAMPLES, a d_acc that is not 16-byte aligned or a null
+ * argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_glossy_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_samples,
+		      const int *d_intersect_id, const float *d_reflect, int num_materials);
 
 /* ---- device: adaptive anti-aliasing, sub-pixel eye rays on edge pixels ----
  * The frame takes one eye ray per pixel, through the pixel's corner.  ugrt_aa_edges finds the pixels that lie on an edge,

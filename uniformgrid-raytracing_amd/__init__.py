@@ -64,6 +64,8 @@ MAX_AO_SET_TILE = 4  # UGRT_MAX_AO_SET_TILE
 MAX_AO_SET_DIRS = 512  # UGRT_MAX_AO_SET_DIRS
 MAX_AA_SAMPLES = 32  # UGRT_MAX_AA_SAMPLES
 MAX_TEMPORAL_FRAMES = 64  # UGRT_MAX_TEMPORAL_FRAMES
+MAX_GLOSSY_SAMPLES = 32  # UGRT_MAX_GLOSSY_SAMPLES
+MAX_GLOSSY_SPREAD = 1.0  # UGRT_MAX_GLOSSY_SPREAD
 TEMPORAL_DEN = 256  # UGRT_TEMPORAL_DEN
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
@@ -123,6 +125,7 @@ PROTOTYPES = {
     "ugrt_scene_reflectlist": (_P, [_P, C.POINTER(C.c_int)]),
     "ugrt_scene_transmitlist": (_P, [_P, C.POINTER(C.c_int)]),
     "ugrt_scene_iorlist": (_P, [_P, C.POINTER(C.c_int)]),
+    "ugrt_scene_sharpnesslist": (_P, [_P, C.POINTER(C.c_int)]),
     "ugrt_scene_save_cache": (C.c_int, [_P, C.c_char_p]),
     "ugrt_scene_load_cache": (C.c_int, [_P, C.c_char_p]),
     "ugrt_scene_bounds": (C.c_int, [_P, _F3, _F3]),
@@ -195,6 +198,8 @@ PROTOTYPES = {
     "ugrt_gi_gather": (C.c_int, [_P] * 8 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_gi_filter": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P]),
     "ugrt_gi_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int]),
+    "ugrt_glossy_gather": (C.c_int, [_P] * 12 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _F3, C.c_float, _P]),
+    "ugrt_glossy_apply": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
     "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
     "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),

@@ -219,6 +219,7 @@ struct ugrt_scene {
 	std::vector<float> reflect;     // obj_material.reflect
 	std::vector<float> transmit;    // 1 - obj_material.trans (the dissolve d: 1 = opaque), clamped to [0, 1]
 	std::vector<float> ior;         // obj_material.refract_index
+	std::vector<float> sharpness;   // obj_material.glossy (the MTL token "sharpness", 0..1000, default 98), raw
 	int num_materials = 0;
 	float bbmin[3] = { 9999.9f, 9999.9f, 9999.9f };
 	float bbmax[3] = { -9999.9f, -9999.9f, -9999.9f };
@@ -323,6 +324,9 @@ extern "C" int ugrt_scene_load_model(ugrt_scene *s, const char *path)
 		s->transmit[i] = tr > 0.0f ? (tr < 1.0f ? tr : 1.0f) : 0.0f; // (a NaN counts as opaque)
 		s->ior[i] = (float)o.mtl[i].refract_index;
 	}
+	s->sharpness.resize(o.mtl.size());
+	for (size_t i = 0; i < o.mtl.size(); i++)
+		s->sharpness[i] = (float)o.mtl[i].glossy;
 	return UGRT_OK;
 }
 
@@ -424,6 +428,8 @@ extern "C" int ugrt_scene_load_cache(ugrt_scene *s, const char *path)
 	// the cache format knows no glass: a cached scene is opaque
 	t.transmit.assign(t.reflect.size(), 0.0f);
 	t.ior.assign(t.reflect.size(), 1.0f);
+	// nor a sharpness: a cached scene's reflections are mirrors
+	t.sharpness.assign(t.reflect.size(), 1000.0f);
 	*s = t;
 	return UGRT_OK;
 }
@@ -467,6 +473,14 @@ extern "C" const float *ugrt_scene_iorlist(const ugrt_scene *s, int *n)
 	if (n)
 		*n = (int)s->ior.size();
 	return s->ior.data();
+}
+extern "C" const float *ugrt_scene_sharpnesslist(const ugrt_scene *s, int *n)
+{
+	if (!s)
+		return nullptr;
+	if (n)
+		*n = (int)s->sharpness.size();
+	return s->sharpness.data();
 }
 extern "C" int ugrt_scene_bounds(const ugrt_scene *s, float bbmin[3], float bbmax[3])
 {

@@ -486,6 +486,26 @@ class Context:
         check(lib.ugrt_gi_apply(self._h, _ptr(img), _ptr(acc), int(num_dirs), gain, _ptr(ids), _ptr(mat_list),
                                 int(num_materials)))
 
+    # -- glossy reflections ----------------------------
+    def glossy_gather(self, value, span, offset, verts, faces, rays, active, orays, ids, mat_idx, spread, num_samples, set_w,
+                      set_h, points, radius, mat_list, num_materials, shadow_light, eps, sums):
+        """The lobe's closest-hit gather, before the shading call (ids holds triangle ids): an active pixel p of
+        reflect_rays' {o, R} sends num_samples rays from o around normalize(R), tilted by spread[material] times the
+        points of its set (points: the DEVICE table [set_w * set_h, num_samples, 2], scenes.glossy_point_sets) and
+        mirrored back over the surface where they would enter it (orays: ao_rays' {o', n}); each is walked, shaded,
+        shadowed and summed as gi_gather does it: sums[4p + k] for k < 3, sums[4p + 3] = 1."""
+        light = None if shadow_light is None else _points([shadow_light])[1]
+        check(lib.ugrt_glossy_gather(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces), _ptr(rays),
+                                     _ptr(active), _ptr(orays), _ptr(ids), _ptr(mat_idx), _ptr(spread), int(num_samples),
+                                     int(set_w), int(set_h), _ptr(points), radius, _ptr(mat_list), int(num_materials), light,
+                                     eps, _ptr(sums)))
+
+    def glossy_apply(self, img, acc, num_samples, ids, reflect, num_materials):
+        """Directly behind the shading call (ids holds material indices): each byte b of a pixel with den = acc[4p + 3]
+        != 0 and k = min(reflect[material], 1) > 0 becomes round((1 - k) * b + k * acc[4p + c] / (num_samples * den))."""
+        check(lib.ugrt_glossy_apply(self._h, _ptr(img), _ptr(acc), int(num_samples), _ptr(ids), _ptr(reflect),
+                                    int(num_materials)))
+
     # -- anti-aliasing (DESIGN.md section 6.11) --------------------------------
     def aa_edges(self, normal, t, dirs, ids, cam_pos, mat_idx, is_shadowed, normal_cos, plane_tol, edge):
         """Before the shading call (ids holds triangle ids): edge[p] = 1 where one of the up to eight neighbours of p

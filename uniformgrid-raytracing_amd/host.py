@@ -89,6 +89,13 @@ class Model:
         p = lib.ugrt_scene_iorlist(self._h, C.byref(n))
         return _view(p, n.value, np.float32)
 
+    @property
+    def h_sharpnesslist(self):
+        """sharpness of the MTL, raw (0..1000, default 98); all 1000 after load_cache."""
+        n = C.c_int()
+        p = lib.ugrt_scene_sharpnesslist(self._h, C.byref(n))
+        return _view(p, n.value, np.float32)
+
     def bounds(self):
         mn, mx = (C.c_float * 3)(), (C.c_float * 3)()
         check(lib.ugrt_scene_bounds(self._h, mn, mx))

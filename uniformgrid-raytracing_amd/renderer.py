@@ -35,6 +35,9 @@ their first hit, which is shaded and shadowed, and a pass that adds the mean to 
 eye rays through the uniform grid and take the mean of their colours.  With ``temporal=N`` the
 frames of a sequence give ``ao``, ``area`` and ``gi`` a different sample set each and blend every frame's share into a
 running mean over at most N frames, reprojected through the surface point when the camera moves.
+With ``glossy=S`` the one-stream single-light frame without ``reflect`` shows its reflecting materials as rough mirrors: S
+rays per primary hit in a lobe around the mirror direction, as wide as the material's spread, to their first hit, and a
+pass directly behind the shading call that blends the lobe's mean into the image.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -44,8 +47,8 @@ import contextlib
 
 import numpy as np
 
-from . import (GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS, MAX_LIGHTS,
-               MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
+from . import (GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS,
+               MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -323,6 +326,46 @@ def check_temporal(temporal, temporal_cos=0.9, temporal_plane=None, effects=Fals
     return int(temporal), float(np.float32(temporal_cos)), temporal_plane
 
 
+def check_glossy(glossy, glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
+                 glossy_shadows=True, reflect=False, refract=False, aa=0, temporal=0, lights=None, reflect_lights=False,
+                 two_streams=False):
+    """The keywords of the glossy reflections.  glossy: an integer 0..MAX_GLOSSY_SAMPLES (0: off,
+    and every other glossy_* keyword must be at its default); glossy_sets, glossy_filter, glossy_filter_cos and
+    glossy_filter_plane: check_ao_filter's rules; glossy_radius: None (+inf: the whole grid) or a number greater than 0;
+    glossy_shadows: a bool.  glossy > 0 needs the one-stream Renderer's single-light frame with reflect=False (ao, area
+    and gi compose): no reflect, refract, aa, temporal (the reprojection follows the primary hit, and a reflection moves
+    with the eye), setup.lights or reflect_lights.  ValueError before anything is enqueued.  Returns None (off) or
+    (glossy, radius, shadows, glossy_sets, glossy_filter, cos or None, plane or None)."""
+    if isinstance(glossy, (bool, np.bool_)) or not isinstance(glossy, (int, np.integer)) \
+            or not 0 <= glossy <= MAX_GLOSSY_SAMPLES:
+        raise ValueError("glossy must be an integer in 0..%d, not %r" % (MAX_GLOSSY_SAMPLES, glossy))
+    if glossy_radius is not None:
+        if isinstance(glossy_radius, (bool, np.bool_)) or not isinstance(glossy_radius, (int, float, np.integer, np.floating)) \
+                or not float(np.float32(glossy_radius)) > 0.0:
+            raise ValueError("glossy_radius must be None or a number greater than 0, not %r" % (glossy_radius,))
+    if not isinstance(glossy_shadows, (bool, np.bool_)):
+        raise ValueError("glossy_shadows must be True or False, not %r" % (glossy_shadows,))
+    sets = _check_sets_filter("glossy", "the lobe's rays and its gather", glossy, glossy_sets, glossy_filter, glossy_filter_cos,
+                              glossy_filter_plane)
+    if glossy == 0:
+        if glossy_radius is not None or not glossy_shadows:
+            raise ValueError("glossy_radius and glossy_shadows need glossy > 0: they shape the lobe's rays")
+        return None
+    if reflect or refract or reflect_lights:
+        raise ValueError("glossy needs reflect=False: lobes on the levels of the bounce chain are not built")
+    if aa:
+        raise ValueError("glossy needs aa=0: the sub-pixel samples send no lobe")
+    if temporal:
+        raise ValueError("glossy needs temporal=0: the reprojection follows the primary hit, and a reflection moves with the eye")
+    if lights is not None:
+        raise ValueError("glossy needs a single-light frame: the lobe's hits under setup.lights are not built")
+    if two_streams:
+        raise ValueError("glossy needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
+                         "side context")
+    radius = float("inf") if glossy_radius is None else float(np.float32(glossy_radius))
+    return (int(glossy), radius, bool(glossy_shadows)) + sets
+
+
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
 # BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
@@ -472,14 +515,15 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
                     f.occlusion_rays, f.occlusion_active, shadow_lights, f.occluded_lights[j])
 
 
-def ao_pass(c, f, cam_pos, dirs, radius, sets=None):
+def ao_pass(c, f, cam_pos, dirs, radius, sets=None, have_rays=False):
     """Ambient occlusion's rays and walk: {origin, normal} of every primary hit, then the any-hit
     walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  sets
     ((table, (set_w, set_h), gather)) with a table: the device table of a direction set per pixel
-    of the tile, and the walk is the pixel-major one over direction sets.  Runs behind the uniform grid's build and before
-    the shading call that rewrites the ids."""
+    of the tile, and the walk is the pixel-major one over direction sets.  have_rays: glossy_pass of this frame wrote the
+    rays already.  Runs behind the uniform grid's build and before the shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
-    c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    if not have_rays:
+        c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
     if sets is not None and sets[0] is not None:
         c.trace_dda_any_hemi_sets(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active, len(dirs), sets[1][0],
                                   sets[1][1], sets[0], radius, f.ao_mask)
@@ -518,6 +562,30 @@ def gi_shade(c, f, gi):
         c.gi_filter(f.gi_sum, f.ao_rays, f.ao_active, gi[5][0], gi[5][1], gi[5][2], f.gi_acc)
         acc = f.gi_acc
     c.gi_apply(f.image, acc, gi[0], gi[4], f.intersect_id, f.d_matlist, f.num_materials)
+
+
+def glossy_pass(c, f, cam_pos, gl, shadow_light):
+    """The lobe's gather, behind reflect_rays (f.rays / f.active: {o, R} of the pixels whose
+    material reflects) and the uniform grid's build: {origin, normal} of every primary hit (ao_rays, into the AO buffers;
+    the frame's other effects read them from there), then the closest-hit walk of the lobe's rays through c's uniform grid
+    into f.glossy_sum.  gl: Renderer._glossy_stage's (S, (set_w, set_h), table, radius, gather, shadows); shadow_light: the
+    point the hits are shadowed from, or None.  Runs before the shading call that rewrites the ids."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    c.glossy_gather(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.rays, f.active, f.ao_rays, f.intersect_id, f.d_matidx,
+                    f.d_spread, gl[0], gl[1][0], gl[1][1], gl[2], gl[3], f.d_matlist, f.num_materials, shadow_light,
+                    f.reflect_eps, f.glossy_sum)
+
+
+def glossy_shade(c, f, gl):
+    """The lobe's mean into the image, directly behind the frame's shading call (glossy_pass' gl): with a gather ((radius,
+    cos, plane)) gi_filter over f.glossy_sum into f.glossy_acc -- among the pixels that carry a lobe: f.active stands in
+    the place of the origins' flags --, then glossy_apply."""
+    acc = f.glossy_sum
+    if gl[4] is not None:
+        c.gi_filter(f.glossy_sum, f.ao_rays, f.active, gl[4][0], gl[4][1], gl[4][2], f.glossy_acc)
+        acc = f.glossy_acc
+    c.glossy_apply(f.image, acc, gl[0], f.intersect_id, f.d_reflect, f.num_materials)
 
 
 def temporal_blend(c, f, tp, st, call, sums, S, out):
@@ -573,15 +641,16 @@ def aa_pass(c, f, eye_camcoords, aa, shadow_light):
                 f.d_matidx, f.d_matlist, f.num_materials, shadow_light, f.reflect_eps, f.aa_sum)
 
 
-def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
+def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
     """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
     f.area_mask.  thru (a refract frame: (mat_idx, transmit, num_materials)): the walk that sees through glass.  sets
     ((num_samples, set_w, set_h)): `samples` is the device table of a set per pixel of the tile,
-    and the walk is the one over sample sets.  Runs behind the uniform grid's build and before the shading call that
-    rewrites the ids."""
+    and the walk is the one over sample sets.  have_rays: glossy_pass of this frame wrote the origins already.  Runs
+    behind the uniform grid's build and before the shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
-    c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
+    if not have_rays:
+        c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
     if sets is not None:
         any_hit(c, "trace_dda_any_area_sets", thru, uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.ao_rays, f.ao_active,
                 sets[0], sets[1], sets[2], samples, f.area_mask)
@@ -590,9 +659,10 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None):
                 samples, f.area_mask)
 
 
-def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False):
+def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
-    depth shading with the occluded levels darkened, at every depth), then add_shadows."""
+    depth shading with the occluded levels darkened, at every depth), then add_shadows.  glossy (glossy_pass' gl): the
+    lobe's blend directly behind the shading call, where the mirror frame has its own."""
     if reflect and reflect_shadows:
         c.shade_reflect_depth_occluded(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
                                        level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
@@ -610,6 +680,8 @@ def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_sha
     else:
         c.shade_spotlight(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
                           f.num_materials)
+    if glossy is not None:
+        glossy_shade(c, f, glossy)
     if shadows:
         c.shade_add_shadows(f.image, f.is_shadowed)
 
@@ -702,6 +774,10 @@ class _Frame:
         # offset tables by (aa, aa_sets)
         self.aa_edge = self.aa_sum = None
         self._aa_set_tables = {}
+        # glossy: the byte sums of the lobe's samples and the gather's sums, four words per pixel (_ensure_glossy_buffers;
+        # the rays are level 1's, the normals ao_rays'); the uploaded point tables by (glossy, glossy_sets) (_glossy_stage)
+        self.glossy_sum = self.glossy_acc = None
+        self._glossy_tables = {}
         # temporal: the previous frame's {o, n} and active flags (they change places with ao_rays / ao_active at the start
         # of every temporal frame), the temporal calls' outputs, the effects' states by name -- two histories, which of
         # them is read next, frames since the reset, the parameters they were accumulated under --, the 16 rotated tables
@@ -841,8 +917,10 @@ class _Band:
 
 class Renderer(_Frame, _Band):
     def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, transmit=None, ior=None, reflect_eps=1e-3,
-                 overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False):
-        """transmit, ior: per material, how much of its colour comes from behind it (0: opaque, the default) and its index
+                 overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False, spread=None):
+        """spread: per material, the tangent of the half-angle of its reflection lobe (scenes.spread_from_sharpness; None:
+        zeros, mirrors), for display(..., glossy=S).
+        transmit, ior: per material, how much of its colour comes from behind it (0: opaque, the default) and its index
         of refraction (default 1), for display(..., refract=True).
         overlap=True: the light grid and the uniform grid (which do not depend on the camera pass) are built
         by a second context on a second HIP stream while the main stream builds the perspective grid and
@@ -865,6 +943,10 @@ class Renderer(_Frame, _Band):
         _Frame.__init__(self, ctx, verts, faces, matidx, mat_list, reflect, reflect_eps, transmit, ior)
         _Band.__init__(self, ctx)
         self.orig = None
+        spr = np.zeros(self.num_materials, np.float32) if spread is None else np.asarray(spread, np.float32).reshape(-1)
+        if len(spr) != self.num_materials:
+            raise ValueError("spread must hold one value per material (%d), not %d" % (self.num_materials, len(spr)))
+        self.d_spread = ctx.upload(spr)
 
     def _make_side_context(self, ctx, aux_stream, helper_thread):
         from .device import Context
@@ -959,7 +1041,8 @@ class Renderer(_Frame, _Band):
                 area_filter=0, area_filter_cos=0.9, area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9,
                 ao_filter_plane=None, gi=0, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0,
                 gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True,
-                temporal=0, temporal_cos=0.9, temporal_plane=None):
+                temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0, glossy_sets=1, glossy_filter=0,
+                glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
@@ -1013,7 +1096,20 @@ class Renderer(_Frame, _Band):
         pixel's surface point lay under the previous frame's camera and dropped where the previous frame's normal
         (temporal_cos) or plane (temporal_plane; None: 1 % of the scene's largest extent) differ, and the effect is shaded
         from the mean (ao_tvis, area_tvis, gi_tacc; temporal_history).  A camera change does not reset the mean;
-        temporal_reset lists what does."""
+        temporal_reset lists what does.
+        glossy (one-stream renderer, single-light frames with reflect=False; ao, area and gi compose; no aa, no temporal;
+        0: off): rough mirrors -- every primary hit on a material with reflect > 0 sends glossy = 1..32 rays from
+        reflect_rays' origin in a lobe around the mirror direction, tilted by the material's spread (Renderer(spread=))
+        times the points of scenes.glossy_point_sets(glossy, glossy_sets) (uploaded once per (glossy, glossy_sets)) and
+        mirrored back over the surface where they would enter it, to their first hit within glossy_radius (None: the whole
+        grid); the hits are shaded under the light and, with glossy_shadows, shadowed from the light camera's eye;
+        glossy_sum holds the bytes' sums, glossy_filter (0: off) gathers them over the lobe-carrying pixels of the same
+        surface with glossy_filter_cos and glossy_filter_plane into glossy_acc, and the mean is blended into the image
+        with the material's reflect directly behind the shading call, before the shadows darken it (DESIGN.md section
+        6.13)."""
+        glossy = check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius,
+                              glossy_shadows, reflect, refract, aa, temporal, getattr(setup, "lights", None), reflect_lights,
+                              self.aux is not None)
         aa = check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), area, gi,
                       reflect_lights, self.aux is not None)
         gi = check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
@@ -1046,6 +1142,8 @@ class Renderer(_Frame, _Band):
                 gi = self._gi_stage(gi, shade)
         if aa:
             aa = self._aa_stage(aa, shade)
+        if glossy:
+            glossy = self._glossy_stage(glossy, shade)
         if reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
@@ -1078,24 +1176,32 @@ class Renderer(_Frame, _Band):
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
+        elif glossy:
+            # (reflect_rays although reflect=False: the lobe's origins and mirror directions are level 1's rays)
+            ctx.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect, self.num_materials,
+                             self.d_verts, self.d_faces, self.reflect_eps, self.rays, self.active)
+            build_grid(ctx, self, GRID_UNIFORM, self.shards)
+            glossy_pass(ctx, self, self.cam_pos, glossy, lcam.worldori[:3] if glossy[5] else None)
         elif ao or area or gi or aa:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
+        have_rays = bool(glossy)  # (glossy_pass wrote ao_rays / ao_active)
         if area:
             thru = see_through(self)
             if tp:
                 area_pass(ctx, self, self.cam_pos, area_t[1], thru, (area,) + area_t[2])
             elif area_sets > 1:
                 area_pass(ctx, self, self.cam_pos, self._area_sets_stage(area, area_sets, area_radius, setup), thru,
-                          (area,) + AREA_SET_TILES[area_sets])
+                          (area,) + AREA_SET_TILES[area_sets], have_rays=have_rays)
             else:
-                area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru)
+                area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru, have_rays=have_rays)
         if ao:
-            ao_pass(ctx, self, self.cam_pos, *ao[:3])
+            ao_pass(ctx, self, self.cam_pos, *ao[:3], have_rays=have_rays)
         if gi:
-            gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area))
+            gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area or glossy))
         if aa:
             aa_pass(ctx, self, cam.camcoords, aa, lcam.worldori[:3] if shadows and aa[5] else None)
-        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows)
+        shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows,
+                    glossy or None)
         if area and tp:
             area_shade_temporal(ctx, self, tp, area_t)
         elif area and area_filter:
@@ -1267,6 +1373,40 @@ class Renderer(_Frame, _Band):
         if filt:
             gather = (filt, cos, default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane)
         return (S, AREA_SET_TILES[sets], tables[(S, sets)], radius, gain, gather, shadows)
+
+    def _glossy_stage(self, glossy, shade):
+        """(S, (set_w, set_h), table, radius, gather, shadows) for glossy_pass and glossy_shade from what check_glossy
+        returned, with the buffers in place; None: nothing is shaded.  table: scenes.glossy_point_sets(S, glossy_sets) on
+        the device, uploaded once per (S, glossy_sets) and kept; gather: (radius, cos, plane), or None without one."""
+        if not shade:
+            return None
+        S, radius, shadows, sets, filt, cos, plane = glossy
+        self._ensure_glossy_buffers(bool(filt))
+        tables = self._glossy_tables
+        if (S, sets) not in tables:
+            from .scenes import glossy_point_sets
+
+            tables[(S, sets)] = self._upload_glossy_points(glossy_point_sets(S, sets))
+        gather = None
+        if filt:
+            gather = (filt, cos, default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane)
+        return (S, AREA_SET_TILES[sets], tables[(S, sets)], radius, gather, shadows)
+
+    def _upload_glossy_points(self, table):
+        return self.ctx.upload(table.reshape(-1))
+
+    def _ensure_glossy_buffers(self, gather):
+        """glossy_sum [4 W*H] and, with a gather, glossy_acc [4 W*H] (uint32 words in int32 tensors), level 1's rays and
+        the normals' buffers ao_rays / ao_active, allocated on first use."""
+        t, N, dev = self.torch, self.N, self.image.device
+        self._ensure_reflect_buffers(1, False)
+        if self.ao_rays is None:
+            self.ao_rays = t.empty(6 * N, dtype=t.float32, device=dev)
+            self.ao_active = t.empty(N, dtype=t.int32, device=dev)
+        if self.glossy_sum is None:
+            self.glossy_sum = t.zeros(4 * N, dtype=t.int32, device=dev)
+        if gather and self.glossy_acc is None:
+            self.glossy_acc = t.zeros(4 * N, dtype=t.int32, device=dev)
 
     def _ensure_gi_buffers(self, gather):
         """gi_sum [4 W*H] and, with a gather, gi_acc [4 W*H] (uint32 words in int32 tensors), and the origins' buffers
@@ -1588,7 +1728,11 @@ class BandedRenderer(_Frame):
                 ao_radius=None, refract=False, area=0, area_radius=None, area_sets=1, area_filter=0, area_filter_cos=0.9,
                 area_filter_plane=None, ao_sets=1, ao_filter=0, ao_filter_cos=0.9, ao_filter_plane=None, gi=0, gi_radius=None,
                 gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
-                aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None):
+                aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0,
+                glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
+                glossy_shadows=True):
+        check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius, glossy_shadows,
+                     reflect, refract, aa, temporal, getattr(setup, "lights", None), False, True)  # raises with glossy > 0
         check_temporal(temporal, temporal_cos, temporal_plane, True, getattr(setup, "lights", None), False,
                        True)  # raises with temporal > 0: the effects it averages are not built here
         check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), 0, gi, False,

@@ -19,6 +19,9 @@ parse the same text, so the float32 vertex arrays are identical.
   glass()    -- a small room with a glass icosphere, a glass slab in front of
                 two boxes and a mirror panel: rays that go through solids
                 (Renderer.display(..., reflect=True, refract=True))
+  glossy()   -- a room whose reflecting floor is split into three strips of
+                sharpness 1000, 700 and 300 under rows of thin coloured posts
+                and a column: rough mirrors (Renderer.display(..., glossy=S))
 """
 import os
 
@@ -175,14 +178,18 @@ CORNELL_QUADS = [
 ]
 
 
-def write_scene(outdir, name, verts, faces, matidx, materials, glass=None):
+def write_scene(outdir, name, verts, faces, matidx, materials, glass=None, sharpness=None):
     """Write <name>.obj, <name>.mtl, <name>.mat; returns their paths.  glass: {material index: (d, Ni)} -- the MTL
-    carries these materials' dissolve and index of refraction, every other material is written as "d 1" without Ni."""
+    carries these materials' dissolve and index of refraction, every other material is written as "d 1" without Ni.
+    sharpness: {material index: value} -- the MTL carries these materials' "sharpness" line behind the dissolve, every
+    other material has none (the loader's default is 98)."""
     os.makedirs(outdir, exist_ok=True)
     obj, mtl, mat = (os.path.join(outdir, name + e) for e in (".obj", ".mtl", ".mat"))
     with open(mtl, "w") as fp:
         for k, (nm, ka, kd, refl) in enumerate(materials):
             d_ni = "d 1\n" if not glass or k not in glass else "d %.6f\nNi %.6f\n" % tuple(glass[k])
+            if sharpness and k in sharpness:
+                d_ni += "sharpness %.6f\n" % sharpness[k]
             fp.write("newmtl %s\nKa %.6f %.6f %.6f\nKd %.6f %.6f %.6f\nKs 1.000000 1.000000 1.000000\nNs 0\n"
                      "%sr %.6f\nillum 2\n\n" % ((nm,) + tuple(ka) + tuple(kd) + (d_ni, refl)))
     with open(mat, "w") as fp:
@@ -208,7 +215,7 @@ def _finish(outdir, name, mesh, materials, extra):
     info.update(extra)
     if outdir is not None:
         info["obj"], info["mtl"], info["mat"] = write_scene(outdir, name, verts, faces, matidx, materials,
-                                                            extra.get("glass"))
+                                                            extra.get("glass"), extra.get("sharpness_of"))
     info["verts"] = verts.astype(np.float32)  # generation values; the loaders parse the 6-decimal text
     info["faces"] = faces
     info["matidx"] = matidx
@@ -410,6 +417,60 @@ def glass(outdir=None, scale=1.0):
     return info
 
 
+MATERIALS_GLOSSY = [
+    # name, Ka, Kd, reflect
+    ("y0_floor_sharp", (0.2, 0.2, 0.2), (0.45, 0.45, 0.50), 0.6),
+    ("y1_floor_satin", (0.2, 0.2, 0.2), (0.45, 0.45, 0.50), 0.6),
+    ("y2_floor_rough", (0.2, 0.2, 0.2), (0.45, 0.45, 0.50), 0.6),
+    ("y3_matte_wall", (0.2, 0.2, 0.2), (0.80, 0.78, 0.70), 0.0),
+    ("y4_red", (0.2, 0.2, 0.2), (0.85, 0.15, 0.12), 0.0),
+    ("y5_blue", (0.2, 0.2, 0.2), (0.12, 0.25, 0.85), 0.0),
+    ("y6_yellow", (0.2, 0.2, 0.2), (0.90, 0.80, 0.15), 0.0),
+    ("y7_column", (0.2, 0.2, 0.2), (0.70, 0.66, 0.60), 0.0),
+]
+# material index -> the MTL's sharpness (0..1000; 1000 is a mirror): the three strips of the floor
+GLOSSY_SHARPNESS_OF = {0: 1000.0, 1: 700.0, 2: 300.0}
+GLOSSY_STRIPS = ((0.0, 2.0), (2.0, 4.0), (4.0, 6.0))  # the strips' y ranges, in the order of the materials
+
+
+def spread_from_sharpness(sh):
+    """The spread of a material's reflection lobe from the MTL's sharpness:
+    0.5 * (1 - clip(sh, 0, 1000) / 1000) ** 2, computed in float64 and returned as float32 -- sharpness 1000 gives 0, a
+    mirror, sharpness 0 gives 0.5, the tangent of the lobe's half-angle.  The library only ever sees spreads as data."""
+    sh = np.clip(np.asarray(sh, dtype=np.float64), 0.0, 1000.0)
+    return (0.5 * (1.0 - sh / 1000.0) ** 2).astype(np.float32)
+
+
+def glossy(outdir=None, scale=1.0):
+    """Room [0,12]x[0,6]x[0,6] with a floor and one matte wall (x = 12) only: rays that climb or leave sideways leave the
+    grid.  The floor is three strips along x, y in GLOSSY_STRIPS, of one Kd and r = 0.6 with sharpness 1000, 700 and 300.
+    On every strip, in the same places, stands a row of six thin posts of alternating colours, and on the middle strip
+    behind its row a column: the posts are narrower than the rough strip's lobe and wider than a pixel, so each strip
+    shows them less crisp than the one before.  The camera looks along x down onto the floor in front of the posts.
+    ~5 000 triangles at scale 1."""
+    mesh = Mesh()
+    s = max(0.05, scale) ** 0.5
+    n = max(2, int(24 * s))
+    for m, (y0, y1) in enumerate(GLOSSY_STRIPS):
+        mesh.add(*grid_quad((0, y0, 0), (12, 0, 0), (0, y1 - y0, 0), n, max(1, n // 6)), m)
+    mesh.add(*grid_quad((12, 0, 0), (0, 6, 0), (0, 0, 6), n, n), 3)
+    nb = max(1, int(4 * s))
+    for y0, _ in GLOSSY_STRIPS:
+        for i in range(6):
+            ya = y0 + 0.2 + 0.3 * i
+            add_box(mesh, (8.0, ya, 0.0), (8.3, ya + 0.14, 2.6), nb, 4 + i % 3, faces="xXyYZ")
+    add_cylinder(mesh, 10.0, 3.0, 0.0, 4.0, 0.35, max(6, int(24 * s)), max(2, int(8 * s)), 7)
+    cams = {"ref": dict(eye=(0.3, 3.0, 2.5), look=(7.0, 3.0, 0.5), up=(0, 0, 1), near=0.1, far=100.0)}
+    light_cam = dict(eye=(5.0, 3.0, 9.0), look=(5.0, 3.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
+    info = _finish(outdir, "glossy%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_GLOSSY,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(5.0, 3.0, 5.0),
+                        sharpness_of=GLOSSY_SHARPNESS_OF))
+    # what the loader makes of the MTL: the written values, and its default 98 where there is no line
+    info["sharpness"] = np.array([GLOSSY_SHARPNESS_OF.get(k, 98.0) for k in range(len(MATERIALS_GLOSSY))], dtype=np.float32)
+    info["spread"] = spread_from_sharpness(info["sharpness"])
+    return info
+
+
 def ao_directions(S):
     """The S local directions of the ambient-occlusion hemisphere: a deterministic
     cosine-weighted spiral, r = sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), direction
@@ -440,6 +501,18 @@ def ao_direction_sets(S, sets):
     if sets not in AREA_SET_RANK:
         raise ValueError("sets must be 1, 4 or 16, not %r" % (sets,))
     return np.stack([_spiral_directions(S, 2.0 * np.pi * rank / float(sets)) for rank in AREA_SET_RANK[sets]])
+
+
+def glossy_points(S):
+    """The S points of a reflection lobe in the unit disk: the (x, y) of ao_directions, float32
+    [S, 2].  Times a material's spread they tilt the mirror direction."""
+    return np.ascontiguousarray(ao_directions(S)[:, :2])
+
+
+def glossy_point_sets(S, sets):
+    """The interleaved point sets of the reflection lobes: the (x, y) of ao_direction_sets(S, sets) -- the same spiral, the
+    same AREA_SET_RANK turns --, float32 [sets, S, 2]; set 0 is glossy_points bit for bit."""
+    return np.ascontiguousarray(ao_direction_sets(S, sets)[:, :, :2])
 
 
 def _disk_points(S, centre, axis, radius, turn):
