@@ -333,7 +333,7 @@ def test_an_area_frame_has_no_light_space_shadow_stage_and_area_0_is_the_frame_a
             == [c[:1] + tuple(x for x in c[1:] if isinstance(x, (str, int))) for c in b.ctx.calls]
     # area > 0
     for kw, want in ((dict(), CAMERA_PASS + ["grid_build_uniform", "ao_rays", "trace_dda_any_area", "shade_simple", "shade_area"]),
-                     (dict(ao=4, ao_radius=1.0), CAMERA_PASS + ["grid_build_uniform", "ao_rays", "trace_dda_any_area", "ao_rays",
+                     (dict(ao=4, ao_radius=1.0), CAMERA_PASS + ["grid_build_uniform", "ao_rays", "trace_dda_any_area",
                                                               "trace_dda_any_hemi", "shade_simple", "shade_area", "shade_ao"]),
                      (reflect, CAMERA_PASS + ["reflect_rays", "grid_build_uniform"] + LEVELS
                       + ["ao_rays", "trace_dda_any_area", "shade_reflect_depth_occluded", "shade_area"]),

@@ -404,7 +404,7 @@ def test_a_temporal_frame_enqueues_gather_blend_shade_per_effect_and_temporal_0_
         assert _names(a) == _names(b) and not [n for n in _names(b) if n.startswith("temporal")] and b.cleared == []
     r = _fake(ugrt)
     r.display(setup, temporal=8, temporal_cos=0.8, temporal_plane=0.02, **every)
-    want = CAMERA_PASS + ["grid_build_uniform", "ao_rays", "trace_dda_any_area_sets", "ao_rays", "trace_dda_any_hemi_sets", "gi_gather",
+    want = CAMERA_PASS + ["grid_build_uniform", "ao_rays", "trace_dda_any_area_sets", "trace_dda_any_hemi_sets", "gi_gather",
                           "shade_simple", "filter_visibility", "temporal_visibility", "shade_area_vis", "gi_filter", "temporal_gi",
                           "gi_apply", "filter_visibility", "temporal_visibility", "shade_ao_vis"]
     assert _names(r) == want, _names(r)

@@ -519,8 +519,8 @@ def ao_pass(c, f, cam_pos, dirs, radius, sets=None, have_rays=False):
     """Ambient occlusion's rays and walk: {origin, normal} of every primary hit, then the any-hit
     walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  sets
     ((table, (set_w, set_h), gather)) with a table: the device table of a direction set per pixel
-    of the tile, and the walk is the pixel-major one over direction sets.  have_rays: glossy_pass of this frame wrote the
-    rays already.  Runs behind the uniform grid's build and before the shading call that rewrites the ids."""
+    of the tile, and the walk is the pixel-major one over direction sets.  have_rays: glossy_pass or area_pass of this frame
+    wrote the rays already.  Runs behind the uniform grid's build and before the shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     if not have_rays:
         c.ao_rays(cam_pos, f.t, f.dir, f.intersect_id, f.d_verts, f.d_faces, f.reflect_eps, f.ao_rays, f.ao_active)
@@ -543,8 +543,8 @@ def ao_shade(c, f, dirs, radius, sets=None):
 
 def gi_pass(c, f, cam_pos, gi, shadow_light, have_rays):
     """The indirect light's gather: {origin, normal} of every primary hit (ao_rays, into the AO
-    buffers, unless area_pass or ao_pass of this frame wrote them: have_rays), then the closest-hit hemisphere walk through
-    c's uniform grid into f.gi_sum.  gi: Renderer._gi_stage's (S, (set_w, set_h), table, radius, gain, gather, shadows);
+    buffers, unless glossy_pass, area_pass or ao_pass of this frame wrote them: have_rays), then the closest-hit hemisphere
+    walk through c's uniform grid into f.gi_sum.  gi: Renderer._gi_stage's (S, (set_w, set_h), table, radius, gain, gather, shadows);
     shadow_light: the point the hits are shadowed from, or None.  Runs behind the uniform grid's build and before the
     shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
@@ -646,7 +646,8 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
     f.area_mask.  thru (a refract frame: (mat_idx, transmit, num_materials)): the walk that sees through glass.  sets
     ((num_samples, set_w, set_h)): `samples` is the device table of a set per pixel of the tile,
-    and the walk is the one over sample sets.  have_rays: glossy_pass of this frame wrote the origins already.  Runs
+    and the walk is the one over sample sets.  have_rays: glossy_pass of this frame wrote the origins already (area_pass is
+    the first of the frame's other passes: ao_pass and gi_pass read what it wrote).  Runs
     behind the uniform grid's build and before the shading call that rewrites the ids."""
     uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
     if not have_rays:
@@ -1045,8 +1046,8 @@ class Renderer(_Frame, _Band):
                 glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
-        1's views.  reflect_shadows: the hits of every reflection level are shadowed (from the light camera's eye, the
-        point the primary shadow pass is cast from); occluded_levels holds the levels' flags.
+        1's views.  reflect_shadows (needs reflect=True): the hits of every reflection level are shadowed (from the light
+        camera's eye, the point the primary shadow pass is cast from); occluded_levels holds the levels' flags.
         setup.lights (one-stream renderer, reflect=False): the shadow stage once per light into shadowed_lights, then one
         Lambertian shading pass over all of them, whatever frame_cnt says.
         reflect_lights (one-stream renderer; needs reflect=True and setup.lights): the reflections of depth `bounces` under
@@ -1106,7 +1107,14 @@ class Renderer(_Frame, _Band):
         glossy_sum holds the bytes' sums, glossy_filter (0: off) gathers them over the lobe-carrying pixels of the same
         surface with glossy_filter_cos and glossy_filter_plane into glossy_acc, and the mean is blended into the image
         with the material's reflect directly behind the shading call, before the shadows darken it (DESIGN.md section
-        6.13)."""
+        6.13).
+        The keywords that shape an effect need the effect: gi_sets and gi_filter (need gi > 0, like every other gi_*
+        keyword), aa_sets (needs aa > 0, like every other aa_* keyword), glossy_sets and glossy_filter (need glossy > 0, like
+        every other glossy_* keyword), temporal_cos and temporal_plane (need temporal > 0).
+        The passes over the image's bytes run in one order, whatever is on (DESIGN.md section 6.14): the shading call;
+        glossy_apply; shade_add_shadows, or with area shade_area / shade_area_vis in its place; gi_apply; aa_resolve;
+        shade_ao / shade_ao_vis.  The primary hits' {origin, normal} (ao_rays / ao_active) are written once per frame, by
+        the first of glossy, area, ao and gi that is on, and read by the others."""
         glossy = check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius,
                               glossy_shadows, reflect, refract, aa, temporal, getattr(setup, "lights", None), reflect_lights,
                               self.aux is not None)
@@ -1195,7 +1203,7 @@ class Renderer(_Frame, _Band):
             else:
                 area_pass(ctx, self, self.cam_pos, self._area_stage(area, area_radius, setup), thru, have_rays=have_rays)
         if ao:
-            ao_pass(ctx, self, self.cam_pos, *ao[:3], have_rays=have_rays)
+            ao_pass(ctx, self, self.cam_pos, *ao[:3], have_rays=have_rays or bool(area))  # (area_pass wrote them as well)
         if gi:
             gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area or glossy))
         if aa:
