@@ -258,6 +258,7 @@ int ugrt_ctx_set_option(ugrt_ctx *ctx, const char *key, int value);
  * context has been synchronised);
  * "uniform_builds_reused" ugrt_grid_build_uniform calls so far that kept the grid the context held instead of building;
  * "light_builds_reused" the same for ugrt_grid_build_spherical;
+ * "smooth_adjacency_builds" / "smooth_normal_builds" ugrt_smooth_adjacency / ugrt_smooth_corner_normals calls so far that built;
  * "recip_mismatches" runs every float bit pattern through the tracers' short reciprocal on the device and
  * returns the number of operands whose result differs from 1.0f / x (0), "f2i_mismatches" does the same for the device
  * forms of ugrt_f2i / ugrt_f2u / ugrt_floor2i against the portable ones of ugrt_fmath.h (0), "lane_reduce_mismatches"
@@ -909,6 +910,50 @@ int ugrt_glossy_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsign
  * argument: UGRT_EINVAL and nothing is enqueued. */
 int ugrt_glossy_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_samples,
 		      const int *d_intersect_id, const float *d_reflect, int num_materials);
+
+/* ---- device: smooth shading, crease-aware vertex normals interpolated per pixel ----
+ * No reference counterpart: the reference shades every pixel with its triangle's normal.  All arithmetic is fp32, every
+ * + - * / sqrt one IEEE operation, CROSS / DOT / NORMALIZE in the reference's operand order; every output is a function of
+ * the inputs alone, bit for bit (no float atomics: each sum is formed by one thread in list order).
+ *
+ * ugrt_smooth_adjacency (topology; again when the face list changes).  Corner c = 3f + k of the face list belongs to
+ * vertex v = d_facelist[c]; its key is d_vertex_key ? d_vertex_key[v] : v (d_vertex_key: one int per vertex, or NULL;
+ * scenes.weld makes one).  Indices and keys lie in 0..num_vertices-1, as the grid builds require of the indices.  The
+ * context keeps the corner indices stably sorted by key -- the corners of a key ascend -- and start[num_vertices + 1]:
+ * the corners of key K stand at positions start[K] .. start[K + 1] - 1.  The context's own radix sort on
+ * ceil(log2 num_vertices) key bits and one search per key; the call does not wait for the device.  num_faces == 0 is legal
+ * (an empty list).  Stage UGRT_ST_BUILD_SORT.  A null d_facelist with faces, faces without a vertex, a negative count or
+ * more than 2^30 corners: UGRT_EINVAL and nothing is enqueued.  ugrt_ctx_get_state "smooth_adjacency_builds" counts the
+ * calls that built.
+ * ugrt_smooth_get_adjacency (tests): the two arrays as device pointers, [3 num_faces] and [num_vertices + 1]; they stand
+ * until the next ugrt_smooth_adjacency.  UGRT_EINVAL before the first one.
+ *
+ * ugrt_smooth_corner_normals (geometry; again when vertices move).  Per face g: A_g = CROSS(v1 - v0, v2 - v0), the
+ * area weight, and N_g = NORMALIZE(A_g).  Per corner (f, k) with key K: S, from +0 per component, plus A_g for the
+ * faces g = corner / 3 of K's list in list order (a face that stands twice in the list is added twice) for which
+ * g == f or (N_f[0] * N_g[0] + N_f[1] * N_g[1]) + N_f[2] * N_g[2] >= crease_cos (a NaN rejects); the corner's normal
+ * d_corner_normals[3c ..] is NORMALIZE(S), or N_f as it is where a component of that is not finite.  crease_cos <= -1:
+ * every face of the list counts; crease_cos > 1: the corner's own face only.  One thread per corner: a vertex shared by
+ * k faces costs k * k additions.  d_corner_normals: [9 num_faces] floats.  Stage UGRT_ST_BUILD_FILL.  UGRT_EINVAL and
+ * nothing enqueued: crease_cos NaN, a null argument with faces, no adjacency, or one built for another num_faces.
+ * ugrt_ctx_get_state "smooth_normal_builds" counts the calls that built.
+ *
+ * ugrt_smooth_normals (per pixel of the context's band, before the shading call: d_intersect_id holds triangle ids).
+ * A pixel with id < 0 or !(t > 0) copies d_normal_in.  Otherwise, with tvec = d_cam_position - v0, e1 = v1 - v0,
+ * e2 = v2 - v0 of triangle id and d the pixel's stored direction: pvec = CROSS(d, e2), det = DOT(e1, pvec) (inside
+ * (-1e-21, 1e-21): failed), inv = 1 / det, u = DOT(tvec, pvec) * inv, v = DOT(d, CROSS(tvec, e1)) * inv -- the
+ * intersection test's own, not clamped --, w = (1 - u) - v, n = NORMALIZE((w * n0 + u * n1) + v * n2) per component from
+ * the triangle's three corner normals, ng = NORMALIZE(CROSS(e1, e2)).  The pixel gets ng where the determinant failed,
+ * where n has a component that is not finite or where !(DOT(n, ng) > 0), else n; with fold != 0 each component c becomes
+ * c < 0 ? c * -1 : c, as the primary tracer stores its normals.  d_normal_out == d_normal_in is allowed; pixels outside
+ * the band are not written.  Stage UGRT_ST_SHADE.  A null argument: UGRT_EINVAL and nothing is enqueued. */
+int ugrt_smooth_adjacency(ugrt_ctx *ctx, const int *d_facelist, int num_faces, int num_vertices, const int *d_vertex_key);
+int ugrt_smooth_get_adjacency(ugrt_ctx *ctx, const unsigned **d_corners, const unsigned **d_start);
+int ugrt_smooth_corner_normals(ugrt_ctx *ctx, const int *d_facelist, const float *d_vertlist, int num_faces,
+			       float crease_cos, float *d_corner_normals);
+int ugrt_smooth_normals(ugrt_ctx *ctx, const float *d_t_value, const float *d_ray_dir, const int *d_intersect_id,
+			const float *d_cam_position, const float *d_vertlist, const int *d_trilist,
+			const float *d_corner_normals, const float *d_normal_in, int fold, float *d_normal_out);
 
 /* ---- device: adaptive anti-aliasing, sub-pixel eye rays on edge pixels ----
  * The frame takes one eye ray per pixel, through the pixel's corner.  ugrt_aa_edges finds the pixels that lie on an edge,

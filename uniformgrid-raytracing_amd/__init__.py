@@ -200,6 +200,10 @@ PROTOTYPES = {
     "ugrt_gi_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int]),
     "ugrt_glossy_gather": (C.c_int, [_P] * 12 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_glossy_apply": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
+    "ugrt_smooth_adjacency": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "ugrt_smooth_get_adjacency": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
+    "ugrt_smooth_corner_normals": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P]),
+    "ugrt_smooth_normals": (C.c_int, [_P] * 9 + [C.c_int, _P]),
     "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
     "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),

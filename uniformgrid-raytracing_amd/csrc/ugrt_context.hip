@@ -182,6 +182,12 @@ extern "C" void ugrt_ctx_destroy(ugrt_ctx *ctx)
 	buf_free(ctx->pseg);
 	buf_free(ctx->pbkt);
 	buf_free(ctx->sray);
+	for (int j = 0; j < 2; j++) {
+		buf_free(ctx->sm_key[j]);
+		buf_free(ctx->sm_val[j]);
+	}
+	buf_free(ctx->sm_start);
+	buf_free(ctx->sm_rec);
 	if (ctx->h_pinned)
 		(void)hipHostFree(ctx->h_pinned);
 	if (ctx->d_small)
@@ -240,6 +246,10 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = (long long)ctx->uniform_reused;
 	else if (strcmp(key, "light_builds_reused") == 0)
 		*value = (long long)ctx->light_reused;
+	else if (strcmp(key, "smooth_adjacency_builds") == 0)
+		*value = (long long)ctx->sm_adjacency_builds;
+	else if (strcmp(key, "smooth_normal_builds") == 0)
+		*value = (long long)ctx->sm_normal_builds;
 	else if (strcmp(key, "primary_slots_unarmed") == 0) {
 		// (tests) merge slots of the primary pass that are not all ones + segment counters that are not zero: between
 		// traces there is none, the wave that finishes a split cell's tile leaves both so

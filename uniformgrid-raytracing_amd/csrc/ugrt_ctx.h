@@ -257,6 +257,12 @@ struct ugrt_ctx {
 	// screen-grid builds that put their merge off, and those of them whose merge was carried out later after all
 	// (ugrt_ctx_get_state "primary_deferred_merges", "primary_completed_merges")
 	unsigned long long merges_deferred = 0, merges_completed = 0;
+	// smooth shading (ugrt_smooth.hip): the corners' keys and indices (ping-pong of the sort; [1] is
+	// sorted), start[] per key, {A, N} per face; the face and vertex counts the adjacency was built for
+	DevBuf sm_key[2], sm_val[2], sm_start, sm_rec;
+	bool sm_valid = false;
+	int sm_faces = 0, sm_vertices = 0;
+	unsigned long long sm_adjacency_builds = 0, sm_normal_builds = 0; // ugrt_ctx_get_state "smooth_adjacency_builds", "smooth_normal_builds"
 };
 
 #define UGRT_HIP(call)                                                                            \

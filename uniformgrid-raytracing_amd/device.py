@@ -506,6 +506,38 @@ class Context:
         check(lib.ugrt_glossy_apply(self._h, _ptr(img), _ptr(acc), int(num_samples), _ptr(ids), _ptr(reflect),
                                     int(num_materials)))
 
+    # -- smooth shading ---------------------------------
+    def smooth_adjacency(self, faces, num_faces, num_vertices, vertex_key=None):
+        """The corners 3f + k of the face list stably sorted by their vertex's key (vertex_key: a DEVICE tensor of one
+        int32 per vertex, scenes.weld's, or None: the vertex itself) and the keys' starts, kept by the context; indices and
+        keys lie in 0..num_vertices-1.  get_state("smooth_adjacency_builds") counts the calls."""
+        check(lib.ugrt_smooth_adjacency(self._h, _ptr(faces), int(num_faces), int(num_vertices), _ptr(vertex_key)))
+        self._smooth_counts = (int(num_faces), int(num_vertices))  # (the sizes of smooth_get_adjacency's views)
+
+    def smooth_get_adjacency(self):
+        """(corners [3F], start [V + 1]) as int32 torch views of the context's arrays (tests)."""
+        corners, start = _P(), _P()
+        check(lib.ugrt_smooth_get_adjacency(self._h, C.byref(corners), C.byref(start)))
+        nf, nv = self._smooth_counts
+        return (self._wrap_u32_uncached(corners.value, 3 * nf) if nf else self.wrap_u32(0, 0),
+                self._wrap_u32_uncached(start.value, nv + 1))
+
+    def smooth_corner_normals(self, faces, verts, num_faces, crease_cos, corner_normals):
+        """corner_normals[9F]: per corner the normalised sum of the area-weighted normals of the faces around its key
+        whose unit normal lies within crease_cos of its own face's (<= -1: all of them, > 1: its own only), in the
+        adjacency's list order; the face's own normal where that sum has no direction.  Needs smooth_adjacency.
+        get_state("smooth_normal_builds") counts the calls."""
+        check(lib.ugrt_smooth_corner_normals(self._h, _ptr(faces), _ptr(verts), int(num_faces), crease_cos,
+                                             _ptr(corner_normals)))
+
+    def smooth_normals(self, t, ray_dir, ids, cam_pos, verts, faces, corner_normals, normal_in, fold, normal_out):
+        """Before the shading call (ids holds triangle ids): normal_out[3p ..] = the hit triangle's corner normals mixed
+        with the hit's barycentric coordinates and normalised, the triangle's own normal where that fails or points away
+        from it, folded into the positive octant with fold; normal_in's where the pixel has no hit.  normal_out may be
+        normal_in."""
+        check(lib.ugrt_smooth_normals(self._h, _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos), _ptr(verts), _ptr(faces),
+                                      _ptr(corner_normals), _ptr(normal_in), 1 if fold else 0, _ptr(normal_out)))
+
     # -- anti-aliasing (DESIGN.md section 6.11) --------------------------------
     def aa_edges(self, normal, t, dirs, ids, cam_pos, mat_idx, is_shadowed, normal_cos, plane_tol, edge):
         """Before the shading call (ids holds triangle ids): edge[p] = 1 where one of the up to eight neighbours of p

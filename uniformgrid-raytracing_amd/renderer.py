@@ -38,6 +38,9 @@ running mean over at most N frames, reprojected through the surface point when t
 With ``glossy=S`` the one-stream single-light frame without ``reflect`` shows its reflecting materials as rough mirrors: S
 rays per primary hit in a lobe around the mirror direction, as wide as the material's spread, to their first hit, and a
 pass directly behind the shading call that blends the lobe's mean into the image.
+With ``smooth=True`` the shading call reads interpolated vertex normals in the place of the triangles' own: the corners'
+adjacency once per geometry, the crease-aware corner normals when the vertices move, and one pass per frame that mixes them
+at every primary hit.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -47,8 +50,8 @@ import contextlib
 
 import numpy as np
 
-from . import (GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES, MAX_FILTER_RADIUS,
-               MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
+from . import (FLAG_STATIC_GEOMETRY, GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES,
+               MAX_FILTER_RADIUS, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -366,6 +369,36 @@ def check_glossy(glossy, glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, 
     return (int(glossy), radius, bool(glossy_shadows)) + sets
 
 
+def check_smooth(smooth, smooth_cos=0.5, smooth_signed=False, reflect=False, refract=False, glossy=0, aa=0,
+                 reflect_lights=False, two_streams=False):
+    """The keywords of smooth shading.  smooth: a bool (False: off, and the other two must be at
+    their defaults); smooth_cos: a number (no NaN), the cosine of the crease angle -- a face's normal counts at a corner
+    where it lies within it of the corner's own face's (<= -1: every face, > 1: none but its own); smooth_signed: a bool,
+    True leaves the normals' signs as they are where the primary tracer folds its normals into the positive octant.
+    smooth needs the one-stream Renderer and no reflect, refract, glossy, aa or reflect_lights.  ValueError before
+    anything is enqueued.  Returns None (off) or (cos, signed)."""
+    if not isinstance(smooth, (bool, np.bool_)):
+        raise ValueError("smooth must be True or False, not %r" % (smooth,))
+    number = (int, float, np.integer, np.floating)
+    if isinstance(smooth_cos, (bool, np.bool_)) or not isinstance(smooth_cos, number) or np.isnan(np.float32(smooth_cos)):
+        raise ValueError("smooth_cos must be a number, not %r" % (smooth_cos,))
+    if not isinstance(smooth_signed, (bool, np.bool_)):
+        raise ValueError("smooth_signed must be True or False, not %r" % (smooth_signed,))
+    if not smooth:
+        if float(np.float32(smooth_cos)) != 0.5 or smooth_signed:
+            raise ValueError("smooth_cos and smooth_signed need smooth=True: they shape the vertex normals")
+        return None
+    if reflect or refract or reflect_lights:
+        raise ValueError("smooth needs reflect=False: the reflected and refracted rays leave along the flat normal")
+    if glossy:
+        raise ValueError("smooth needs glossy=0: the lobe stands around the flat normal's mirror direction")
+    if aa:
+        raise ValueError("smooth needs aa=0: the sub-pixel samples shade with the flat normal")
+    if two_streams:
+        raise ValueError("smooth needs the one-stream Renderer: the two-stream and banded frames are not built")
+    return float(np.float32(smooth_cos)), bool(smooth_signed)
+
+
 # -- the stages of a frame.  Each enqueues on the context c it is given, with the frame arrays of f (a Renderer or a
 # BandedRenderer) and the arrays of b that belong to one context (the Renderer itself, or one band).
 
@@ -433,9 +466,20 @@ def trace_shadows(c, f, b, light_grid, is_shadowed=None):
                    f.is_shadowed if is_shadowed is None else is_shadowed, b._d_map, b._prefix, b.cam_pos, b._num_chunks)
 
 
-def shade_lights(c, f, cam_pos, lights, shadows):
-    """The Lambertian shading of every light and its shadows, averaged, in one pass."""
-    c.shade_lights(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.num_materials,
+def smooth_pass(c, f, cam_pos, signed):
+    """The shading normals of a smooth frame into f.snormal, directly before the shading call
+    (the ids are the triangles' still): the corner normals mixed at every primary hit, f.normal's words elsewhere.  Returns
+    the buffer the shading call reads in the place of f.normal; f.normal itself is left to the frame's other stages."""
+    c.smooth_normals(f.t, f.dir, f.intersect_id, cam_pos, f.d_verts, f.d_faces, f.corner_normals, f.normal, not signed,
+                     f.snormal)
+    return f.snormal
+
+
+def shade_lights(c, f, cam_pos, lights, shadows, normal=None):
+    """The Lambertian shading of every light and its shadows, averaged, in one pass.  normal: the
+    normals the pass reads (smooth_pass'), f.normal unless given."""
+    c.shade_lights(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
+                   f.d_matlist, f.num_materials,
                    [pos for _, pos in lights], f.shadowed_lights if shadows else None)
 
 
@@ -660,10 +704,11 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
                 samples, f.area_mask)
 
 
-def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None):
+def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None, normal=None):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
     depth shading with the occluded levels darkened, at every depth), then add_shadows.  glossy (glossy_pass' gl): the
-    lobe's blend directly behind the shading call, where the mirror frame has its own."""
+    lobe's blend directly behind the shading call, where the mirror frame has its own.  normal (smooth_pass'): the normals
+    simpleShade | spotlight_shade read, f.normal unless given."""
     if reflect and reflect_shadows:
         c.shade_reflect_depth_occluded(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
                                        level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
@@ -676,10 +721,12 @@ def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_sha
                               level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
                               f.active_levels, f.hit_t_levels, f.hit_id_levels)
     elif frame_cnt < 2:
-        c.shade_simple(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+        c.shade_simple(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
+                       f.d_matlist,
                        f.num_materials)
     else:
-        c.shade_spotlight(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
+        c.shade_spotlight(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
+                          f.d_matlist,
                           f.num_materials)
     if glossy is not None:
         glossy_shade(c, f, glossy)
@@ -918,8 +965,11 @@ class _Band:
 
 class Renderer(_Frame, _Band):
     def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, transmit=None, ior=None, reflect_eps=1e-3,
-                 overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False, spread=None):
-        """spread: per material, the tangent of the half-angle of its reflection lobe (scenes.spread_from_sharpness; None:
+                 overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False, spread=None,
+                 vertex_key=None):
+        """vertex_key: one int per vertex, in 0..V-1 (scenes.weld; None: every vertex is its own key), for
+        display(..., smooth=True): the faces around the vertices of one key share their normals.
+        spread: per material, the tangent of the half-angle of its reflection lobe (scenes.spread_from_sharpness; None:
         zeros, mirrors), for display(..., glossy=S).
         transmit, ior: per material, how much of its colour comes from behind it (0: opaque, the default) and its index
         of refraction (default 1), for display(..., refract=True).
@@ -948,6 +998,18 @@ class Renderer(_Frame, _Band):
         if len(spr) != self.num_materials:
             raise ValueError("spread must hold one value per material (%d), not %d" % (self.num_materials, len(spr)))
         self.d_spread = ctx.upload(spr)
+        # smooth shading: the host arrays are checked here, the device side is made by the first
+        # smooth frame (_smooth_stage)
+        V = len(np.asarray(verts).reshape(-1)) // 3
+        f = np.asarray(faces).reshape(-1)
+        self._smooth_faces_ok = bool(f.size == 0 or (f.min() >= 0 and f.max() < V))
+        self._vertex_key = None
+        if vertex_key is not None:
+            key = np.asarray(vertex_key)
+            if key.ndim != 1 or len(key) != V or not np.issubdtype(key.dtype, np.integer) \
+                    or (V and (key.min() < 0 or key.max() >= V)):
+                raise ValueError("vertex_key must hold one integer in 0..%d per vertex (%d)" % (V - 1, V))
+            self._vertex_key = key.astype(np.int32)
 
     def _make_side_context(self, ctx, aux_stream, helper_thread):
         from .device import Context
@@ -1002,6 +1064,8 @@ class Renderer(_Frame, _Band):
         if self.aux is not None:
             self.aux.geometry_changed()  # the second context did not see the call
         self.temporal_reset()
+        if getattr(self, "_smooth", None) is not None:
+            self._smooth["normals"] = None  # the vertices moved: the corner normals are formed again
 
     def geometry_changed(self):
         """The vertex or face array was rewritten outside rotate_bunny: Context.geometry_changed on every context, and the
@@ -1010,6 +1074,9 @@ class Renderer(_Frame, _Band):
         if self.aux is not None:
             self.aux.geometry_changed()
         self.temporal_reset()
+        if getattr(self, "_smooth", None) is not None:
+            self._smooth["adjacency"] = False  # the faces may be others: the adjacency and the corner normals again
+            self._smooth["normals"] = None
 
     def temporal_reset(self):
         """Every effect's running mean starts again with the next temporal frame: the frame
@@ -1043,7 +1110,8 @@ class Renderer(_Frame, _Band):
                 ao_filter_plane=None, gi=0, gi_radius=None, gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0,
                 gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True,
                 temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0, glossy_sets=1, glossy_filter=0,
-                glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True):
+                glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True, smooth=False,
+                smooth_cos=0.5, smooth_signed=False):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows (needs reflect=True): the hits of every reflection level are shadowed (from the light
@@ -1108,13 +1176,29 @@ class Renderer(_Frame, _Band):
         surface with glossy_filter_cos and glossy_filter_plane into glossy_acc, and the mean is blended into the image
         with the material's reflect directly behind the shading call, before the shadows darken it (DESIGN.md section
         6.13).
+        smooth (one-stream renderer; the plain frame, frame_cnt=2, shadows=False and setup.lights; ao, area, gi and
+        temporal compose; no reflect, refract, glossy, aa or reflect_lights; False: off): smooth shading -- the shading
+        call reads, in the place of the triangles' own normals, the corner normals of the hit triangle mixed with the
+        hit's barycentric coordinates (snormal).  A corner's normal is the normalised sum of the area-weighted normals of
+        the faces around its vertex's key (Renderer(vertex_key=); scenes.weld) whose normal lies within smooth_cos, the
+        cosine of the crease angle, of the corner's own face's (corner_normals).  The adjacency is built once per renderer
+        and again after geometry_changed; the corner normals every frame, or with FLAG_STATIC_GEOMETRY when the geometry
+        (rotate_bunny, geometry_changed) or smooth_cos changed.  smooth_signed keeps the normals' signs where the primary
+        tracer folds them into the positive octant.  Nothing else reads snormal: normal, the {origin, normal} of ao_rays
+        and every mask and sum are the frame's without smooth.
         The keywords that shape an effect need the effect: gi_sets and gi_filter (need gi > 0, like every other gi_*
         keyword), aa_sets (needs aa > 0, like every other aa_* keyword), glossy_sets and glossy_filter (need glossy > 0, like
-        every other glossy_* keyword), temporal_cos and temporal_plane (need temporal > 0).
+        every other glossy_* keyword), temporal_cos and temporal_plane (need temporal > 0), smooth_cos and smooth_signed (need
+        smooth=True).
         The passes over the image's bytes run in one order, whatever is on (DESIGN.md section 6.14): the shading call;
         glossy_apply; shade_add_shadows, or with area shade_area / shade_area_vis in its place; gi_apply; aa_resolve;
         shade_ao / shade_ao_vis.  The primary hits' {origin, normal} (ao_rays / ao_active) are written once per frame, by
         the first of glossy, area, ao and gi that is on, and read by the others."""
+        if smooth is False and smooth_signed is False and smooth_cos == 0.5:
+            smooth = None  # (the defaults: nothing to check, and the frame loop pays nothing for the keywords)
+        else:
+            smooth = check_smooth(smooth, smooth_cos, smooth_signed, reflect, refract, glossy, aa, reflect_lights,
+                                  self.aux is not None)
         glossy = check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius,
                               glossy_shadows, reflect, refract, aa, temporal, getattr(setup, "lights", None), reflect_lights,
                               self.aux is not None)
@@ -1141,7 +1225,7 @@ class Renderer(_Frame, _Band):
                                                 self._ao_stage(ao, ao_radius, shade, ao_more))
         if getattr(setup, "lights", None) is not None:
             lights = check_lights(setup.lights, reflect, self.aux is not None)
-            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more))
+            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more), smooth)
         if temporal and shade:  # (the effects' stages are made behind _temporal_begin)
             ao_asked, gi_asked, ao = ao, gi, None
         else:
@@ -1208,8 +1292,12 @@ class Renderer(_Frame, _Band):
             gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area or glossy))
         if aa:
             aa_pass(ctx, self, cam.camcoords, aa, lcam.worldori[:3] if shadows and aa[5] else None)
+        normal = None
+        if smooth:
+            self._smooth_stage(smooth[0])
+            normal = smooth_pass(ctx, self, self.cam_pos, smooth[1])
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows,
-                    glossy or None)
+                    glossy or None, normal)
         if area and tp:
             area_shade_temporal(ctx, self, tp, area_t)
         elif area and area_filter:
@@ -1230,6 +1318,29 @@ class Renderer(_Frame, _Band):
             ao_shade_temporal(ctx, self, tp, ao)
         elif ao:
             ao_shade(ctx, self, *ao)
+
+    # -- smooth shading
+    def _smooth_stage(self, cos):
+        """What smooth_pass reads, in place: snormal [3 W*H] and corner_normals [9 F], allocated on first use; the
+        context's adjacency, built once and again after geometry_changed; the corner normals, formed every frame -- with
+        FLAG_STATIC_GEOMETRY only when the geometry (rotate_bunny, geometry_changed) or cos is not what they were formed
+        of."""
+        ctx, t = self.ctx, self.torch
+        st = getattr(self, "_smooth", None)
+        if st is None:
+            if not self._smooth_faces_ok:
+                raise ValueError("smooth needs every index of the face list in 0..V-1")
+            st = self._smooth = {"adjacency": False, "normals": None,
+                                 "key": None if self._vertex_key is None else ctx.upload(self._vertex_key)}
+            self.snormal = ctx.empty(3 * self.N, t.float32)
+            self.corner_normals = ctx.empty(9 * self.F, t.float32)
+        if not st["adjacency"]:
+            ctx.smooth_adjacency(self.d_faces, self.F, self.d_verts.numel() // 3, st["key"])
+            st["adjacency"], st["normals"] = True, None
+        static = bool(int(ctx.cfg.flags) & FLAG_STATIC_GEOMETRY)
+        if not static or st["normals"] != (cos,):
+            ctx.smooth_corner_normals(self.d_faces, self.d_verts, self.F, cos, self.corner_normals)
+            st["normals"] = (cos,)
 
     # -- temporal accumulation (DESIGN.md section 6.12)
     def _temporal_begin(self, temporal, cam):
@@ -1486,7 +1597,7 @@ class Renderer(_Frame, _Band):
     def _upload_area_sets(self, table):
         return self.ctx.upload(table.reshape(-1))
 
-    def _display_lights(self, setup, lights, shadows, shade, ao=None):
+    def _display_lights(self, setup, lights, shadows, shade, ao=None, smooth=None):
         """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
         shadow stage into its row of shadowed_lights, then ONE shading pass.  dd_camcoords is the last light's when
         the shading runs, as the reference's loop leaves it."""
@@ -1509,7 +1620,11 @@ class Renderer(_Frame, _Band):
         if ao:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             ao_pass(ctx, self, self.cam_pos, *ao)
-        shade_lights(ctx, self, self.cam_pos, lights, shadows)
+        normal = None
+        if smooth:
+            self._smooth_stage(smooth[0])
+            normal = smooth_pass(ctx, self, self.cam_pos, smooth[1])
+        shade_lights(ctx, self, self.cam_pos, lights, shadows, normal)
         if ao:
             ao_shade(ctx, self, *ao)
 
@@ -1738,7 +1853,8 @@ class BandedRenderer(_Frame):
                 gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
                 aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0,
                 glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
-                glossy_shadows=True):
+                glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False):
+        check_smooth(smooth, smooth_cos, smooth_signed, False, False, 0, 0, False, True)  # raises with smooth=True
         check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius, glossy_shadows,
                      reflect, refract, aa, temporal, getattr(setup, "lights", None), False, True)  # raises with glossy > 0
         check_temporal(temporal, temporal_cos, temporal_plane, True, getattr(setup, "lights", None), False,

@@ -471,6 +471,74 @@ def glossy(outdir=None, scale=1.0):
     return info
 
 
+def weld(verts, tol=0.0):
+    """One int32 key per vertex for Renderer(vertex_key=): the lowest index among the vertices
+    equal to it, so that the generators' duplicated vertices -- every quad of add_box brings its own corners -- share their
+    faces.  tol == 0 compares the float32 bit patterns, -0 equal to +0.  tol > 0 compares the coordinates rounded to
+    multiples of tol: add_cylinder's seam columns (cos and sin of 0 and of 2 pi) differ in their last bits and need it."""
+    v = np.ascontiguousarray(np.asarray(verts, np.float32).reshape(-1, 3))
+    if not float(tol) >= 0.0:
+        raise ValueError("tol must be a number not below 0, not %r" % (tol,))
+    if len(v) == 0:
+        return np.zeros(0, np.int32)
+    if tol == 0:
+        rows = v.view(np.uint32).copy()
+        rows[rows == 0x80000000] = 0
+    else:
+        rows = np.rint(v.astype(np.float64) / float(tol))
+        rows[rows == 0] = 0.0  # (-0 as +0)
+        rows = rows.view(np.uint64)
+    _, first, inverse = np.unique(rows, axis=0, return_index=True, return_inverse=True)
+    return first[np.asarray(inverse).reshape(-1)].astype(np.int32)
+
+
+MATERIALS_SMOOTH = [
+    # name, Ka, Kd, reflect
+    ("s0_floor", (0.2, 0.2, 0.2), (0.62, 0.60, 0.55), 0.0),
+    ("s1_back_wall", (0.2, 0.2, 0.2), (0.30, 0.40, 0.80), 0.0),
+    ("s2_right_wall", (0.2, 0.2, 0.2), (0.80, 0.25, 0.20), 0.0),
+    ("s3_left_wall", (0.2, 0.2, 0.2), (0.25, 0.70, 0.30), 0.0),
+    ("s4_ball", (0.2, 0.2, 0.2), (0.85, 0.80, 0.70), 0.0),
+    ("s5_column", (0.2, 0.2, 0.2), (0.70, 0.66, 0.60), 0.0),
+    ("s6_box", (0.2, 0.2, 0.2), (0.90, 0.75, 0.15), 0.0),
+]
+
+
+def smooth(outdir=None, scale=1.0):
+    """glass()'s room [0,10]x[0,8]x[0,5] with three solids for display(smooth=True): an
+    icosphere(2) ball, whose 320 flat triangles are what smooth shading is for; a 32-segment column without caps, whose
+    seam only a weld with a tolerance closes; and a box with 3 x 3 vertices per side, whose edges a crease angle must
+    keep.  info["vertex_key"] is weld(verts, 1e-5); info["objects"] names the solids' face ranges [begin, end).  The
+    solids are wound outwards.  The room's tessellation follows the scale, the solids do not."""
+    mesh = Mesh()
+    n = max(2, int(20 * max(0.05, scale) ** 0.5))
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 0, faces="z")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 1, faces="X")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 2, faces="y")
+    add_box(mesh, (0, 0, 0), (10, 8, 5), n, 3, faces="Y")
+    objects = {}
+    begin = mesh.ntris()
+    sv, sf = icosphere(2)
+    mesh.add(*_wind_outwards(sv * 1.1 + np.array([5.5, 2.4, 1.35]), sf), 4)
+    objects["sphere"] = (begin, mesh.ntris())
+    begin = mesh.ntris()
+    add_cylinder(mesh, 6.6, 5.6, 0.0, 3.2, 0.6, 32, 4, 5)
+    objects["cylinder"] = (begin, mesh.ntris())
+    begin = mesh.ntris()
+    box = Mesh()
+    add_box(box, (3.9, 3.7, 0.0), (4.9, 4.7, 1.0), 2, 6)
+    bv, bf, _ = box.arrays()
+    mesh.add(*_wind_outwards(bv, bf), 6)
+    objects["box"] = (begin, mesh.ntris())
+    cams = {"ref": dict(eye=(0.6, 3.9, 2.0), look=(6.0, 4.3, 1.2), up=(0, 0, 1), near=0.1, far=100.0)}
+    light_cam = dict(eye=(4.0, 4.0, 9.0), look=(4.0, 4.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
+    info = _finish(outdir, "smooth%dk" % round(mesh.ntris() / 1000), mesh, MATERIALS_SMOOTH,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(4.0, 4.0, 4.5)))
+    info["vertex_key"] = weld(info["verts"], 1e-5)
+    info["objects"] = objects
+    return info
+
+
 def ao_directions(S):
     """The S local directions of the ambient-occlusion hemisphere: a deterministic
     cosine-weighted spiral, r = sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), direction
