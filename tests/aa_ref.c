@@ -108,6 +108,16 @@ static void aa_dir(const float *eye, const float *tex, int W, int H, int strict,
 	NORMALIZE(d);
 }
 
+/* aa_dir for n image positions, exported so that a test can aim triangles at the rays of chosen (pixel, offset) pairs
+ * (tests/test_antialias_synthetic.py); d: [n][3].  The offset is the caller's: no clamp here. */
+void aa_directions(const float *eye, const float *tex, int W, int H, int strict, int n, const float *fcol, const float *frow,
+		   float *d)
+{
+	int i;
+	for (i = 0; i < n; i++)
+		aa_dir(eye, tex, W, H, strict, fcol[i], frow[i], d + 3 * (size_t)i);
+}
+
 /* Moller-Trumbore in the operation order of orc_mt_signed: 1 and *t when the ray hits with t_lo < t < t_hi */
 static int aa_mt(const float *o, const float *d, const float *vertlist, const int *trilist, u32 f, float t_lo, float t_hi,
 		 float *t_out)

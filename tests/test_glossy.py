@@ -668,6 +668,33 @@ def test_launch_shapes_and_a_band_change_no_word(ugrt, O, GL, torch):
 
 
 @pytest.mark.gpu
+def test_a_table_that_is_not_16_byte_aligned_changes_no_word(ugrt, O, GL, torch):
+    """The copy of the point table to LDS goes float4 by float4 where the table is 16-byte aligned and float by float
+    elsewhere: the table 0, 4, 8 and 12 bytes into an allocation.  Its 2 S set_w set_h floats leave 0 or 2 behind the last
+    float4 (an even count leaves neither 1 nor 3): S = 2 and 4 and the 2 x 3 tile leave 0, S = 1, 3 and 5 leave 2; S = 5 on
+    the 4 x 4 tile is 160 floats, three rounds of the float-by-float loop."""
+    z = gsyn(O, ugrt)
+    d = _syn_context(ugrt, z)
+    radius = 3.0
+    for S, tile in ((2, (1, 1)), (4, (1, 1)), (1, (1, 1)), (3, (1, 1)), (5, (1, 1)), (8, (2, 3)), (5, (4, 4))):
+        pts = np.ascontiguousarray(_points(ugrt, S, 16)[:tile[0] * tile[1]])
+        count = 2 * S * tile[0] * tile[1]
+        assert count % 4 == (2 if tile == (1, 1) and S % 2 else 0)
+        want = syn_sums(GL, z, S, tile, pts, radius, True)
+        for shift in (0, 1, 2, 3):
+            room = torch.full((count + 8,), float("nan"), dtype=torch.float32, device=d.ctx.device)
+            base = (-room.data_ptr() // 4) % 4  # floats up to the next 16-byte boundary
+            table = room[base + shift:base + shift + count]
+            table.copy_(d.ctx.upload(pts.reshape(-1)))
+            assert table.data_ptr() % 16 == 4 * shift
+            # first the same points in the reverse order from an aligned table: what a launch finds in LDS is not its table
+            turned = d.ctx.upload(np.ascontiguousarray(pts[:, ::-1]).reshape(-1))
+            np.testing.assert_array_equal(_gather(torch, d, z, S, tile, turned, radius, True), want)
+            np.testing.assert_array_equal(_gather(torch, d, z, S, tile, table, radius, True), want,
+                                          err_msg="S %d tile %s, %d bytes into the allocation" % (S, tile, 4 * shift))
+
+
+@pytest.mark.gpu
 def test_the_gather_is_the_composition_of_the_kernels_that_exist(ugrt, O, GL, torch):
     """S = 8, radius +inf, one set: per sample the restatement's explicit rays through ugrt_trace_dda, ugrt_occlusion_rays,
     ugrt_trace_dda_any and ugrt_shade_reflect_depth_occluded at depth 1 with every material's reflect = 1 over a black

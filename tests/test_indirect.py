@@ -532,6 +532,31 @@ def test_launch_shapes_and_a_band_change_no_word(ugrt, O, IR, torch):
 
 
 @pytest.mark.gpu
+def test_a_table_that_is_not_16_byte_aligned_changes_no_word(ugrt, O, IR, torch):
+    """The copy of the direction table to LDS goes float4 by float4 where the table is 16-byte aligned and float by float
+    elsewhere: the table 0, 4, 8 and 12 bytes into an allocation, with 3 S floats that leave 0, 1, 2 and 3 behind the last
+    float4 (S = 4, 3, 2, 5) and with more than 64 of them (S = 32: a second round of the float-by-float loop)."""
+    y = syn(O, ugrt)
+    d = _syn_context(ugrt, y)
+    radius = 3.0
+    for S in (4, 3, 2, 5, 32):
+        dirs = _table(ugrt, S, 1)
+        assert (3 * S) % 4 == {4: 0, 3: 1, 2: 2, 5: 3, 32: 0}[S]
+        want = syn_sums(IR, y, S, (1, 1), dirs, radius, True)
+        for shift in (0, 1, 2, 3):
+            room = torch.full((3 * S + 8,), float("nan"), dtype=torch.float32, device=d.ctx.device)
+            base = (-room.data_ptr() // 4) % 4  # floats up to the next 16-byte boundary
+            table = room[base + shift:base + shift + 3 * S]
+            table.copy_(d.ctx.upload(dirs.reshape(-1)))
+            assert table.data_ptr() % 16 == 4 * shift
+            # first the same directions in the reverse order from an aligned table: what a launch finds in LDS is not its table
+            turned = d.ctx.upload(np.ascontiguousarray(dirs[:, ::-1]).reshape(-1))
+            np.testing.assert_array_equal(_gather(torch, d, y, S, (1, 1), turned, radius, True), want)
+            np.testing.assert_array_equal(_gather(torch, d, y, S, (1, 1), table, radius, True), want,
+                                          err_msg="S %d, %d bytes into the allocation" % (S, 4 * shift))
+
+
+@pytest.mark.gpu
 def test_the_gather_is_the_composition_of_the_kernels_that_exist(ugrt, O, IR, torch):
     """S = 8, radius +inf, one set: per direction the explicit rays through ugrt_trace_dda, ugrt_occlusion_rays,
     ugrt_trace_dda_any and ugrt_shade_reflect_depth_occluded at depth 1 with every material's reflect = 1 over a black
