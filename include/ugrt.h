@@ -911,6 +911,54 @@ int ugrt_glossy_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsign
 int ugrt_glossy_apply(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_acc, int num_samples,
 		      const int *d_intersect_id, const float *d_reflect, int num_materials);
 
+/* ---- device: Fresnel glass, a reflected and a transmitted ray per glass hit ----
+ * The refraction chain follows one ray per hit; here a glass hit splits, and a pixel's rays form a tree of depth `depth`
+ * that one launch walks.  Per frame: ugrt_refract_rays, ugrt_fresnel_gather, ugrt_fresnel_shade in the place of
+ * ugrt_shade_reflect_depth*.  All arithmetic is fp32 without contraction, in the stated order.
+ *
+ * A node is a ray {o, d} with a weight w and a level j, and its hit (t, triangle) of material m in range.  The root
+ * (level 0) is the primary hit of an active pixel: ray {cam, dir}, w = 1.  k = d_transmit[m] > 0 ? d_transmit[m] :
+ * d_reflect[m].  A mirror (d_transmit[m] not > 0, d_reflect[m] > 0) has one child: the reflected ray, weight w*k.  Glass
+ * (d_transmit[m] > 0) forms n, front, u, c, ior, eta and k2 = 1 - (eta*eta)*(1 - c*c) as the refracted ray above does; k2 < 0
+ * gives one child, the mirrored ray, weight w*k; otherwise r0 = ((1 - ior)/(1 + ior))^2, cs = front ? c : sqrt(k2),
+ * x = 1 - cs, F = scale * (r0 + (1 - r0)*(((x*x)*(x*x))*x)), child 0 the transmitted ray with (w*k)*(1 - F) and child 1 the
+ * reflected ray with (w*k)*F.  The root's child 0 is d_rays[6p ..] as given.  A child is followed where its weight is
+ * > min_weight (a NaN is not).  A node goes on when j < depth and a child is followed: it adds (w*(1 - k))*L, any other
+ * node w*L, where L is the clamped Lambert colour of the hit under the context's camera block and light -- 0 on a miss or
+ * a material out of range, the stored normal and t > 0 for the root, the triangle's normal for a level, and there divided
+ * by 3.0f where the any-hit walk that sees through glass (t_max = 1) flags the occlusion ray of the hit to shadow_light
+ * (host float[3]; NULL: no shadow phase).  Leaf b (depth bits; bit j = the child taken at level j's split, 0 where there
+ * was none) owns the nodes whose remaining bits are 0 and adds their terms front to back from +0; the pixel's value is the
+ * leaves' sum formed for j = depth-1 .. 0 by s[b] = s[b] + s[b + 2^j] (b < 2^j).  With scale = 0 every leaf but 0 holds +0
+ * and the bytes are those of the chain of refracted levels shaded at the same depth.
+ *
+ * The gather: d_rays / d_active are the level-1 rays and words of the refracted rays' first call, d_normal ..
+ * d_cam_position the primary arrays (d_intersect_id holds TRIANGLES: the call runs before the shading call).  For an
+ * active pixel p of the band d_acc[4p .. 4p + 2] is the value above and d_acc[4p + 3] = 1.0f; inactive pixels of the band
+ * get four zeros, pixels outside the band are not written.  2^depth neighbouring lanes are the leaves of a pixel; one
+ * prepare launch over d_active, groups drawn from a ticket, one 16-byte store per pixel, no atomics on the sums.  Options
+ * "any_rays_per_wave", "any_coop" and "dda_blocks" shape the launch and change no word.  Stages UGRT_ST_WORKLIST /
+ * UGRT_ST_TRACE_DDA.  The call leaves the split-walk history of the closest-hit trace alone.  The context's state
+ * "fresnel_nodes" gives the nodes the last call walked (it waits for the stream), "fresnel_gathers" counts the calls.
+ * depth outside 1..UGRT_MAX_FRESNEL_DEPTH, scale outside [0, 1] or NaN, min_weight < 0 or NaN, eps NaN, num_materials < 1,
+ * a d_acc that is not 16-byte aligned, or a null argument other than shadow_light: UGRT_EINVAL and nothing is enqueued;
+ * without a built uniform grid the error of the closest-hit trace. */
+#define UGRT_MAX_FRESNEL_DEPTH 6 /* 2^6 leaves: one wave */
+int ugrt_fresnel_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+			const float *d_vertlist, const int *d_trilist, const float *d_rays, const int *d_active,
+			const float *d_normal, const float *d_t_value, const float *d_ray_dir, const int *d_intersect_id,
+			const float *d_cam_position, const int *d_mat_idx, const float *d_mat_list, const float *d_reflect,
+			const float *d_transmit, const float *d_ior, int num_materials, int depth, float scale, float min_weight,
+			const float *shadow_light, float eps, float *d_acc);
+/* The shading call of a Fresnel frame (it rewrites d_intersect_id to material indices as the other shading calls do):
+ * a pixel of the band with d_acc[4p + 3] != 0 gets the bytes of d_acc[4p .. 4p + 2], every other pixel what the depth
+ * shading gives a pixel without a level-1 ray.  Stage UGRT_ST_SHADE.  A d_acc that is not 16-byte aligned or a null
+ * argument: UGRT_EINVAL and nothing is enqueued.  (Named fresnel_shade, not shade_fresnel: the ugrt_shade_* family is a
+ * closed table that tests/test_shade_calls.py counts.) */
+int ugrt_fresnel_shade(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+		       const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+		       const float *d_mat_list, int num_materials, const float *d_acc);
+
 /* ---- device: smooth shading, crease-aware vertex normals interpolated per pixel ----
  * No reference counterpart: the reference shades every pixel with its triangle's normal.  All arithmetic is fp32, every
  * + - * / sqrt one IEEE operation, CROSS / DOT / NORMALIZE in the reference's operand order; every output is a function of

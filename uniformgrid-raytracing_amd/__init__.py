@@ -66,6 +66,7 @@ MAX_AA_SAMPLES = 32  # UGRT_MAX_AA_SAMPLES
 MAX_TEMPORAL_FRAMES = 64  # UGRT_MAX_TEMPORAL_FRAMES
 MAX_GLOSSY_SAMPLES = 32  # UGRT_MAX_GLOSSY_SAMPLES
 MAX_GLOSSY_SPREAD = 1.0  # UGRT_MAX_GLOSSY_SPREAD
+MAX_FRESNEL_DEPTH = 6  # UGRT_MAX_FRESNEL_DEPTH
 TEMPORAL_DEN = 256  # UGRT_TEMPORAL_DEN
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
@@ -200,6 +201,8 @@ PROTOTYPES = {
     "ugrt_gi_apply": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P, _P, C.c_int]),
     "ugrt_glossy_gather": (C.c_int, [_P] * 12 + [C.c_int, C.c_int, C.c_int, _P, C.c_float, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_glossy_apply": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
+    "ugrt_fresnel_gather": (C.c_int, [_P] * 18 + [C.c_int, C.c_int, C.c_float, C.c_float, _F3, C.c_float, _P]),
+    "ugrt_fresnel_shade": (C.c_int, [_P] * 9 + [C.c_int, _P]),
     "ugrt_smooth_adjacency": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "ugrt_smooth_get_adjacency": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "ugrt_smooth_corner_normals": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P]),

@@ -250,7 +250,18 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = (long long)ctx->sm_adjacency_builds;
 	else if (strcmp(key, "smooth_normal_builds") == 0)
 		*value = (long long)ctx->sm_normal_builds;
-	else if (strcmp(key, "primary_slots_unarmed") == 0) {
+	else if (strcmp(key, "fresnel_gathers") == 0)
+		*value = (long long)ctx->fresnel_gathers;
+	else if (strcmp(key, "fresnel_nodes") == 0) {
+		// the nodes the last ugrt_fresnel_gather walked (waits for the stream)
+		unsigned long long n = 0;
+		if (ctx->fresnel_gathers) {
+			UGRT_HIP(hipSetDevice(ctx->device));
+			UGRT_HIP(hipStreamSynchronize(ctx->stream));
+			UGRT_HIP(hipMemcpy(&n, ctx->d_small + UGRT_DSMALL_FRESNEL, sizeof(n), hipMemcpyDeviceToHost));
+		}
+		*value = (long long)n;
+	} else if (strcmp(key, "primary_slots_unarmed") == 0) {
 		// (tests) merge slots of the primary pass that are not all ones + segment counters that are not zero: between
 		// traces there is none, the wave that finishes a split cell's tile leaves both so
 		const size_t ncell = (size_t)ctx->nbx * (size_t)ctx->nby;

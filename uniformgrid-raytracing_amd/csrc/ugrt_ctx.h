@@ -123,7 +123,8 @@ struct Grid {
                                    // found, status word, pad, the two u64 work counters at the start of the exact pass
 #define UGRT_DSMALL_PRIMARY 264    // u64 [UGRT_PRIMARY_STATS] work counters of the primary tracer (FLAG_COUNT_WORK)
 #define UGRT_DSMALL_FRAGS 296       // [3] shadow tracer by fragments: cursor, finished workgroups (both zero between passes), checked count
-#define UGRT_DSMALL_WORDS (132 + 104 + 28 + 32 + 4)
+#define UGRT_DSMALL_FRESNEL 300     // u64: nodes walked by the last ugrt_fresnel_gather
+#define UGRT_DSMALL_WORDS (132 + 104 + 28 + 32 + 4 + 2)
 // layout of ugrt_ctx::h_pinned (u32 words of pinned host memory for small read-backs)
 #define UGRT_PIN_RW 0           // {narrow references, wide triangles} of the running (waiting) build
 #define UGRT_PIN_CELLS_USED 4   // [3] per grid
@@ -145,7 +146,7 @@ struct Grid {
 #define UGRT_DDA_STATS 46
 #define UGRT_PRIMARY_STATS 16
 static_assert(UGRT_DSMALL_DDA + 2 * UGRT_DDA_STATS <= UGRT_DSMALL_RW, "the DDA's counters run into the build counts");
-static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_FRAGS && UGRT_DSMALL_FRAGS + 3 <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
+static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_FRAGS && UGRT_DSMALL_FRAGS + 3 <= UGRT_DSMALL_FRESNEL && UGRT_DSMALL_FRESNEL + 2 <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
 
 struct ProfPair {
 	hipEvent_t a, b;
@@ -263,6 +264,7 @@ struct ugrt_ctx {
 	bool sm_valid = false;
 	int sm_faces = 0, sm_vertices = 0;
 	unsigned long long sm_adjacency_builds = 0, sm_normal_builds = 0; // ugrt_ctx_get_state "smooth_adjacency_builds", "smooth_normal_builds"
+	unsigned long long fresnel_gathers = 0; // ugrt_fresnel_gather calls that launched ("fresnel_gathers")
 };
 
 #define UGRT_HIP(call)                                                                            \

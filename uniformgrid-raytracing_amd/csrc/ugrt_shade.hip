@@ -995,6 +995,65 @@ extern "C" int ugrt_shade_reflect_depth_occluded(ugrt_ctx *ctx, unsigned char *d
 				   d_trilist, depth, d_rays, d_active, d_hit_t, d_hit_id, d_occluded);
 }
 
+// Fresnel glass: ugrt_fresnel_gather's sums into the image, in the place of
+// ugrt_shade_reflect_depth*.  A pixel that carries a tree (acc[4p + 3] != 0) gets the bytes of its three sums; every other
+// pixel what k_shade_reflect_depth gives a pixel without a level-1 ray: acc = 0 + 1 * the primary colour.
+__global__ __launch_bounds__(PX_THREADS) void k_fresnel_shade(CamBlock cam, unsigned char *__restrict__ d_img,
+							       const float *__restrict__ dd_normal,
+							       const float *__restrict__ dd_t_value,
+							       const float *__restrict__ dd_dir, int *__restrict__ dd_intersect_id,
+							       const float *__restrict__ d_cam_pos, const int *__restrict__ mat_idx,
+							       const float *__restrict__ mat_list, int mat_count,
+							       const float *__restrict__ sums, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	int pixelID = p0 + i;
+	float acc[3] = { 0.0f, 0.0f, 0.0f };
+	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
+	const int idx = hit.material_id();
+	const float4 s = *(const float4 *)(sums + 4 * (size_t)pixelID);
+	if (s.w != 0.0f) {
+		acc[0] = s.x;
+		acc[1] = s.y;
+		acc[2] = s.z;
+	} else if (idx >= 0) {
+		float color[3] = { 0.0f, 0.0f, 0.0f }, material[6];
+		const float t_value = hit.t_value();
+		d_material_kd(mat_list, idx, material);
+		if (t_value > 0) {
+			float point[3], nrm[3];
+			hit.point(t_value, point);
+			hit.normal(nrm);
+			d_lambert<false>(cam, point, nrm, color, material, 1.0f);
+			d_clamp1(color);
+		}
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+			acc[k] = acc[k] + 1.0f * color[k];
+	}
+	d_img[pixelID * 3 + 0] = d_to_u8(acc[0]);
+	d_img[pixelID * 3 + 1] = d_to_u8(acc[1]);
+	d_img[pixelID * 3 + 2] = d_to_u8(acc[2]);
+}
+
+extern "C" int ugrt_fresnel_shade(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+				  const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+				  const float *d_mat_list, int num_materials, const float *d_acc)
+{
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx, d_mat_list,
+			       "fresnel_shade");
+	if (rc)
+		return rc;
+	if (!d_acc)
+		return ugrt_fail(UGRT_EINVAL, "fresnel_shade: null argument");
+	if (((size_t)d_acc & 15u) != 0u)
+		return ugrt_fail(UGRT_EINVAL, "fresnel_shade: d_acc is not 16-byte aligned");
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_fresnel_shade, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, d_acc);
+}
+
 // ---------------------------------------------------------------------------
 // reflections under several lights: the depth composition of k_shade_reflect_depth<OCC> and
 // k_add_shadows once per light and the mean of the bytes, in one pass.  The level chain (active_{j+1}, k_j, w) does not

@@ -10,13 +10,27 @@
 
 #define WALK_AHEAD 8 // steps planned (and looked up in the bitmap) per window
 
-// k_trace_dda_any's loop: true = some triangle of a visited cell passes the exact test with 0 < t < t_max.
-template <bool REC>
+// THRU: which triangles a ray passes (as ugrt_trace_dda_any_thru says it): f is see-through when
+// m = mat_idx[f] is in range and transmit[m] > 0
+struct WalkThru {
+	const int *mat_idx;
+	const float *transmit;
+	int mat_count;
+};
+__device__ __forceinline__ bool d_walk_see_through(const WalkThru *a, u32 f)
+{
+	const int m = a->mat_idx[f];
+	return m >= 0 && m < a->mat_count && a->transmit[m] > 0;
+}
+
+// k_trace_dda_any's loop: true = some triangle of a visited cell passes the exact test with 0 < t < t_max.  THRU: an
+// accepted test counts only if the triangle is not see-through (thru; without THRU it is not read).
+template <bool REC, bool THRU = false>
 __device__ __forceinline__ bool d_any_walk(const DGrid &g, const u32 *__restrict__ value_list, const u32 *__restrict__ span,
 					   const u32 *__restrict__ offset, const u32 *__restrict__ bitmap,
 					   const float *__restrict__ verts, const int *__restrict__ tris,
 					   const float4 *__restrict__ rec, const float *o, const float *d, float t_max,
-					   bool walking, u32 COOP, int lane)
+					   bool walking, u32 COOP, int lane, const WalkThru *thru = nullptr)
 {
 	float tmax[3] = { 0, 0, 0 }, tdelta[3] = { 0, 0, 0 };
 	int c[3] = { 0, 0, 0 }, step[3] = { 0, 0, 0 };
@@ -65,6 +79,10 @@ __device__ __forceinline__ bool d_any_walk(const DGrid &g, const u32 *__restrict
 					float t9[9], t;
 					d_load_triangle<REC>(rec, verts, tris, value_list[off + r], o[0], o[1], o[2], t9);
 					if (d_mt_core(&t9[0], &t9[3], &t9[6], d, &t) && t > 0.0f && t < t_max) {
+						if constexpr (THRU) { // (the two loads: behind an accepted test only)
+							if (d_walk_see_through(thru, value_list[off + r]))
+								continue;
+						}
 						occ = true;
 						break;
 					}
@@ -85,6 +103,10 @@ __device__ __forceinline__ bool d_any_walk(const DGrid &g, const u32 *__restrict
 						float t9[9], t;
 						d_load_triangle<REC>(rec, verts, tris, value_list[offl + r], ox, oy, oz, t9);
 						acc = d_mt_core(&t9[0], &t9[3], &t9[6], dl, &t) && t > 0.0f && t < t_max;
+						if constexpr (THRU) {
+							if (acc && d_walk_see_through(thru, value_list[offl + r]))
+								acc = false;
+						}
 					}
 					hit = __ballot(acc) != 0ull;
 				}

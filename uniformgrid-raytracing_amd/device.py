@@ -506,6 +506,28 @@ class Context:
         check(lib.ugrt_glossy_apply(self._h, _ptr(img), _ptr(acc), int(num_samples), _ptr(ids), _ptr(reflect),
                                     int(num_materials)))
 
+    # -- Fresnel glass ----------------------------------
+    def fresnel_gather(self, value, span, offset, verts, faces, rays, active, normal, t, ray_dir, ids, cam_pos, mat_idx,
+                       mat_list, reflect, transmit, ior, num_materials, depth, scale, min_weight, shadow_light, eps, acc):
+        """A pixel's whole ray tree in one launch, before the shading call (ids holds triangle ids): an active pixel of
+        refract_rays' level-1 rays follows, at every glass hit down to level `depth` (1..MAX_FRESNEL_DEPTH), the
+        transmitted ray with (1 - F) and the reflected ray with F of the material's transmit, F = scale * Schlick's share,
+        children of a weight <= min_weight dropped; the levels' Lambert colours (a third where shadow_light, three host
+        floats or None, is hidden behind something that is not glass) are blended as shade_reflect_depth blends the
+        chain's: acc[4p + k] for k < 3 (float32), acc[4p + 3] = 1."""
+        light = None if shadow_light is None else _points([shadow_light])[1]
+        check(lib.ugrt_fresnel_gather(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces), _ptr(rays),
+                                      _ptr(active), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                      _ptr(mat_idx), _ptr(mat_list), _ptr(reflect), _ptr(transmit), _ptr(ior),
+                                      int(num_materials), int(depth), scale, min_weight, light, eps, _ptr(acc)))
+
+    def shade_fresnel(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, acc):
+        """The shading call of a fresnel frame (ugrt_fresnel_shade; ids become material indices): the bytes of
+        fresnel_gather's sums where acc[4p + 3] != 0, elsewhere the primary hit's colour as shade_reflect_depth gives it
+        to a pixel without a level-1 ray."""
+        check(lib.ugrt_fresnel_shade(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                     _ptr(mat_idx), _ptr(mat_list), int(num_materials), _ptr(acc)))
+
     # -- smooth shading (DESIGN.md section 6.15) ---------------------------------
     def smooth_adjacency(self, faces, num_faces, num_vertices, vertex_key=None):
         """The corners 3f + k of the face list stably sorted by their vertex's key (vertex_key: a DEVICE tensor of one

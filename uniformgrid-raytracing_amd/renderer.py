@@ -41,6 +41,9 @@ pass directly behind the shading call that blends the lobe's mean into the image
 With ``smooth=True`` the shading call reads interpolated vertex normals in the place of the triangles' own: the corners'
 adjacency once per geometry, the crease-aware corner normals when the vertices move, and one pass per frame that mixes them
 at every primary hit.
+With ``fresnel=True`` the ``refract`` frame's glass both transmits and reflects: every glass hit sends the two rays, weighted
+by Schlick's share at the hit's angle, and one launch walks the whole ray tree of a pixel in the place of the level chain
+(DESIGN.md section 6.16).
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -51,7 +54,7 @@ import contextlib
 import numpy as np
 
 from . import (FLAG_STATIC_GEOMETRY, GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES,
-               MAX_FILTER_RADIUS, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
+               MAX_FILTER_RADIUS, MAX_FRESNEL_DEPTH, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -80,6 +83,36 @@ def check_refract(refract, reflect):
     if refract and not reflect:
         raise ValueError("refract=True needs reflect=True: the transmitted rays are levels of the bounce chain")
     return bool(refract)
+
+
+def check_fresnel(fresnel, fresnel_cut=0.0, reflect=False, refract=False, bounces=1, lights=None, reflect_lights=False,
+                  two_streams=False):
+    """The keywords of the Fresnel glass.  fresnel: False (off) or a number in (0, 1], the scale
+    of Schlick's share (True: 1.0); fresnel_cut: a number >= 0, the weight at or below which a child ray is dropped
+    (needs fresnel).  fresnel needs reflect=True and refract=True, bounces <= MAX_FRESNEL_DEPTH and the one-stream
+    Renderer's single-light frame (no setup.lights, no reflect_lights).  ValueError before anything is enqueued; returns
+    None (off) or (scale, cut)."""
+    num = (int, float, np.integer, np.floating)
+    if isinstance(fresnel_cut, (bool, np.bool_)) or not isinstance(fresnel_cut, num) or not float(np.float32(fresnel_cut)) >= 0.0:
+        raise ValueError("fresnel_cut must be a number >= 0, not %r" % (fresnel_cut,))
+    if fresnel is False or (isinstance(fresnel, np.bool_) and not fresnel):
+        if float(fresnel_cut) != 0.0:
+            raise ValueError("fresnel_cut needs fresnel: it drops the light children of a glass hit")
+        return None
+    if fresnel is True or isinstance(fresnel, np.bool_):
+        fresnel = 1.0
+    if not isinstance(fresnel, num) or not 0.0 < float(np.float32(fresnel)) <= 1.0:
+        raise ValueError("fresnel must be False, True or a number in (0, 1], not %r" % (fresnel,))
+    if not (reflect and refract):
+        raise ValueError("fresnel needs reflect=True and refract=True: it splits the glass hits of the refract frame")
+    if bounces > MAX_FRESNEL_DEPTH:
+        raise ValueError("fresnel needs bounces <= %d: the 2^bounces leaves of a pixel's ray tree are the lanes of one wave"
+                         % MAX_FRESNEL_DEPTH)
+    if lights is not None or reflect_lights:
+        raise ValueError("fresnel needs a single-light frame: the ray tree under setup.lights is not built")
+    if two_streams:
+        raise ValueError("fresnel needs the one-stream Renderer: the two-stream and banded frames keep the level chain")
+    return float(np.float32(fresnel)), float(np.float32(fresnel_cut))
 
 
 _CAMERA_KEYS = ("eye", "look", "up", "near", "far")
@@ -559,6 +592,16 @@ def trace_reflections(c, f, bounces, shadow_light=None, shadow_lights=None):
                     f.occlusion_rays, f.occlusion_active, shadow_lights, f.occluded_lights[j])
 
 
+def fresnel_pass(c, f, cam_pos, bounces, fresnel, shadow_light=None):
+    """The ray tree of every pixel with a level-1 ray, in the place of trace_reflections: one
+    fresnel_gather through c's uniform grid into f.f_acc.  fresnel: check_fresnel's (scale, cut); shadow_light
+    (reflect_shadows): the light camera's eye."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.fresnel_gather(uvalue, uspan, uoffset, f.d_verts, f.d_faces, f.rays, f.active, f.normal, f.t, f.dir, f.intersect_id,
+                     cam_pos, f.d_matidx, f.d_matlist, f.d_reflect, f.d_transmit, f.d_ior, f.num_materials, bounces,
+                     fresnel[0], fresnel[1], shadow_light, f.reflect_eps, f.f_acc)
+
+
 def ao_pass(c, f, cam_pos, dirs, radius, sets=None, have_rays=False):
     """Ambient occlusion's rays and walk: {origin, normal} of every primary hit, then the any-hit
     walk along the hemisphere directions `dirs` up to `radius` through c's uniform grid into f.ao_mask.  sets
@@ -704,12 +747,17 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
                 samples, f.area_mask)
 
 
-def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None, normal=None):
+def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None, normal=None,
+                fresnel=None):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
     depth shading with the occluded levels darkened, at every depth), then add_shadows.  glossy (glossy_pass' gl): the
     lobe's blend directly behind the shading call, where the mirror frame has its own.  normal (smooth_pass'): the normals
-    simpleShade | spotlight_shade read, f.normal unless given."""
-    if reflect and reflect_shadows:
+    simpleShade | spotlight_shade read, f.normal unless given.  fresnel (check_fresnel's pair): shade_fresnel over
+    fresnel_pass' sums in the place of the reflections' shading."""
+    if fresnel:
+        c.shade_fresnel(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.num_materials,
+                        f.f_acc)
+    elif reflect and reflect_shadows:
         c.shade_reflect_depth_occluded(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
                                        level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
                                        f.active_levels, f.hit_t_levels, f.hit_id_levels, f.occluded_levels)
@@ -826,6 +874,8 @@ class _Frame:
         # the rays are level 1's, the normals ao_rays'); the uploaded point tables by (glossy, glossy_sets) (_glossy_stage)
         self.glossy_sum = self.glossy_acc = None
         self._glossy_tables = {}
+        # fresnel: the ray trees' sums, four float32 words per pixel (_ensure_fresnel_buffers; the rays are level 1's)
+        self.f_acc = None
         # temporal: the previous frame's {o, n} and active flags (they change places with ao_rays / ao_active at the start
         # of every temporal frame), the temporal calls' outputs, the effects' states by name -- two histories, which of
         # them is read next, frames since the reset, the parameters they were accumulated under --, the 16 rotated tables
@@ -890,6 +940,12 @@ class _Frame:
         if self.occlusion_rays is None:
             self.occlusion_rays = t.empty(6 * N, dtype=t.float32, device=dev)
             self.occlusion_active = t.empty(N, dtype=t.int32, device=dev)
+
+    def _ensure_fresnel_buffers(self):
+        """f_acc [4 W*H] float32 and level 1's rays and active words, allocated on first use."""
+        self._ensure_reflect_buffers(1, False)
+        if self.f_acc is None:
+            self.f_acc = self.torch.zeros(4 * self.N, dtype=self.torch.float32, device=self.image.device)
 
     def _ensure_reflect_buffers(self, bounces=1, reflect_shadows=False):
         """rays_levels / active_levels / hit_t_levels / hit_id_levels: [depth, W*H(*6)], allocated once for the
@@ -1111,7 +1167,7 @@ class Renderer(_Frame, _Band):
                 gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True,
                 temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0, glossy_sets=1, glossy_filter=0,
                 glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True, smooth=False,
-                smooth_cos=0.5, smooth_signed=False):
+                smooth_cos=0.5, smooth_signed=False, fresnel=False, fresnel_cut=0.0):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows (needs reflect=True): the hits of every reflection level are shadowed (from the light
@@ -1186,6 +1242,13 @@ class Renderer(_Frame, _Band):
         (rotate_bunny, geometry_changed) or smooth_cos changed.  smooth_signed keeps the normals' signs where the primary
         tracer folds them into the positive octant.  Nothing else reads snormal: normal, the {origin, normal} of ao_rays
         and every mask and sum are the frame's without smooth.
+        fresnel (one-stream renderer, single-light frames with reflect=True and refract=True, bounces <= 6; ao, area, gi
+        and temporal compose as with the refract frame; no aa, glossy or smooth; False: off): Fresnel glass -- a glass hit
+        sends the transmitted ray AND the reflected ray, weighted (1 - F) and F of the material's transmit, F = fresnel
+        (True: 1.0; a number in (0, 1] scales it) times Schlick's share at the hit's angle; a pixel's rays form a tree
+        of depth `bounces` that one fresnel_gather walks in the place of the level chain, with reflect_shadows shadowing
+        every node from the light camera's eye; fresnel_cut (needs fresnel): children of a weight <= fresnel_cut are
+        dropped; f_acc holds the trees' sums and shade_fresnel writes the bytes.
         The keywords that shape an effect need the effect: gi_sets and gi_filter (need gi > 0, like every other gi_*
         keyword), aa_sets (needs aa > 0, like every other aa_* keyword), glossy_sets and glossy_filter (need glossy > 0, like
         every other glossy_* keyword), temporal_cos and temporal_plane (need temporal > 0), smooth_cos and smooth_signed (need
@@ -1211,6 +1274,9 @@ class Renderer(_Frame, _Band):
                                                                                        area_filter_cos, area_filter_plane)
         self.refract = check_refract(refract, reflect)
         bounces = check_bounces(bounces)
+        if fresnel is not False or fresnel_cut != 0.0:
+            fresnel = check_fresnel(fresnel, fresnel_cut, reflect, refract, bounces, getattr(setup, "lights", None),
+                                    reflect_lights, self.aux is not None)
         reflect_shadows = check_reflect_shadows(reflect_shadows, reflect)
         reflect_lights = check_reflect_lights(reflect_lights, reflect, getattr(setup, "lights", None))
         ao, ao_radius = check_ao(ao, ao_radius, self.aux is not None)
@@ -1236,7 +1302,9 @@ class Renderer(_Frame, _Band):
             aa = self._aa_stage(aa, shade)
         if glossy:
             glossy = self._glossy_stage(glossy, shade)
-        if reflect and shade:
+        if fresnel and shade:
+            self._ensure_fresnel_buffers()
+        elif reflect and shade:
             self._ensure_reflect_buffers(bounces, reflect_shadows)
         if self.aux is not None and shade:
             two_streams = self._display_two_streams_inline if self._inline else self._display_overlapped
@@ -1267,7 +1335,10 @@ class Renderer(_Frame, _Band):
         if reflect:
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
-            trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
+            if fresnel:
+                fresnel_pass(ctx, self, self.cam_pos, bounces, fresnel, lcam.worldori[:3] if reflect_shadows else None)
+            else:
+                trace_reflections(ctx, self, bounces, lcam.worldori[:3] if reflect_shadows else None)
         elif glossy:
             # (reflect_rays although reflect=False: the lobe's origins and mirror directions are level 1's rays)
             ctx.reflect_rays(self.cam_pos, self.t, self.dir, self.intersect_id, self.d_matidx, self.d_reflect, self.num_materials,
@@ -1297,7 +1368,7 @@ class Renderer(_Frame, _Band):
             self._smooth_stage(smooth[0])
             normal = smooth_pass(ctx, self, self.cam_pos, smooth[1])
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows,
-                    glossy or None, normal)
+                    glossy or None, normal, fresnel or None)
         if area and tp:
             area_shade_temporal(ctx, self, tp, area_t)
         elif area and area_filter:
@@ -1853,8 +1924,10 @@ class BandedRenderer(_Frame):
                 gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
                 aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0,
                 glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
-                glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False):
+                glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False, fresnel=False, fresnel_cut=0.0):
         check_smooth(smooth, smooth_cos, smooth_signed, False, False, 0, 0, False, True)  # raises with smooth=True
+        check_fresnel(fresnel, fresnel_cut, reflect, refract, 1, getattr(setup, "lights", None), False,
+                      True)  # raises with fresnel: the tree's gather is not built here
         check_glossy(glossy, glossy_sets, glossy_filter, glossy_filter_cos, glossy_filter_plane, glossy_radius, glossy_shadows,
                      reflect, refract, aa, temporal, getattr(setup, "lights", None), False, True)  # raises with glossy > 0
         check_temporal(temporal, temporal_cos, temporal_plane, True, getattr(setup, "lights", None), False,
