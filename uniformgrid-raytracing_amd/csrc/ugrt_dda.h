@@ -24,6 +24,10 @@ static inline DGrid ugrt_dgrid_of(const Grid &G)
 	return g;
 }
 
+// the one k_dda_prepare launch of every call that walks the grid from a ray list (ugrt_dda.hip)
+int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
+		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out);
+
 // Segments of the window kernel's long ray groups (ugrt_dda_walk.hip, "split walks"); all pointers null: no splitting
 #define WK_FBW 32      // windows of a group whose job counts are remembered (one byte each; later windows share the last)
 #define WK_MAXSEG 4    // segments a group is cut into at most

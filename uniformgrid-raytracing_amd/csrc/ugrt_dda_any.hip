@@ -25,14 +25,10 @@
 // set_w x set_h tile of the image: the sets lie in device memory, a workgroup copies them to LDS once.
 // ugrt_trace_dda_any_hemi_sets is the hemisphere walk in that index space: the S directions of a
 // pixel in neighbouring lanes, one set of local directions per pixel of the tile, the word stored whole from one ballot.
-#include "ugrt_dda.h"
+#include "ugrt_gather.h" // (d_stage_table, d_ticket_draw)
 #include <type_traits>
 
 #define ANY_AHEAD 8 // steps planned (and looked up in the bitmap) per window
-
-// ugrt_dda.hip
-int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
-		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out);
 
 // What the rays of a launch aim at.  AnyRays: the rays as they are stored, up to t_max (ugrt_trace_dda_any).  AnyLights: from
 // the stored origins towards num_lights points (ugrt_trace_dda_any_lights): the index space is
@@ -164,16 +160,7 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 		t_max = aim;
 	// AnyArea: the samples in LDS
 	if constexpr (Aim::sets) {
-		// 3 * K * S floats: float4 per lane while four are left (a 16-byte aligned table), then single floats
-		const u32 total = 3u * (u32)aim.count * aim.set_w * aim.set_h;
-		u32 done = 0u;
-		if (((size_t)aim.pos & 15u) == 0u) {
-			for (u32 i = 4u * (u32)lane; i + 4u <= total; i += 256u)
-				*(float4 *)(s_sets_pos + i) = *(const float4 *)(aim.pos + i);
-			done = total & ~3u;
-		}
-		for (u32 i = done + (u32)lane; i < total; i += 64u)
-			s_sets_pos[i] = aim.pos[i];
+		d_stage_table(s_sets_pos, aim.pos, 3u * (u32)aim.count * aim.set_w * aim.set_h, lane); // 3 * K * S floats
 		__syncthreads();
 	} else if constexpr (Aim::area) {
 		const u32 S = (u32)aim.count;
@@ -342,9 +329,7 @@ __global__ __launch_bounds__(64) void k_trace_dda_any(DGrid g, const u32 *__rest
 			else
 				occluded[p] = 1;
 		}
-		if (lane == 0)
-			grp = gridDim.x + atomicAdd(ticket, 1u);
-		grp = (u32)__builtin_amdgcn_readfirstlane((int)grp);
+		grp = d_ticket_draw(lane, grp, ticket);
 	}
 }
 

@@ -14,14 +14,10 @@
 //   * the owner adds its nodes' terms front to back from +0; the leaves' sums are added pairwise from the deepest bit up
 //     (step j: leaf b < 2^j takes leaf b + 2^j) and leaf 0 stores the pixel's 16 bytes.  No atomics on the sums;
 //   * the words that only the code between the walks reads (the material arrays, the primary arrays, the view rotation,
-//     the lights) are staged in LDS (ugrt_gi.hip's reason: kept in scalar registers over both walks they spill);
+//     the lights) are staged in LDS (ugrt_gather.h's reason: kept in scalar registers over both walks they spill);
 //   * groups of pixels are drawn from a ticket.
 // ugrt_fresnel_shade (ugrt_shade.hip) turns the sums into the image's bytes.
-#include "ugrt_walks.h"
-
-// ugrt_dda.hip
-int ugrt_dda_prepare(ugrt_ctx *ctx, const DGrid &g, const int *d_active, float *d_hit_t, int *d_hit_id, const u32 *d_span,
-		     bool with_bitmap, u32 *chunk, u32 **list_out, u32 **dcount_out);
+#include "ugrt_gather.h" // (gather_launch, d_ticket_draw)
 
 struct FresnelArg {
 	const float *t_value, *ray_dir, *normal; // the primary hits
@@ -79,9 +75,9 @@ __global__ __launch_bounds__(64) void k_fresnel_gather(DGrid g, const u32 *__res
 						       const u32 *__restrict__ offset, const u32 *__restrict__ bitmap,
 						       const float *__restrict__ verts, const int *__restrict__ tris,
 						       const float4 *__restrict__ rec, const float *__restrict__ rays,
-						       const u32 *__restrict__ list, const u32 *__restrict__ count_p,
-						       const FresnelArg a, const CamBlock cam, float *__restrict__ acc_out, u32 PPW,
-						       u32 COOP, u32 *__restrict__ ticket, unsigned long long *__restrict__ nodes)
+						       const u32 *__restrict__ list, const u32 *__restrict__ count_p, u32 PPW,
+						       u32 COOP, const FresnelArg a, const CamBlock cam, float *__restrict__ acc_out,
+						       u32 *__restrict__ ticket, unsigned long long *__restrict__ nodes)
 {
 	__shared__ FresnelLate s_late;
 	const int lane = threadIdx.x;
@@ -262,9 +258,7 @@ __global__ __launch_bounds__(64) void k_fresnel_gather(DGrid g, const u32 *__res
 		}
 		if (inb && b == 0u)
 			*(float4 *)(S0.acc_out + 4u * (size_t)p) = make_float4(acc[0], acc[1], acc[2], 1.0f);
-		if (lane == 0)
-			grp = gridDim.x + atomicAdd(S0.ticket, 1u);
-		grp = (u32)__builtin_amdgcn_readfirstlane((int)grp);
+		grp = d_ticket_draw(lane, grp, S0.ticket);
 	}
 	if (lane == 0 && walked != 0u)
 		atomicAdd(nodes, (unsigned long long)walked);
@@ -293,12 +287,6 @@ extern "C" int ugrt_fresnel_gather(ugrt_ctx *ctx, const unsigned *d_value_list, 
 		return ugrt_fail(UGRT_EINVAL, "fresnel_gather: num_materials %d is less than 1", num_materials);
 	if (((size_t)d_acc & 15u) != 0u)
 		return ugrt_fail(UGRT_EINVAL, "fresnel_gather: d_acc is not 16-byte aligned");
-	Grid &G = ctx->grid[UGRT_GRID_UNIFORM];
-	if (!G.valid)
-		return ugrt_fail(UGRT_EINVAL, "trace_dda: build the uniform grid first (it defines the cell geometry)");
-	UGRT_HIP(hipSetDevice(ctx->device));
-	const DGrid g = ugrt_dgrid_of(G);
-	const float4 *rec = ugrt_trirec_of(ctx, d_vertlist, d_trilist);
 	FresnelArg a = {};
 	a.t_value = d_t_value;
 	a.ray_dir = d_ray_dir;
@@ -317,37 +305,15 @@ extern "C" int ugrt_fresnel_gather(ugrt_ctx *ctx, const unsigned *d_value_list, 
 	for (int k = 0; k < 3; k++)
 		a.light[k] = shadow_light ? shadow_light[k] : 0.0f;
 	a.eps = eps;
-	// launch shape (ugrt_ctx_set_option; no effect on results): ugrt_trace_dda_any_area's, a pixel taking 2^depth lanes
-	const u32 L = ctx->opt[UGRT_OPT_ANY_RPW] > 0 ? (ctx->opt[UGRT_OPT_ANY_RPW] < 64 ? (u32)ctx->opt[UGRT_OPT_ANY_RPW] : 64u) : 64u;
-	const u32 PPW = (L >> depth) > 0u ? L >> depth : 1u;
-	const u32 COOP = ctx->opt[UGRT_OPT_ANY_COOP] > 0 ? (u32)ctx->opt[UGRT_OPT_ANY_COOP] : 8u;
-	// One prepare launch and one ray list, as ugrt_glossy_gather takes them: the form that writes no hit defaults is handed
-	// the band's own words to clear one int per pixel into, and the whole band is cleared behind it, in stream order.
-	u32 *list, *dcount;
+	// a pixel takes 2^depth lanes; the node counter is cleared with the band
+	static const GatherKernel<FresnelArg, CamBlock, float *, u32 *, unsigned long long *> kernel[2][2] = {
+		{ k_fresnel_gather<false, false>, k_fresnel_gather<false, true> },
+		{ k_fresnel_gather<true, false>, k_fresnel_gather<true, true> },
+	};
 	unsigned long long *nodes = (unsigned long long *)(ctx->d_small + UGRT_DSMALL_FRESNEL);
-	ugrt_prof_begin(ctx, UGRT_ST_WORKLIST);
-	const int rc = ugrt_dda_prepare(ctx, g, d_active, nullptr, (int *)d_acc + (size_t)3 * (size_t)ctx->p0, d_span, true, nullptr,
-					&list, &dcount);
-	hipError_t he = hipSuccess;
-	if (!rc)
-		he = hipMemsetAsync(d_acc + (size_t)4 * (size_t)ctx->p0, 0, (size_t)ctx->npix * 16u, ctx->stream);
-	if (!rc && he == hipSuccess)
-		he = hipMemsetAsync(nodes, 0, 8, ctx->stream);
-	ugrt_prof_end(ctx, UGRT_ST_WORKLIST);
-	if (rc)
+	if (int rc = gather_launch({ ctx, d_value_list, d_span, d_offset, d_vertlist, d_trilist, d_rays, d_active, d_acc }, 1u << depth, 0,
+				   kernel, shadow_light != nullptr, nodes, a, ctx->cam, d_acc, ctx->d_small + UGRT_DSMALL_TICKET, nodes))
 		return rc;
-	UGRT_HIP(he);
-	int blocks = launch_blocks_for((u32)ctx->npix / PPW + 1u);
-	if (ctx->opt[UGRT_OPT_DDA_BLOCKS] > 0 && blocks > ctx->opt[UGRT_OPT_DDA_BLOCKS])
-		blocks = ctx->opt[UGRT_OPT_DDA_BLOCKS];
-	const auto kernel = shadow_light ? (rec ? k_fresnel_gather<true, true> : k_fresnel_gather<false, true>)
-					 : (rec ? k_fresnel_gather<true, false> : k_fresnel_gather<false, false>);
-	ugrt_prof_begin(ctx, UGRT_ST_TRACE_DDA);
-	hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, ctx->stream, g, d_value_list, d_span, d_offset,
-			   (const u32 *)ctx->ubitmap.p, d_vertlist, d_trilist, rec, d_rays, (const u32 *)list, (const u32 *)dcount, a,
-			   ctx->cam, d_acc, PPW, COOP, ctx->d_small + UGRT_DSMALL_TICKET, nodes);
-	ugrt_prof_end(ctx, UGRT_ST_TRACE_DDA);
-	UGRT_HIP(hipGetLastError());
 	ctx->fresnel_gathers++;
 	return UGRT_OK;
 }

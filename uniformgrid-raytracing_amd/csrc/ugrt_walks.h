@@ -1,6 +1,6 @@
 // ugrt_walks.h -- the two walks through the uniform grid of the kernels that give a pixel S rays in neighbouring lanes and
-// keep each ray, its hit and what follows from it in registers (ugrt_gi.hip: the indirect light's gather; ugrt_aa.hip: the
-// sub-pixel eye rays).  One ray per lane; every lane of the wave calls a walk, a lane without a ray only serves the
+// keep each ray, its hit and what follows from it in registers (ugrt_gather.h: k_pixel_gather, the body of the indirect
+// light's, the glossy lobe's and the sub-pixel eye rays' gathers; ugrt_fresnel.hip: the tree).  One ray per lane; every lane of the wave calls a walk, a lane without a ray only serves the
 // cooperative rounds.  The windowed plan (WALK_AHEAD steps at a time) and the bitmap look-up in front of the headers are
 // the any-hit kernel's (ugrt_dda_any.hip).
 #ifndef UGRT_WALKS_H
