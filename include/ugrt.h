@@ -1058,6 +1058,47 @@ int ugrt_aa_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *
  * UGRT_EINVAL and nothing is enqueued. */
 int ugrt_aa_resolve(ugrt_ctx *ctx, unsigned char *d_img, const unsigned *d_sum, int num_samples);
 
+/* ---- device: depth of field, thin-lens eye rays on the pixels whose blur matters ----
+ * The frame's camera is a pinhole.  ugrt_dof_pixels finds the pixels that a circle of confusion reaches, ugrt_dof_gather
+ * sends num_samples rays from points of a lens through each of them and shades every sample as the frame shades a primary
+ * hit, ugrt_aa_resolve puts the mean into the image.  A sample from the lens's centre IS ugrt_aa_gather's sample.  Per
+ * frame: the primary pass and the shadow stage, ugrt_dof_pixels, the uniform grid, ugrt_dof_gather, the shading calls,
+ * ugrt_aa_resolve.  All arithmetic is fp32 without contraction, in the stated order, or 32-bit integer. */
+#define UGRT_MAX_DOF_WINDOW 8 /* radius of ugrt_dof_pixels */
+/* The lens flags, for the context's band; called BEFORE the frame's shading call, while d_intersect_id holds triangle ids.
+ * axis is HOST memory, float[3]: A, the unit view axis.  For a pixel q with hit(q) = d_t_value[q] > 0 &&
+ * d_intersect_id[q] >= 0:
+ *   z_q = d_t_value[q] * ((dir_q0*A_0 + dir_q1*A_1) + dir_q2*A_2), dir_q = d_ray_dir[3q ..];
+ *   coc_q = (coc_scale * fabsf(z_q - focus)) / z_q for a hit with z_q > 0, and 0 otherwise (a miss, a NaN t).
+ * d_flags[p] = 1 when some q inside the image (rows outside the band are read) with m = max(|dx|, |dy|) <= radius, p
+ * itself included, has coc_q >= coc_min and coc_q >= (float)m; otherwise 0 (a coc_q that is a NaN meets neither).
+ * Pixels outside the band are not written.  coc_scale is the caller's: lens radius * focal length in pixels / focus.
+ * Stage UGRT_ST_SHADE, one launch.  A NaN in axis, focus, coc_scale or coc_min, radius outside 0..UGRT_MAX_DOF_WINDOW or a
+ * null argument: UGRT_EINVAL (the message names the argument) and nothing is enqueued. */
+int ugrt_dof_pixels(ugrt_ctx *ctx, const float *d_t_value, const float *d_ray_dir, const int *d_intersect_id,
+		    const float *axis, float focus, float coc_scale, float coc_min, int radius, int *d_flags);
+/* The lens rays of the pixels of the band with d_flags[p] != 0 (ugrt_dof_pixels', or any caller's).  The arguments are
+ * ugrt_aa_gather's, with d_flags where d_edge stands, and lens, HOST memory, float[10]: lens[0..2] = U and lens[3..5] = V,
+ * world vectors along the lens's two axes whose length is the lens radius; lens[6..8] = A, the unit view axis; lens[9] =
+ * F, the focus distance along A.  d_table is DEVICE memory, [set_w * set_h][num_samples][4] floats (sx, sy, lu, lv);
+ * sample s of pixel p = (col, row) reads entry k(p) * num_samples + s, k(p) as in ugrt_aa_gather, and is formed in this
+ * order:
+ *   sx, sy clamped as ugrt_aa_gather clamps them; lu, lv each clamped to [-1, 1], a NaN counts as 0;
+ *   d0 = ugrt_aa_gather's direction at ((float)col + sx, (float)row + sy), UGRT_FLAG_STRICT_TEXTURE included;
+ *   c = (d0_0*A_0 + d0_1*A_1) + d0_2*A_2;  s_f = F / c;  L_k = lu*U_k + lv*V_k;
+ *   !(c > 0): the pinhole ray, o = eye, d = d0;  otherwise o_k = eye_k + L_k, d_k = d0_k - L_k / s_f.
+ * d is not normalised again: t keeps the pinhole ray's scale, and all lens rays of one image point meet on the plane
+ * A . (P - eye) = F.  With lu = lv = 0, or U = V = 0, the ray is ugrt_aa_gather's.  Everything behind the ray is
+ * ugrt_aa_gather's on {o, d}: the closest hit, the depth gate under the eye's MVP at P = o + t * d, the primary hit's
+ * shading at P, the occlusion ray towards shadow_light and the / 3, d_sum's four words per pixel, the zeros of the band's
+ * other pixels, the index space, the options and the stages.  Every case that is UGRT_EINVAL for ugrt_aa_gather, a null
+ * lens, a U, V or A that is not finite, an F that is not finite or F <= 0: UGRT_EINVAL (the message names the argument)
+ * and nothing is enqueued. */
+int ugrt_dof_gather(ugrt_ctx *ctx, const unsigned *d_value_list, const unsigned *d_span, const unsigned *d_offset,
+		    const float *d_vertlist, const int *d_trilist, const float *eye_camcoords, const float *lens,
+		    const int *d_flags, int num_samples, int set_w, int set_h, const float *d_table, const int *d_mat_idx,
+		    const float *d_mat_list, int num_materials, const float *shadow_light, float eps, unsigned *d_sum);
+
 /* ---- device: temporal accumulation, DESIGN.md section 6.12 ----
  * A sequence of frames gives frame f a different sample set and carries a per-pixel running mean of the share of open
  * rays (ambient occlusion, area light) or of the indirect light's colour from frame to frame: after N frames a pixel has

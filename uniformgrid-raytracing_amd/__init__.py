@@ -63,6 +63,7 @@ MAX_FILTER_RADIUS = 8  # UGRT_MAX_FILTER_RADIUS
 MAX_AO_SET_TILE = 4  # UGRT_MAX_AO_SET_TILE
 MAX_AO_SET_DIRS = 512  # UGRT_MAX_AO_SET_DIRS
 MAX_AA_SAMPLES = 32  # UGRT_MAX_AA_SAMPLES
+MAX_DOF_WINDOW = 8  # UGRT_MAX_DOF_WINDOW
 MAX_TEMPORAL_FRAMES = 64  # UGRT_MAX_TEMPORAL_FRAMES
 MAX_GLOSSY_SAMPLES = 32  # UGRT_MAX_GLOSSY_SAMPLES
 MAX_GLOSSY_SPREAD = 1.0  # UGRT_MAX_GLOSSY_SPREAD
@@ -210,6 +211,8 @@ PROTOTYPES = {
     "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
     "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),
+    "ugrt_dof_pixels": (C.c_int, [_P] * 4 + [_F3, C.c_float, C.c_float, C.c_float, C.c_int, _P]),
+    "ugrt_dof_gather": (C.c_int, [_P] * 6 + [_F3, _F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_temporal_visibility": (C.c_int, [_P, _P, C.c_int, _P, _P, _F3, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P]),
     "ugrt_temporal_gi": (C.c_int, [_P, _P, C.c_int, _P, _P, _F3, _P, _P, _P, C.c_int, C.c_float, C.c_float, _P, _P]),
     "ugrt_animate": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_float]),

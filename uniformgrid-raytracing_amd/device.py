@@ -588,6 +588,28 @@ class Context:
         (sums[4p + k] + num_samples // 2) // num_samples; every other pixel stays."""
         check(lib.ugrt_aa_resolve(self._h, _ptr(img), _ptr(sums), int(num_samples)))
 
+    # -- depth of field (DESIGN.md section 6.17) --------------------------------
+    def dof_pixels(self, t, dirs, ids, axis, focus, coc_scale, coc_min, radius, flags):
+        """Before the shading call (ids holds triangle ids): flags[p] = 1 where the circle of confusion of a pixel q within
+        `radius` pixels of p (p included) is at least coc_min and at least max(|dx|, |dy|) wide; 0 elsewhere.  The circle of
+        a hit at depth z = t * (dir . axis) > 0 is coc_scale * |z - focus| / z, of every other pixel 0.  axis: three host
+        floats, the unit view axis; flags: int32 [W * H]."""
+        check(lib.ugrt_dof_pixels(self._h, _ptr(t), _ptr(dirs), _ptr(ids), None if axis is None else _f3(axis), focus,
+                                  coc_scale, coc_min, int(radius), _ptr(flags)))
+
+    def dof_gather(self, value, span, offset, verts, faces, eye_camcoords, lens, flags, num_samples, set_w, set_h, table,
+                   mat_idx, mat_list, num_materials, shadow_light, eps, sums):
+        """The lens rays of the pixels with flags[p] != 0: aa_gather with a table of (sx, sy, lu, lv) entries (the DEVICE
+        table [set_w * set_h, num_samples, 4]: scenes.lens_sample_sets, uploaded) and lens, ten host floats: U[3] and V[3],
+        the lens's axes with the lens radius as their length, A[3], the unit view axis, and F, the focus distance along
+        A.  A sample starts at eye + lu U + lv V and meets the pinhole ray through (col + sx, row + sy) on the plane
+        A . (P - eye) = F; everything else, sums included, is aa_gather's."""
+        light = None if shadow_light is None else _points([shadow_light])[1]
+        check(lib.ugrt_dof_gather(self._h, _ptr(value), _ptr(span), _ptr(offset), _ptr(verts), _ptr(faces),
+                                  None if eye_camcoords is None else _f3(eye_camcoords), None if lens is None else _f3(lens),
+                                  _ptr(flags), int(num_samples), int(set_w), int(set_h), _ptr(table), _ptr(mat_idx),
+                                  _ptr(mat_list), int(num_materials), light, eps, _ptr(sums)))
+
     # -- temporal accumulation (DESIGN.md section 6.12) -------------------------
     def temporal_visibility(self, vis, num_bits, orays, oactive, prev_camcoords, prev_orays, prev_oactive, hist_in, max_frames,
                             normal_cos, plane_tol, hist_out, vis_out):

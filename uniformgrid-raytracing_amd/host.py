@@ -147,6 +147,24 @@ class Camera:
         check(lib.ugrt_camera_direction_table(self.s.camcoords, t))
         return np.array(t[:], dtype=np.float32)
 
+    def lens(self, aperture, focus, height):
+        """The thin lens of this camera: (lens, coc_scale) for Context.dof_gather and
+        Context.dof_pixels.  With c the eye, l the look-at point and u the up vector, in float64:
+        A = (l - c) / |l - c|, R = (A x u) / |A x u|, T = R x A; lens = float32 (aperture R, aperture T, A, F) with
+        F = focus, or (l - c) . A = |l - c| for focus None; coc_scale = aperture * f / F, f = (height / 2) /
+        tan(fovy / 2) the focal length in pixels of a frame `height` pixels high."""
+        c, l, u = (np.asarray(v, np.float64) for v in (self.c, self.l, self.u))
+        A = l - c
+        dist = float(np.sqrt((A * A).sum()))
+        A = A / dist
+        R = np.cross(A, u)
+        R = R / np.sqrt((R * R).sum())
+        T = np.cross(R, A)
+        F = dist if focus is None else float(focus)
+        f = 0.5 * float(height) / np.tan(np.radians(self.fovy) / 2.0)
+        lens = np.concatenate([float(aperture) * R, float(aperture) * T, A, [F]]).astype(np.float32)
+        return lens, float(np.float32(float(aperture) * f / F))
+
 
 def write_ppm(path, rgb):
     """writePPM, per_app_funcs.h:39.  rgb: uint8 array [H, W, 3], row 0 = bottom of the view."""

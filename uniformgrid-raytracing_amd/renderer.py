@@ -44,6 +44,9 @@ at every primary hit.
 With ``fresnel=True`` the ``refract`` frame's glass both transmits and reflects: every glass hit sends the two rays, weighted
 by Schlick's share at the hit's angle, and one launch walks the whole ray tree of a pixel in the place of the level chain
 (DESIGN.md section 6.16).
+With ``dof=S`` the one-stream single-light plain frame is seen through a thin lens of radius ``dof_aperture`` focused at
+``dof_focus``: the pixels that a circle of confusion reaches send S rays from points of the lens through the uniform grid
+and take the mean of their colours.
 
 Each stage is one function below, shared by the four frame paths (one stream, two streams with a helper thread, two
 streams from one host thread, one frame in bands); the paths differ only in the context and stream a stage runs on
@@ -54,7 +57,7 @@ import contextlib
 import numpy as np
 
 from . import (FLAG_STATIC_GEOMETRY, GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES,
-               MAX_FILTER_RADIUS, MAX_FRESNEL_DEPTH, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
+               MAX_DOF_WINDOW, MAX_FILTER_RADIUS, MAX_FRESNEL_DEPTH, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -328,6 +331,67 @@ def check_aa(aa, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True, reflect=
         raise ValueError("aa needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
                          "side context")
     return int(aa), int(aa_sets), float(np.float32(aa_cos)), aa_plane, bool(aa_shadows)
+
+
+def check_dof(dof, dof_aperture=0.0, dof_focus=None, dof_sets=1, dof_min=0.5, dof_window=4, dof_shadows=True, aa=0,
+              reflect=False, refract=False, fresnel=False, glossy=0, gi=0, area=0, smooth=False, temporal=0, frame_cnt=1,
+              lights=None, reflect_lights=False, two_streams=False):
+    """The keywords of the depth of field.  dof: an integer 0..MAX_AA_SAMPLES (0: off, and every
+    other dof_* keyword must be at its default); dof_aperture: the lens radius, a finite number >= 0; dof_focus: None (the
+    distance to the camera's look-at point) or a finite number > 0; dof_sets: 1, 4 or 16; dof_min: a finite number > 0,
+    the smallest circle of confusion in pixels that is traced; dof_window: an integer 0..MAX_DOF_WINDOW, how far a
+    neighbour's circle is followed; dof_shadows: a bool.  dof > 0 needs the one-stream Renderer's single-light plain frame
+    with frame_cnt < 2 and no aa, reflect, refract, fresnel, glossy, gi, area, smooth or temporal.  ValueError before
+    anything is enqueued.  Returns None (off) or (dof, dof_sets, aperture, focus or None, min, window, shadows)."""
+    number = (int, float, np.integer, np.floating)
+
+    def real(v):
+        return not isinstance(v, (bool, np.bool_)) and isinstance(v, number) and bool(np.isfinite(np.float32(v)))
+
+    if isinstance(dof, (bool, np.bool_)) or not isinstance(dof, (int, np.integer)) or not 0 <= dof <= MAX_AA_SAMPLES:
+        raise ValueError("dof must be an integer in 0..%d, not %r" % (MAX_AA_SAMPLES, dof))
+    if not real(dof_aperture) or float(np.float32(dof_aperture)) < 0:
+        raise ValueError("dof_aperture must be a finite number >= 0, not %r" % (dof_aperture,))
+    if dof_focus is not None and (not real(dof_focus) or not float(np.float32(dof_focus)) > 0):
+        raise ValueError("dof_focus must be None or a finite number > 0, not %r" % (dof_focus,))
+    if isinstance(dof_sets, (bool, np.bool_)) or not isinstance(dof_sets, (int, np.integer)) or int(dof_sets) not in AREA_SET_TILES:
+        raise ValueError("dof_sets must be 1, 4 or 16, not %r" % (dof_sets,))
+    if not real(dof_min) or not float(np.float32(dof_min)) > 0:
+        raise ValueError("dof_min must be a finite number > 0, not %r" % (dof_min,))
+    if isinstance(dof_window, (bool, np.bool_)) or not isinstance(dof_window, (int, np.integer)) or \
+            not 0 <= dof_window <= MAX_DOF_WINDOW:
+        raise ValueError("dof_window must be an integer in 0..%d, not %r" % (MAX_DOF_WINDOW, dof_window))
+    if not isinstance(dof_shadows, (bool, np.bool_)):
+        raise ValueError("dof_shadows must be True or False, not %r" % (dof_shadows,))
+    if dof == 0:
+        if float(np.float32(dof_aperture)) != 0.0 or dof_focus is not None or dof_sets != 1 or \
+                float(np.float32(dof_min)) != 0.5 or dof_window != 4 or not dof_shadows:
+            raise ValueError("dof_aperture, dof_focus, dof_sets, dof_min, dof_window and dof_shadows need dof > 0: they shape "
+                             "the depth of field")
+        return None
+    if aa:
+        raise ValueError("dof needs aa=0: the lens samples already carry sub-pixel offsets")
+    if reflect or refract or fresnel or reflect_lights:
+        raise ValueError("dof needs reflect=False, refract=False and fresnel=False: the lens samples send no secondary rays")
+    if glossy:
+        raise ValueError("dof needs glossy=0: the lens samples send no lobe")
+    if gi:
+        raise ValueError("dof needs gi=0: the lens samples gather no indirect light")
+    if area:
+        raise ValueError("dof needs area=0: the lens samples are not shaded under an area light")
+    if smooth:
+        raise ValueError("dof needs smooth=False: the lens samples shade with the flat normal")
+    if temporal:
+        raise ValueError("dof needs temporal=0: the lens samples are not accumulated over frames")
+    if isinstance(frame_cnt, (bool, np.bool_)) or not isinstance(frame_cnt, (int, np.integer)) or frame_cnt >= 2:
+        raise ValueError("dof needs frame_cnt < 2: the samples are shaded as the plain frame shades, not under the spot light")
+    if lights is not None:
+        raise ValueError("dof needs a single-light frame: the samples under setup.lights are not built")
+    if two_streams:
+        raise ValueError("dof needs the one-stream Renderer: the two-stream and banded frames keep the uniform grid on a "
+                         "side context")
+    return (int(dof), int(dof_sets), float(np.float32(dof_aperture)), None if dof_focus is None else float(np.float32(dof_focus)),
+            float(np.float32(dof_min)), int(dof_window), bool(dof_shadows))
 
 
 def check_temporal(temporal, temporal_cos=0.9, temporal_plane=None, effects=False, lights=None, reflect_lights=False,
@@ -728,6 +792,22 @@ def aa_pass(c, f, eye_camcoords, aa, shadow_light):
                 f.d_matidx, f.d_matlist, f.num_materials, shadow_light, f.reflect_eps, f.aa_sum)
 
 
+def dof_pixels(c, f, dof):
+    """The depth of field's pixel flags into f.dof_flag, behind the shadow stage and before the
+    shading call that rewrites the ids.  dof: Renderer._dof_stage's (S, (set_w, set_h), table, lens, coc_scale, min,
+    window, shadows)."""
+    lens = dof[3]
+    c.dof_pixels(f.t, f.dir, f.intersect_id, lens[6:9], float(lens[9]), dof[4], dof[5], dof[6], f.dof_flag)
+
+
+def dof_pass(c, f, eye_camcoords, dof, shadow_light):
+    """The lens rays of the flagged pixels through c's uniform grid into f.dof_sum (dof_pixels' dof); eye_camcoords and
+    shadow_light as in aa_pass."""
+    uvalue, uspan, uoffset, _ = c.grid_ptrs(GRID_UNIFORM)
+    c.dof_gather(uvalue, uspan, uoffset, f.d_verts, f.d_faces, eye_camcoords, dof[3], f.dof_flag, dof[0], dof[1][0], dof[1][1],
+                 dof[2], f.d_matidx, f.d_matlist, f.num_materials, shadow_light, f.reflect_eps, f.dof_sum)
+
+
 def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
     """An area light's shadow rays and walk: the origin of every primary hit (ao_rays, into the AO
     buffers), then the any-hit walk towards the points `samples` of the light's disk through c's uniform grid into
@@ -870,6 +950,10 @@ class _Frame:
         # offset tables by (aa, aa_sets)
         self.aa_edge = self.aa_sum = None
         self._aa_set_tables = {}
+        # dof: the lens flags and the byte sums of the pixels seen through the lens, four words per pixel (_dof_stage); the
+        # uploaded sample tables by (dof, dof_sets)
+        self.dof_flag = self.dof_sum = None
+        self._dof_set_tables = {}
         # glossy: the byte sums of the lobe's samples and the gather's sums, four words per pixel (_ensure_glossy_buffers;
         # the rays are level 1's, the normals ao_rays'); the uploaded point tables by (glossy, glossy_sets) (_glossy_stage)
         self.glossy_sum = self.glossy_acc = None
@@ -1167,7 +1251,8 @@ class Renderer(_Frame, _Band):
                 gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1, aa_cos=0.9, aa_plane=None, aa_shadows=True,
                 temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0, glossy_sets=1, glossy_filter=0,
                 glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True, smooth=False,
-                smooth_cos=0.5, smooth_signed=False, fresnel=False, fresnel_cut=0.0):
+                smooth_cos=0.5, smooth_signed=False, dof=0, dof_aperture=0.0, dof_focus=None, dof_sets=1, dof_min=0.5,
+                dof_window=4, dof_shadows=True, fresnel=False, fresnel_cut=0.0):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows (needs reflect=True): the hits of every reflection level are shadowed (from the light
@@ -1249,7 +1334,17 @@ class Renderer(_Frame, _Band):
         of depth `bounces` that one fresnel_gather walks in the place of the level chain, with reflect_shadows shadowing
         every node from the light camera's eye; fresnel_cut (needs fresnel): children of a weight <= fresnel_cut are
         dropped; f_acc holds the trees' sums and shade_fresnel writes the bytes.
-        The keywords that shape an effect need the effect: gi_sets and gi_filter (need gi > 0, like every other gi_*
+        dof (one-stream renderer, the single-light plain frame: frame_cnt < 2, no setup.lights, aa, reflect, refract,
+        fresnel, glossy, gi, area, smooth or temporal; ao composes; 0: off): depth of field -- the camera is a thin lens
+        of radius dof_aperture (world units) around the eye, perpendicular to the view, focused at the distance dof_focus
+        along the view (None: the distance to the camera's look-at point).  A pixel is seen through the lens where its own
+        circle of confusion, or that of a pixel at most dof_window = 0..8 pixels away which reaches it, is at least dof_min
+        pixels wide (dof_flag); it sends dof = 1..32 rays (scenes.lens_sample_sets(dof, dof_sets), uploaded once per
+        (dof, dof_sets)) from points of the lens through the uniform grid, each shaded as the frame shades a primary hit
+        and, with shadows and dof_shadows, shadowed from the light camera's eye; dof_sum holds the bytes' sums and their
+        mean replaces the pixel where aa_resolve stands in the order below.  dof_aperture=0 flags nothing (DESIGN.md
+        section 6.17).
+        The keywords that shape an effect need the effect: dof_* (need dof > 0), gi_sets and gi_filter (need gi > 0, like every other gi_*
         keyword), aa_sets (needs aa > 0, like every other aa_* keyword), glossy_sets and glossy_filter (need glossy > 0, like
         every other glossy_* keyword), temporal_cos and temporal_plane (need temporal > 0), smooth_cos and smooth_signed (need
         smooth=True).
@@ -1267,6 +1362,13 @@ class Renderer(_Frame, _Band):
                               self.aux is not None)
         aa = check_aa(aa, aa_sets, aa_cos, aa_plane, aa_shadows, reflect, frame_cnt, getattr(setup, "lights", None), area, gi,
                       reflect_lights, self.aux is not None)
+        if dof != 0 or dof_aperture != 0.0 or dof_focus is not None or dof_sets != 1 or dof_min != 0.5 or dof_window != 4 \
+                or dof_shadows is not True:
+            dof = check_dof(dof, dof_aperture, dof_focus, dof_sets, dof_min, dof_window, dof_shadows, aa, reflect, refract,
+                            fresnel is not False, glossy, gi, area, bool(smooth), temporal,
+                            frame_cnt, getattr(setup, "lights", None), reflect_lights, self.aux is not None)
+        else:
+            dof = None  # (the defaults: nothing to check)
         gi = check_gi(gi, gi_radius, gi_gain, gi_shadows, gi_sets, gi_filter, gi_filter_cos, gi_filter_plane,
                       getattr(setup, "lights", None), reflect_lights, self.aux is not None)
         area, area_radius = check_area(area, area_radius, shadows, getattr(setup, "lights", None), self.aux is not None)
@@ -1311,6 +1413,8 @@ class Renderer(_Frame, _Band):
             return two_streams(setup, frame_cnt, shadows, reflect, bounces, reflect_shadows)
         ctx = self.ctx
         cam = make_camera(setup.camera, setup.fovy, self.aspect)
+        if dof:
+            dof = self._dof_stage(dof, shade, cam)
         tp = area_t = None
         if temporal and shade:
             tp = self._temporal_begin(temporal, cam)
@@ -1332,6 +1436,8 @@ class Renderer(_Frame, _Band):
             return
         if aa:
             aa_edges(ctx, self, self.cam_pos, aa, shadows and aa[5])
+        if dof:
+            dof_pixels(ctx, self, dof)
         if reflect:
             reflect_rays(ctx, self, self.cam_pos)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
@@ -1345,7 +1451,7 @@ class Renderer(_Frame, _Band):
                              self.d_verts, self.d_faces, self.reflect_eps, self.rays, self.active)
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
             glossy_pass(ctx, self, self.cam_pos, glossy, lcam.worldori[:3] if glossy[5] else None)
-        elif ao or area or gi or aa:
+        elif ao or area or gi or aa or dof:
             build_grid(ctx, self, GRID_UNIFORM, self.shards)
         have_rays = bool(glossy)  # (glossy_pass wrote ao_rays / ao_active)
         if area:
@@ -1363,6 +1469,8 @@ class Renderer(_Frame, _Band):
             gi_pass(ctx, self, self.cam_pos, gi, lcam.worldori[:3] if gi[6] else None, bool(ao or area or glossy))
         if aa:
             aa_pass(ctx, self, cam.camcoords, aa, lcam.worldori[:3] if shadows and aa[5] else None)
+        if dof:
+            dof_pass(ctx, self, cam.camcoords, dof, lcam.worldori[:3] if shadows and dof[7] else None)
         normal = None
         if smooth:
             self._smooth_stage(smooth[0])
@@ -1385,6 +1493,8 @@ class Renderer(_Frame, _Band):
             gi_shade(ctx, self, gi)
         if aa:
             ctx.aa_resolve(self.image, self.aa_sum, aa[0])
+        if dof:
+            ctx.aa_resolve(self.image, self.dof_sum, dof[0])
         if ao and tp:
             ao_shade_temporal(ctx, self, tp, ao)
         elif ao:
@@ -1538,6 +1648,30 @@ class Renderer(_Frame, _Band):
             tables[(S, sets)] = self._upload_ao_sets(aa_offset_sets(S, sets))
         return (S, AREA_SET_TILES[sets], tables[(S, sets)], cos, default_filter_plane(self.bbmin, self.bbmax) if plane is None else plane,
                 shadows)
+
+    def _dof_stage(self, dof, shade, cam):
+        """(S, (set_w, set_h), table, lens, coc_scale, min, window, shadows) for dof_pixels and dof_pass from what check_dof
+        returned and the frame's camera (Camera.lens: U, V, A, F and the circle's scale in pixels), with the buffers
+        dof_flag [W*H] and dof_sum [4 W*H] (uint32 words in an int32 tensor) in place; None: nothing is shaded.  table:
+        scenes.lens_sample_sets(S, dof_sets) on the device, uploaded once per (S, dof_sets) and kept."""
+        if not shade:
+            return None
+        S, sets, aperture, focus, cmin, window, shadows = dof
+        self._ensure_dof_buffers()
+        tables = self._dof_set_tables
+        if (S, sets) not in tables:
+            from .scenes import lens_sample_sets
+
+            tables[(S, sets)] = self._upload_ao_sets(lens_sample_sets(S, sets))
+        lens, coc_scale = cam.lens(aperture, focus, self.ctx.height)
+        return (S, AREA_SET_TILES[sets], tables[(S, sets)], lens, coc_scale, cmin, window, shadows)
+
+    def _ensure_dof_buffers(self):
+        """dof_flag [W*H] and dof_sum [4 W*H] (uint32 words in an int32 tensor), allocated on first use."""
+        t, N, dev = self.torch, self.N, self.image.device
+        if self.dof_flag is None:
+            self.dof_flag = t.zeros(N, dtype=t.int32, device=dev)
+            self.dof_sum = t.zeros(4 * N, dtype=t.int32, device=dev)
 
     def _ensure_aa_buffers(self):
         """aa_edge [W*H] and aa_sum [4 W*H] (uint32 words in an int32 tensor), allocated on first use."""
@@ -1924,7 +2058,9 @@ class BandedRenderer(_Frame):
                 gi_gain=1.0, gi_shadows=True, gi_sets=1, gi_filter=0, gi_filter_cos=0.9, gi_filter_plane=None, aa=0, aa_sets=1,
                 aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0,
                 glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
-                glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False, fresnel=False, fresnel_cut=0.0):
+                glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False, dof=0, dof_aperture=0.0, dof_focus=None,
+                dof_sets=1, dof_min=0.5, dof_window=4, dof_shadows=True, fresnel=False, fresnel_cut=0.0):
+        check_dof(dof, dof_aperture, dof_focus, dof_sets, dof_min, dof_window, dof_shadows, two_streams=True)  # raises with dof > 0
         check_smooth(smooth, smooth_cos, smooth_signed, False, False, 0, 0, False, True)  # raises with smooth=True
         check_fresnel(fresnel, fresnel_cut, reflect, refract, 1, getattr(setup, "lights", None), False,
                       True)  # raises with fresnel: the tree's gather is not built here

@@ -22,6 +22,9 @@ parse the same text, so the float32 vertex arrays are identical.
   glossy()   -- a room whose reflecting floor is split into three strips of
                 sharpness 1000, 700 and 300 under rows of thin coloured posts
                 and a column: rough mirrors (Renderer.display(..., glossy=S))
+  depth()    -- a floor with five identical thin posts at growing distances
+                along the view: a lens focused on the middle one
+                (Renderer.display(..., dof=S, dof_aperture=a))
 """
 import os
 
@@ -539,6 +542,35 @@ def smooth(outdir=None, scale=1.0):
     return info
 
 
+DEPTH_POSTS = ((5.0, -0.8), (8.0, 0.45), (12.0, 0.0), (18.0, -0.4), (26.0, 0.8))  # distance along the view, side
+
+
+def depth(outdir=None, scale=1.0):
+    """A floor [2,30]x[0,26] at z = 0 (in front of the eye only: the primary pass takes |t|) and five identical thin
+    posts, 0.5 x 0.5 x 5, at the distances of DEPTH_POSTS along the view axis +x of a camera at (1, 13, 2.5), each moved
+    sideways by its second entry times a third of its distance so that none hides another.  The default look-at is the
+    middle post's axis: a lens focused there (Renderer.display(..., dof=S)) keeps it sharp and blurs the near and the far
+    ones.  info["posts"]: per post (first face, one past its last face, distance).  ~700 triangles at scale 1."""
+    mesh = Mesh()
+    s = max(0.05, scale) ** 0.5
+    n = max(2, int(12 * s))
+    mesh.add(*grid_quad((2, 0, 0), (28, 0, 0), (0, 26, 0), n, n), 0)
+    nb = max(1, int(3 * s))
+    posts = []
+    for dist, side in DEPTH_POSTS:
+        first = mesh.ntris()
+        x, y = 1.0 + dist, 13.0 + side * dist / 3.0
+        add_box(mesh, (x - 0.25, y - 0.25, 0.0), (x + 0.25, y + 0.25, 5.0), nb, 5, faces="xXyYZ")
+        posts.append((first, mesh.ntris(), dist))
+    cams = {"ref": dict(eye=(1.0, 13.0, 2.5), look=(13.0, 13.0, 2.5), up=(0, 0, 1), near=0.1, far=100.0)}
+    # the lights stand behind and above the eye: the faces the camera sees are lit alike, post after post
+    light_cam = dict(eye=(-8.0, 13.0, 16.0), look=(14.0, 13.0, 0.0), up=(0, 1, 0), near=0.1, far=100.0)
+    info = _finish(outdir, "depth", mesh, MATERIALS_ROOM,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(-10.0, 13.0, 8.0)))
+    info["posts"] = posts
+    return info
+
+
 def ao_directions(S):
     """The S local directions of the ambient-occlusion hemisphere: a deterministic
     cosine-weighted spiral, r = sqrt((s + 1/2) / S), phi = s * pi * (3 - sqrt(5)), direction
@@ -656,6 +688,13 @@ def aa_offset_sets(S, sets):
     rank = AREA_SET_RANK[sets]
     step = 1.0 / (float(sets + 1) * float(int(S)))
     return np.stack([_aa_points(S, rank[k] * step, (rank[sets - 1 - k] * step) if k else 0.0) for k in range(sets)])
+
+
+def lens_sample_sets(S, sets):
+    """The interleaved sample sets of the depth of field's lens rays: per sample
+    (sx, sy, lu, lv) -- aa_offset_sets(S, sets)' sub-pixel offset and glossy_point_sets(S, sets)' point of the unit disk,
+    the spiral turned per set by the AREA_SET_RANK turns.  float32 [sets, S, 4]."""
+    return np.ascontiguousarray(np.concatenate([aa_offset_sets(S, sets), glossy_point_sets(S, sets)], 2), dtype=np.float32)
 
 
 def temporal_sets(table16, sets, frame):
