@@ -178,6 +178,26 @@ const float *ugrt_scene_iorlist(const ugrt_scene *s, int *mtl_count);
  * and what a lobe's spread is made of is the caller's business (scenes.spread_from_sharpness).  A scene loaded from a
  * cache reports 1000 for every material -- the cache format does not hold the list --, so its reflections stay mirrors. */
 const float *ugrt_scene_sharpnesslist(const ugrt_scene *s, int *mtl_count);
+/* Texture coordinates and texture names of the loaded OBJ / MTL (obj_parser.cpp:52-104, 281-285, 348-351).
+ * ugrt_scene_uvlist: [2T] floats, the first two atof() values of every "vt" line in file order (a missing value is 0, a
+ * third one is dropped); *count = T.
+ * ugrt_scene_uv_facelist: [3F] ints, one per corner of the face list.  A token "v/t" or "v/t/n" has the texture index
+ * atoi() finds behind its first '/', a token "v" or "v//n" has 0; the index is converted like a vertex index against the
+ * number of "vt" lines read so far (0: -1, negative: relative to that number, else 1-based to 0-based), and whatever then
+ * lies outside 0..T-1 is stored as -1: that face is untextured.  load_model does not fail on such a face.
+ * ugrt_scene_texture_name: the texture of material `material` of the mtllib (0..mtl_count-1), "" for none and for a
+ * material out of range.  It is the token behind "map_Kd"; where the material has no map_Kd line, the token behind
+ * "map_Ka" (the field the reference fills).  Tokens split on " \t"; trailing '\r' and '\n' are stripped.  Options such as
+ * "-s" are not supported: a name that starts with '-' makes the material untextured.  The pointer stands until the
+ * scene is loaded again or destroyed.
+ * ugrt_scene_texture_dir: the directory of the mtllib that was read, with its trailing '/', or "" (the working
+ * directory): directory + name is the texture's path.
+ * A scene loaded from a cache has no texture coordinate, uv indices of -1 and no texture name: the cache format does not
+ * hold them. */
+const float *ugrt_scene_uvlist(const ugrt_scene *s, int *count);
+const int *ugrt_scene_uv_facelist(const ugrt_scene *s);
+const char *ugrt_scene_texture_name(const ugrt_scene *s, int material);
+const char *ugrt_scene_texture_dir(const ugrt_scene *s);
 /* Binary cache of a loaded scene (the strtok parser takes seconds on 1 M triangles).
  * Little-endian: "UGRTSCN1", counts, then the flat lists exactly as the accessors return them.
  * load_cache replaces the scene's contents; a truncated or foreign file gives UGRT_EIO. */
@@ -198,6 +218,17 @@ int ugrt_camera_direction_table(const float camcoords[64], float table[100]);
 
 /* writePPM(char*), per_app_funcs.h:39 (returns UGRT_EIO instead of exit(1)) */
 int ugrt_write_ppm(const char *path, int width, int height, const unsigned char *rgb);
+/* The counterpart of ugrt_write_ppm: reads a P3 (text) or P6 (binary) PPM.  The header is the magic, width, height and
+ * maxval, separated by white space, with "# ... end of line" comments anywhere between them; one white-space character
+ * follows the maxval of a P6 file.  maxval is 1..255; a sample v of a file whose maxval is below 255 becomes
+ * v * 255 / maxval in integers.  *width and *height are set once the header is read; rgb == NULL returns there (the size
+ * only).  Otherwise rgb[0 .. 3 * width * height) gets the samples in file order and `capacity` is the room of rgb in bytes.
+ * UGRT_EINVAL: path, width or height null.  UGRT_EIO, with a message: the file cannot be opened, is no P3 / P6 file, a
+ * dimension outside 1..UGRT_MAX_TEXTURE_DIM, a maxval outside 1..255, a sample above maxval, a file that ends before its
+ * last sample, capacity below 3 * width * height.  Nothing outside rgb[0 .. capacity) is written and no allocation is
+ * sized by a header value. */
+#define UGRT_MAX_TEXTURE_DIM 4096
+int ugrt_read_ppm(const char *path, int *width, int *height, unsigned char *rgb, size_t capacity);
 /* cosf/sinf of the animation angle as the library evaluates them */
 int ugrt_rot_cos_sin(float rot, float *c, float *s);
 
@@ -1002,6 +1033,97 @@ int ugrt_smooth_corner_normals(ugrt_ctx *ctx, const int *d_facelist, const float
 int ugrt_smooth_normals(ugrt_ctx *ctx, const float *d_t_value, const float *d_ray_dir, const int *d_intersect_id,
 			const float *d_cam_position, const float *d_vertlist, const int *d_trilist,
 			const float *d_corner_normals, const float *d_normal_in, int fold, float *d_normal_out);
+
+/* ---- device: texture mapping, a mip-mapped anisotropic albedo per pixel ----
+ * No reference counterpart: the reference parses texture coordinates and a texture name and shades with Kd alone.
+ * ugrt_texture_set builds a mip atlas on the device, ugrt_texture_albedo writes three floats per pixel -- the diffuse
+ * colour of the pixel's primary hit --, ugrt_texture_shade / ugrt_texture_shade_lights shade with them in the place of the
+ * material's Kd.  All float arithmetic is fp32, every + - * / sqrt floor one IEEE operation in the order written here, no
+ * contraction; the mip chain is exact in integers.  Every output is a function of the inputs alone, bit for bit.
+ *
+ * ugrt_texture_set(ctx, n, wh, rgb_host).  n = 0..UGRT_MAX_TEXTURES textures; texture i is wh[2i] texels wide and
+ * wh[2i + 1] high (each 1..UGRT_MAX_TEXTURE_DIM), rgb_host[i] points to its 3 * w * h bytes in HOST memory, row 0 first (the
+ * row of v = 0), R G B per texel; all textures together hold at most UGRT_MAX_TEXTURE_TEXELS texels.  The context keeps one
+ * device array of packed words r | g << 8 | b << 16 | 255 << 24 for every level of every texture (row-major) and a table
+ * {width, height, word offset, levels} per (texture, level).  Level l + 1 of a texture has max(1, w_l >> 1) x
+ * max(1, h_l >> 1) texels; its texel (x, y) is per channel (a + b + c + d + 2) >> 2 of the level-l texels at the columns
+ * min(2x, w_l - 1), min(2x + 1, w_l - 1) and the rows min(2y, h_l - 1), min(2y + 1, h_l - 1); alpha stays 255.  The chain
+ * ends at 1 x 1, so a texture has 1 + floor(log2(max(w, h))) levels, at most UGRT_MAX_TEXTURE_LEVELS.  Level 0 is copied
+ * to the device, every further level is built there by one kernel launch per level over all textures; the call does not
+ * wait for the device (rgb_host may be released when it returns; a call that follows another waits for that one's two
+ * copies, whose host sources it writes again).  A call replaces the atlas of the call before; n = 0 drops it: it waits
+ * for the context's stream and frees the device arrays.  Stage UGRT_ST_BUILD_FILL.  ugrt_ctx_get_state "texture_builds" counts the calls that succeeded with n > 0,
+ * "texture_count" is n of the last call.  UGRT_EINVAL, and the atlas of the call before stands: n out of range, a null
+ * wh or rgb_host or rgb_host[i] with n > 0, a dimension or the texel total out of range.  Any other failure (UGRT_ENOMEM
+ * for the device arrays, UGRT_EHIP) leaves the context without an atlas -- "texture_count" 0, "texture_builds" as it was --,
+ * never with a half-written one.
+ * ugrt_texture_get_level (tests): width, height and the device pointer of the words of level `level` of texture `tex`;
+ * they stand until the next ugrt_texture_set.  UGRT_EINVAL: no such texture or level.
+ *
+ * ugrt_texture_albedo: d_albedo[3p ..] for every pixel p = row * width + col of the context's band, before the shading
+ * call (d_intersect_id holds triangle ids); it reads the context's current camera (ugrt_upload_camera).
+ *   id < 0, !(t > 0), or m = d_mat_idx[id] outside 0..num_materials-1: three +0.
+ *   Otherwise Kd = d_mat_list[6m + 3 ..], T = d_mat_texture[m] (device, one int per material; < 0: none) and the pixel gets
+ *   Kd where T < 0 (or T >= the atlas's count, which the host check below excludes), where one of the three
+ *   d_uv_facelist[3 id + k] lies outside 0..num_uvs-1, where the centre's determinant fails or where a component of the
+ *   centre's uv is not finite.  Otherwise it gets Kd[c] * (filtered[c] / 255) per channel c.
+ *   A ray's uv: tvec = d_cam_position - v0, e1 = v1 - v0, e2 = v2 - v0 of triangle id and a direction d; pvec = CROSS(d, e2),
+ *   det = DOT(e1, pvec) (inside (-1e-21, 1e-21): failed), inv = 1 / det, u = DOT(tvec, pvec) * inv,
+ *   v = DOT(d, CROSS(tvec, e1)) * inv -- ugrt_smooth_normals' own, not clamped --, w = (1 - u) - v, and per component
+ *   uv = (w * uv0 + u * uv1) + v * uv2 of the corners' d_uvlist entries.  The centre's d is the pixel's stored direction
+ *   d_ray_dir[3p ..]; the two neighbours' are the eye rays the primary pass forms at the image positions
+ *   ((float)(col + 1), (float)row) and ((float)col, (float)(row + 1)) from the camera's node table (with
+ *   UGRT_FLAG_STRICT_TEXTURE: through its filter rule), formed anew: nothing is read from another pixel, and the last
+ *   column, the last row and a band's edge are pixels like the others.
+ *   Footprint: W0 x H0 = level 0 of T.  dx = ((uvX[0] - uv[0]) * (float)W0, (uvX[1] - uv[1]) * (float)H0), dy likewise from
+ *   the second neighbour; Lx = sqrt(dx[0] * dx[0] + dx[1] * dx[1]), Ly likewise.  major = dy where Ly > Lx, else dx;
+ *   Lmax its length, Lmin the other's.  Where a neighbour's determinant failed or !(Lx < LIM) or !(Ly < LIM),
+ *   LIM = 2 * UGRT_MAX_TEXTURE_DIM * 16 (a NaN or an infinite length lands here): N = 1, the last level, fraction 0 and
+ *   major = (+0, +0) -- one tap at the centre on the 1 x 1 level.
+ *   Otherwise N = the smallest integer in 1..max_aniso with Lmin * (float)N >= Lmax, or max_aniso where there is none;
+ *   lambda = (Lmax / (float)N) * lod_bias_scale with lod_bias_scale = 2^lod_bias formed on the host; !(lambda > 1):
+ *   level e = 0 and fraction f = 0; else e = lambda's unbiased exponent read from its bits and f = lambda / 2^e - 1 (the
+ *   piecewise-linear log2); e >= the last level: the last level and f = 0.
+ *   Tap i = 0..N-1: s = (float)(2i + 1) / (float)(2N) - 0.5, at (uv[0] + (s * major[0]) / (float)W0,
+ *   uv[1] + (s * major[1]) / (float)H0); its value per channel is A = the bilinear value on level e, and where f != 0
+ *   (1 - f) * A + f * B with B the bilinear value on level e + 1.
+ *   Bilinear at (a, b) on a level of w x h: a' = a - floor(a), x = a' * (float)w - 0.5, x0 = floor(x), fx = x - x0, the
+ *   columns (int)x0 and (int)x0 + 1, each c < 0 ? c + w : c, then c >= w ? c - w : c (the texture repeats; a' may be
+ *   exactly 1 for a tiny negative a and stays inside; float to int as ugrt_f2i; an index that were still outside 0..w-1
+ *   reads column 0); b, h and the rows likewise.  With the four texels' channel as floats 0..255:
+ *   (c00 * (1 - fx) + c10 * fx) * (1 - fy) + (c01 * (1 - fx) + c11 * fx) * fy, c10 the next column, c01 the next row.
+ *   filtered = the taps' values added in the order i = 0..N-1, from +0, divided by (float)N.
+ *   max_aniso 1..UGRT_MAX_TEXTURE_ANISO (1: isotropic trilinear), lod_bias -16..16.  mat_texture_host is the host copy of
+ *   d_mat_texture, read by the call's check only.  One thread per pixel; pixels outside the band are not written.  Stage
+ *   UGRT_ST_SHADE.  UGRT_EINVAL and nothing enqueued: a null argument (d_uvlist may be null where num_uvs is 0),
+ *   num_uvs or num_materials negative, a mat_texture_host entry >= the atlas's count (0 where there is no atlas: a material
+ *   that names a texture needs one), max_aniso or lod_bias out of range.
+ *
+ * ugrt_texture_shade / ugrt_texture_shade_spotlight / ugrt_texture_shade_lights: ugrt_shade_simple / ugrt_shade_spotlight
+ * (d_dump may be null) / ugrt_shade_lights with one more argument.  The Kd
+ * that the shading of pixel p reads (twice: shader_kernel.cu:180-186) is d_albedo[3p ..] in the place of
+ * d_mat_list[6m + 3 ..]; the id rewrite, the guards, the clamps and the bytes' rule are the same.  Where d_albedo holds
+ * the material's Kd the image is that of the call without it, bit for bit. */
+#define UGRT_MAX_TEXTURES 64
+#define UGRT_MAX_TEXTURE_LEVELS 13          /* 1 + log2(UGRT_MAX_TEXTURE_DIM) */
+#define UGRT_MAX_TEXTURE_TEXELS (1u << 26)  /* level 0 of all textures together */
+#define UGRT_MAX_TEXTURE_ANISO 16
+int ugrt_texture_set(ugrt_ctx *ctx, int n, const int *wh, const unsigned char *const *rgb_host);
+int ugrt_texture_get_level(ugrt_ctx *ctx, int tex, int level, int *width, int *height, const unsigned **d_words);
+int ugrt_texture_albedo(ugrt_ctx *ctx, const float *d_t_value, const float *d_ray_dir, const int *d_intersect_id,
+			const float *d_cam_position, const float *d_vertlist, const int *d_facelist, const float *d_uvlist,
+			int num_uvs, const int *d_uv_facelist, const int *d_mat_idx, const float *d_mat_list, int num_materials,
+			const int *d_mat_texture, const int *mat_texture_host, int max_aniso, int lod_bias, float *d_albedo);
+int ugrt_texture_shade(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+		      const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+		      const float *d_mat_list, int num_materials, const float *d_albedo);
+int ugrt_texture_shade_spotlight(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+				const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+				const float *d_mat_list, int num_materials, float *d_dump, const float *d_albedo);
+int ugrt_texture_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+			     const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position, const int *d_mat_idx,
+			     const float *d_mat_list, int num_materials, int num_lights, const float *light_pos,
+			     const int *d_is_shadowed, const float *d_albedo);
 
 /* ---- device: adaptive anti-aliasing, sub-pixel eye rays on edge pixels ----
  * The frame takes one eye ray per pixel, through the pixel's corner.  ugrt_aa_edges finds the pixels that lie on an edge,

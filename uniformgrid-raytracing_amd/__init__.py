@@ -69,6 +69,10 @@ MAX_GLOSSY_SAMPLES = 32  # UGRT_MAX_GLOSSY_SAMPLES
 MAX_GLOSSY_SPREAD = 1.0  # UGRT_MAX_GLOSSY_SPREAD
 MAX_FRESNEL_DEPTH = 6  # UGRT_MAX_FRESNEL_DEPTH
 TEMPORAL_DEN = 256  # UGRT_TEMPORAL_DEN
+MAX_TEXTURES = 64  # UGRT_MAX_TEXTURES
+MAX_TEXTURE_DIM = 4096  # UGRT_MAX_TEXTURE_DIM
+MAX_TEXTURE_LEVELS = 13  # UGRT_MAX_TEXTURE_LEVELS
+MAX_TEXTURE_ANISO = 16  # UGRT_MAX_TEXTURE_ANISO
 STAGES = [
     "build_count", "build_scan", "build_fill", "build_sort", "build_bounds", "trace_primary", "map_rays",
     "sort_rays", "trace_shadow", "shade", "reflect_gen", "trace_dda", "animate", "worklist", "shadow_cull", "shadow_prep",
@@ -208,6 +212,17 @@ PROTOTYPES = {
     "ugrt_smooth_get_adjacency": (C.c_int, [_P, C.POINTER(_P), C.POINTER(_P)]),
     "ugrt_smooth_corner_normals": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, _P]),
     "ugrt_smooth_normals": (C.c_int, [_P] * 9 + [C.c_int, _P]),
+    "ugrt_scene_uvlist": (_P, [_P, C.POINTER(C.c_int)]),
+    "ugrt_scene_uv_facelist": (_P, [_P]),
+    "ugrt_scene_texture_name": (C.c_char_p, [_P, C.c_int]),
+    "ugrt_scene_texture_dir": (C.c_char_p, [_P]),
+    "ugrt_read_ppm": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.c_size_t]),
+    "ugrt_texture_set": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int), C.POINTER(_P)]),
+    "ugrt_texture_get_level": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(_P)]),
+    "ugrt_texture_albedo": (C.c_int, [_P] * 8 + [C.c_int] + [_P] * 3 + [C.c_int, _P, C.POINTER(C.c_int), C.c_int, C.c_int, _P]),
+    "ugrt_texture_shade": (C.c_int, [_P] * 9 + [C.c_int, _P]),
+    "ugrt_texture_shade_spotlight": (C.c_int, [_P] * 9 + [C.c_int, _P, _P]),
+    "ugrt_texture_shade_lights": (C.c_int, [_P] * 9 + [C.c_int, C.c_int, _F3, _P, _P]),
     "ugrt_aa_edges": (C.c_int, [_P] * 8 + [C.c_float, C.c_float, _P]),
     "ugrt_aa_gather": (C.c_int, [_P] * 6 + [_F3, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, _F3, C.c_float, _P]),
     "ugrt_aa_resolve": (C.c_int, [_P, _P, _P, C.c_int]),
@@ -242,7 +257,7 @@ def _f3(v):
     return (C.c_float * len(v))(*[float(x) for x in v])
 
 
-from .host import Model, Camera, write_ppm  # noqa: E402
+from .host import Model, Camera, write_ppm, read_ppm  # noqa: E402
 from .device import Context  # noqa: E402
 from . import scenes  # noqa: E402
 from .renderer import Renderer, FrameSetup, BandedRenderer  # noqa: E402

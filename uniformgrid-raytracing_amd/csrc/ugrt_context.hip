@@ -188,6 +188,10 @@ extern "C" void ugrt_ctx_destroy(ugrt_ctx *ctx)
 	}
 	buf_free(ctx->sm_start);
 	buf_free(ctx->sm_rec);
+	if (ctx->tx_copied)
+		(void)hipEventDestroy(ctx->tx_copied);
+	buf_free(ctx->tx_words);
+	buf_free(ctx->tx_table);
 	if (ctx->h_pinned)
 		(void)hipHostFree(ctx->h_pinned);
 	if (ctx->d_small)
@@ -252,6 +256,10 @@ extern "C" int ugrt_ctx_get_state(ugrt_ctx *ctx, const char *key, long long *val
 		*value = (long long)ctx->sm_normal_builds;
 	else if (strcmp(key, "fresnel_gathers") == 0)
 		*value = (long long)ctx->fresnel_gathers;
+	else if (strcmp(key, "texture_builds") == 0)
+		*value = (long long)ctx->tx_builds;
+	else if (strcmp(key, "texture_count") == 0)
+		*value = (long long)ctx->tx_count;
 	else if (strcmp(key, "fresnel_nodes") == 0) {
 		// the nodes the last ugrt_fresnel_gather walked (waits for the stream)
 		unsigned long long n = 0;

@@ -148,6 +148,11 @@ struct Grid {
 static_assert(UGRT_DSMALL_DDA + 2 * UGRT_DDA_STATS <= UGRT_DSMALL_RW, "the DDA's counters run into the build counts");
 static_assert(UGRT_DSMALL_RW + 6 <= UGRT_DSMALL_SHADOW && UGRT_DSMALL_SHADOW + 10 <= UGRT_DSMALL_PRIMARY && UGRT_DSMALL_PRIMARY + 2 * UGRT_PRIMARY_STATS <= UGRT_DSMALL_FRAGS && UGRT_DSMALL_FRAGS + 3 <= UGRT_DSMALL_FRESNEL && UGRT_DSMALL_FRESNEL + 2 <= UGRT_DSMALL_WORDS && UGRT_PIN_SHADOW + 8 <= UGRT_PIN_WORDS && UGRT_PIN_REPORT + 12 <= UGRT_PIN_SHADOW, "scratch layout");
 
+// one level of one texture in the mip atlas (16 bytes: one aligned load)
+struct TexLevel {
+	u32 w, h, offset, levels; // texels, first word in the atlas, levels of the texture (0: no such level)
+};
+
 struct ProfPair {
 	hipEvent_t a, b;
 };
@@ -265,6 +270,14 @@ struct ugrt_ctx {
 	int sm_faces = 0, sm_vertices = 0;
 	unsigned long long sm_adjacency_builds = 0, sm_normal_builds = 0; // ugrt_ctx_get_state "smooth_adjacency_builds", "smooth_normal_builds"
 	unsigned long long fresnel_gathers = 0; // ugrt_fresnel_gather calls that launched ("fresnel_gathers")
+	// texture mapping (ugrt_texture.hip): the mip atlas' words, the table {w, h, offset, levels} per
+	// (texture, level) on the device and on the host, the texture count (0: no atlas)
+	DevBuf tx_words, tx_table;
+	std::vector<TexLevel> tx_levels; // [tx_count * UGRT_MAX_TEXTURE_LEVELS]
+	std::vector<u32> tx_stage;       // the packed level 0 of the last ugrt_texture_set (the source of its copy)
+	hipEvent_t tx_copied = nullptr;  // recorded behind that call's two copies: tx_stage and tx_levels are free again once it has passed
+	int tx_count = 0;
+	unsigned long long tx_builds = 0; // ugrt_ctx_get_state "texture_builds"
 };
 
 #define UGRT_HIP(call)                                                                            \

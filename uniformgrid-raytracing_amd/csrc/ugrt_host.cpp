@@ -38,17 +38,19 @@ extern "C" int ugrt_version(void) { return UGRT_VERSION; }
 //  - lines are cut at 499 characters (fgets into OBJ_LINE_SIZE, :305,331)
 //  - tokens split on " \t\n\r"; a line whose first token starts with '#' is a
 //    comment (:336)
-//  - v/vn/vt: three atof() values (:163-170)
+//  - v/vn/vt: three atof() values (:163-170); of a vt line the first two are kept
 //  - f: up to 4 "v", "v/t", "v//n", "v/t/n" tokens, atoi() per field (:49-84);
 //    index 0 -> -1, negative -> relative to the vertices read so far, else
-//    1-based -> 0-based (:16-26)
+//    1-based -> 0-based (:16-26); the texture index likewise against the vt
+//    lines read so far, "v" and "v//n" have none (:52-90)
 //  - usemtl: the FIRST material whose stored name starts with the token
 //    (list_find is a strncmp prefix match, list.cpp:115-126), else -1
 //  - mtllib: parsed immediately (:415-420)
 //  - sp/pl/p/lp/ld/lq/c/o/s/g are accepted and ignored by the renderer
 // MTL (:182-296): newmtl opens a material with the defaults of :28-45; names
 // are split on " \t" only, so they keep the line's trailing newline; Ka is
-// split on " " only; Kd Ks Ns d r sharpness Ni map_Ka as usual.
+// split on " " only; Kd Ks Ns d r sharpness Ni map_Ka as usual; map_Kd (not in
+// the reference) names the texture before map_Ka does.
 // ---------------------------------------------------------------------------
 namespace {
 
@@ -58,13 +60,18 @@ struct Material {
 	std::string name;
 	double amb[3], diff[3], spec[3];
 	double reflect, trans, shiny, glossy, refract_index;
-	std::string texture;
+	std::string texture;    // map_Ka (texture_filename, obj_parser.cpp:281-285)
+	std::string texture_kd; // map_Kd
+	bool has_kd = false;
 };
 
 struct ObjFile {
 	std::vector<double> v;  // 3 per vertex
-	size_t nvn = 0, nvt = 0;
+	size_t nvn = 0;
+	std::vector<float> vt;  // 2 per texture vertex
 	std::vector<int> fidx;  // 4 per face (vertex indices, converted)
+	std::vector<int> ftex;  // 4 per face (texture indices, converted against the vt lines read so far)
+	std::string mtl_dir;    // directory of the mtllib that was read, with its '/'
 	std::vector<int> fmat;  // material per face
 	std::vector<Material> mtl;
 };
@@ -141,6 +148,10 @@ bool parse_mtl(const std::string &path, std::vector<Material> &out)
 		} else if (!strcmp(tok, "map_Ka")) {
 			char *t = strtok_r(nullptr, " \t", &save);
 			out.back().texture = t ? t : "";
+		} else if (!strcmp(tok, "map_Kd")) {
+			char *t = strtok_r(nullptr, " \t", &save);
+			out.back().texture_kd = t ? t : "";
+			out.back().has_kd = true;
 		}
 	}
 	fclose(fp);
@@ -180,19 +191,29 @@ bool parse_obj(const char *path, ObjFile &o)
 		} else if (!strcmp(tok, "vn")) {
 			o.nvn++;
 		} else if (!strcmp(tok, "vt")) {
-			o.nvt++;
+			const double tu = tok_atof(WS, &save), tv = tok_atof(WS, &save);
+			o.vt.push_back((float)tu);
+			o.vt.push_back((float)tv);
 		} else if (!strcmp(tok, "f")) {
-			int idx[4] = { 0, 0, 0, 0 };
+			int idx[4] = { 0, 0, 0, 0 }, tex[4] = { 0, 0, 0, 0 };
 			int cnt = 0;
 			char *t;
 			while ((t = strtok_r(nullptr, WS, &save)) != nullptr) {
-				if (cnt < 4)
+				if (cnt < 4) {
 					idx[cnt] = atoi(t);
+					// obj_parse_vertex_index, obj_parser.cpp:68-84: "v//n" has no texture index, "v/t" and
+					// "v/t/n" the number behind the first '/'
+					const char *slash = strchr(t, '/');
+					if (slash && !strstr(t, "//"))
+						tex[cnt] = atoi(slash + 1);
+				}
 				cnt++;
 			}
-			int nv = (int)(o.v.size() / 3);
-			for (int k = 0; k < 4; k++)
+			int nv = (int)(o.v.size() / 3), nt = (int)(o.vt.size() / 2);
+			for (int k = 0; k < 4; k++) {
 				o.fidx.push_back(convert_index(nv, idx[k]));
+				o.ftex.push_back(convert_index(nt, tex[k]));
+			}
 			o.fmat.push_back(current_material);
 		} else if (!strcmp(tok, "usemtl")) {
 			current_material = find_material(o.mtl, strtok_r(nullptr, WS, &save));
@@ -200,8 +221,16 @@ bool parse_obj(const char *path, ObjFile &o)
 			char *fn = strtok_r(nullptr, WS, &save);
 			if (fn) {
 				// next to the .obj first, then relative to the cwd (reference behaviour)
-				if (!parse_mtl(dir + fn, o.mtl))
-					parse_mtl(fn, o.mtl);
+				std::string used = dir + fn;
+				bool ok = parse_mtl(used, o.mtl);
+				if (!ok) {
+					used = fn;
+					ok = parse_mtl(used, o.mtl);
+				}
+				if (ok) {
+					const size_t cut = used.find_last_of('/');
+					o.mtl_dir = cut == std::string::npos ? std::string() : used.substr(0, cut + 1);
+				}
 			}
 		}
 	}
@@ -220,6 +249,10 @@ struct ugrt_scene {
 	std::vector<float> transmit;    // 1 - obj_material.trans (the dissolve d: 1 = opaque), clamped to [0, 1]
 	std::vector<float> ior;         // obj_material.refract_index
 	std::vector<float> sharpness;   // obj_material.glossy (the MTL token "sharpness", 0..1000, default 98), raw
+	std::vector<float> uvlist;      // vertex_texture_list: u, v per "vt" line
+	std::vector<int> uvfacelist;    // face->texture_index per corner of facelist; -1 = none
+	std::vector<std::string> texture; // per mtllib material: map_Kd, else map_Ka; "" = none
+	std::string texture_dir;
 	int num_materials = 0;
 	float bbmin[3] = { 9999.9f, 9999.9f, 9999.9f };
 	float bbmax[3] = { -9999.9f, -9999.9f, -9999.9f };
@@ -327,6 +360,24 @@ extern "C" int ugrt_scene_load_model(ugrt_scene *s, const char *path)
 	s->sharpness.resize(o.mtl.size());
 	for (size_t i = 0; i < o.mtl.size(); i++)
 		s->sharpness[i] = (float)o.mtl[i].glossy;
+	s->uvlist = o.vt;
+	const int nt = (int)(o.vt.size() / 2);
+	s->uvfacelist.resize(nf * 3);
+	for (size_t f = 0; f < nf; f++)
+		for (int k = 0; k < 3; k++) {
+			const int ti = o.ftex[f * 4 + k];
+			s->uvfacelist[f * 3 + k] = ti >= 0 && ti < nt ? ti : -1;
+		}
+	s->texture.assign(o.mtl.size(), std::string());
+	for (size_t i = 0; i < o.mtl.size(); i++) {
+		std::string name = o.mtl[i].has_kd ? o.mtl[i].texture_kd : o.mtl[i].texture;
+		while (!name.empty() && (name.back() == '\n' || name.back() == '\r'))
+			name.pop_back();
+		if (!name.empty() && name[0] == '-') // an option ("-s 2 2 file"): not supported, the material is untextured
+			name.clear();
+		s->texture[i] = name;
+	}
+	s->texture_dir = o.mtl_dir;
 	return UGRT_OK;
 }
 
@@ -430,6 +481,9 @@ extern "C" int ugrt_scene_load_cache(ugrt_scene *s, const char *path)
 	t.ior.assign(t.reflect.size(), 1.0f);
 	// nor a sharpness: a cached scene's reflections are mirrors
 	t.sharpness.assign(t.reflect.size(), 1000.0f);
+	// nor texture coordinates or texture names: a cached scene is untextured
+	t.uvfacelist.assign(t.facelist.size(), -1);
+	t.texture.assign(t.reflect.size(), std::string());
 	*s = t;
 	return UGRT_OK;
 }
@@ -482,6 +536,22 @@ extern "C" const float *ugrt_scene_sharpnesslist(const ugrt_scene *s, int *n)
 		*n = (int)s->sharpness.size();
 	return s->sharpness.data();
 }
+extern "C" const float *ugrt_scene_uvlist(const ugrt_scene *s, int *n)
+{
+	if (!s)
+		return nullptr;
+	if (n)
+		*n = (int)(s->uvlist.size() / 2);
+	return s->uvlist.data();
+}
+extern "C" const int *ugrt_scene_uv_facelist(const ugrt_scene *s) { return s ? s->uvfacelist.data() : nullptr; }
+extern "C" const char *ugrt_scene_texture_name(const ugrt_scene *s, int material)
+{
+	if (!s || material < 0 || (size_t)material >= s->texture.size())
+		return "";
+	return s->texture[(size_t)material].c_str();
+}
+extern "C" const char *ugrt_scene_texture_dir(const ugrt_scene *s) { return s ? s->texture_dir.c_str() : ""; }
 extern "C" int ugrt_scene_bounds(const ugrt_scene *s, float bbmin[3], float bbmax[3])
 {
 	if (!s || !bbmin || !bbmax)
@@ -674,6 +744,108 @@ extern "C" int ugrt_write_ppm(const char *path, int W, int H, const unsigned cha
 	int rc = fclose(fp);
 	if (w != out.size() || rc != 0)
 		return ugrt_fail(UGRT_EIO, "write_ppm: short write to %s", path);
+	return UGRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// ugrt_read_ppm: P3 / P6.  The file is read through stdio, one character at a time in the header and the text samples;
+// nothing is sized by what the header says.
+// ---------------------------------------------------------------------------
+namespace {
+
+// the next character that is neither white space nor inside a "# ..." comment; EOF at the end
+int ppm_skip(FILE *fp)
+{
+	for (;;) {
+		int c = fgetc(fp);
+		if (c == '#') {
+			while (c != '\n' && c != '\r' && c != EOF)
+				c = fgetc(fp);
+			if (c == EOF)
+				return EOF;
+			continue;
+		}
+		if (c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == '\v' || c == '\f')
+			continue;
+		return c;
+	}
+}
+
+// an unsigned decimal number of at most 9 digits; *last = the character behind it.  false: none, or too long
+bool ppm_number(FILE *fp, unsigned *out, int *last)
+{
+	int c = ppm_skip(fp);
+	if (c < '0' || c > '9')
+		return false;
+	unsigned v = 0;
+	int digits = 0;
+	while (c >= '0' && c <= '9') {
+		if (++digits > 9)
+			return false;
+		v = v * 10u + (unsigned)(c - '0');
+		c = fgetc(fp);
+	}
+	if (c == '#') // a comment that starts at the number's end: left for the next skip
+		ungetc(c, fp);
+	*out = v;
+	*last = c;
+	return true;
+}
+
+} // namespace
+
+extern "C" int ugrt_read_ppm(const char *path, int *width, int *height, unsigned char *rgb, size_t capacity)
+{
+	if (!path || !width || !height)
+		return ugrt_fail(UGRT_EINVAL, "read_ppm: null argument");
+	FILE *fp = fopen(path, "rb");
+	if (!fp)
+		return ugrt_fail(UGRT_EIO, "read_ppm: fopen %s: %s", path, strerror(errno));
+	struct Closer {
+		FILE *f;
+		~Closer() { fclose(f); }
+	} closer = { fp };
+	const int m0 = fgetc(fp), m1 = fgetc(fp);
+	if (m0 != 'P' || (m1 != '3' && m1 != '6'))
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s is neither a P3 nor a P6 file", path);
+	const bool text = m1 == '3';
+	unsigned w = 0, h = 0, maxval = 0;
+	int last = 0;
+	if (!ppm_number(fp, &w, &last) || !ppm_number(fp, &h, &last) || !ppm_number(fp, &maxval, &last))
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s: the header is not `width height maxval`", path);
+	if (w < 1 || w > UGRT_MAX_TEXTURE_DIM || h < 1 || h > UGRT_MAX_TEXTURE_DIM)
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s: %u x %u is outside 1..%d", path, w, h, UGRT_MAX_TEXTURE_DIM);
+	if (maxval < 1 || maxval > 255)
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s: maxval %u is outside 1..255", path, maxval);
+	if (!(last == ' ' || last == '\t' || last == '\n' || last == '\r' || last == '\v' || last == '\f') && !(text && last == '#'))
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s: no white space behind the maxval", path);
+	*width = (int)w;
+	*height = (int)h;
+	if (!rgb)
+		return UGRT_OK;
+	const size_t total = (size_t)3 * w * h;
+	if (capacity < total)
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s: %zu bytes do not fit a capacity of %zu", path, total, capacity);
+	if (text) {
+		for (size_t i = 0; i < total; i++) {
+			unsigned v = 0;
+			if (!ppm_number(fp, &v, &last))
+				return ugrt_fail(UGRT_EIO, "read_ppm: %s ends or breaks off at sample %zu of %zu", path, i, total);
+			if (v > maxval)
+				return ugrt_fail(UGRT_EIO, "read_ppm: %s: sample %zu is %u, above the maxval %u", path, i, v, maxval);
+			rgb[i] = (unsigned char)(v * 255u / maxval);
+		}
+		return UGRT_OK;
+	}
+	if (fread(rgb, 1, total, fp) != total)
+		return ugrt_fail(UGRT_EIO, "read_ppm: %s ends before its %zu bytes", path, total);
+	if (maxval < 255)
+		for (size_t i = 0; i < total; i++) {
+			const unsigned v = rgb[i];
+			if (v > maxval)
+				return ugrt_fail(UGRT_EIO, "read_ppm: %s: sample %zu is %u, above the maxval %u", path, i, v, maxval);
+			rgb[i] = (unsigned char)(v * 255u / maxval);
+		}
 	return UGRT_OK;
 }
 

@@ -286,18 +286,26 @@ struct PrimaryHit {
 	}
 };
 
-template <bool SPOT>
-__global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned char *__restrict__ d_img,
-						       const float *__restrict__ dd_normal,
-						       const float *__restrict__ dd_t_value, const float *__restrict__ dd_dir,
-						       int *__restrict__ dd_intersect_id, const float *__restrict__ d_cam_pos,
-						       const int *__restrict__ mat_idx, const float *__restrict__ mat_list,
-						       int mat_count, float *__restrict__ dump, int p0, int n)
+// Kd of the pixel, twice, where the shading reads it from the per-pixel albedo (ugrt_texture_albedo) and not from the
+// material: d_material_kd's counterpart
+__device__ __forceinline__ void d_albedo_kd(const float *__restrict__ albedo, int pixelID, float *material)
 {
-	int i = blockIdx.x * PX_THREADS + threadIdx.x;
-	if (i >= n)
-		return;
-	int pixelID = p0 + i;
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		material[k] = albedo[pixelID * 3 + k];
+		material[3 + k] = albedo[pixelID * 3 + k];
+	}
+}
+
+// k_shade's pixel; ALBEDO: Kd is the pixel's albedo[3 pixelID ..] (k_texture_shade), else the material's and albedo is not read
+template <bool SPOT, bool ALBEDO>
+__device__ __forceinline__ void d_shade_pixel(const CamBlock &cam, unsigned char *__restrict__ d_img,
+					      const float *__restrict__ dd_normal, const float *__restrict__ dd_t_value,
+					      const float *__restrict__ dd_dir, int *__restrict__ dd_intersect_id,
+					      const float *__restrict__ d_cam_pos, const int *__restrict__ mat_idx,
+					      const float *__restrict__ mat_list, int mat_count, float *__restrict__ dump,
+					      const float *__restrict__ albedo, int pixelID)
+{
 	float color[3] = { 0.0f, 0.0f, 0.0f }, drop_off = 1.0f, point[3];
 	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
 	const int idx = hit.material_id();
@@ -319,7 +327,10 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned cha
 	}
 	if (idx >= 0 && (SPOT || t_value > 0)) {
 		float material[6], nrm[3];
-		d_material_kd(mat_list, idx, material);
+		if (ALBEDO)
+			d_albedo_kd(albedo, pixelID, material);
+		else
+			d_material_kd(mat_list, idx, material);
 		hit.normal(nrm);
 		d_lambert<SPOT>(cam, point, nrm, color, material, drop_off);
 		d_clamp1(color);
@@ -327,6 +338,36 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned cha
 	d_img[pixelID * 3 + 0] = d_to_u8(color[0]);
 	d_img[pixelID * 3 + 1] = d_to_u8(color[1]);
 	d_img[pixelID * 3 + 2] = d_to_u8(color[2]);
+}
+
+template <bool SPOT>
+__global__ __launch_bounds__(PX_THREADS) void k_shade(CamBlock cam, unsigned char *__restrict__ d_img,
+						       const float *__restrict__ dd_normal,
+						       const float *__restrict__ dd_t_value, const float *__restrict__ dd_dir,
+						       int *__restrict__ dd_intersect_id, const float *__restrict__ d_cam_pos,
+						       const int *__restrict__ mat_idx, const float *__restrict__ mat_list,
+						       int mat_count, float *__restrict__ dump, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	d_shade_pixel<SPOT, false>(cam, d_img, dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count,
+				   dump, nullptr, p0 + i);
+}
+
+// k_shade<false> with the pixel's albedo in the place of the material's Kd
+__global__ __launch_bounds__(PX_THREADS) void k_texture_shade(CamBlock cam, unsigned char *__restrict__ d_img,
+							      const float *__restrict__ dd_normal,
+							      const float *__restrict__ dd_t_value, const float *__restrict__ dd_dir,
+							      int *__restrict__ dd_intersect_id, const float *__restrict__ d_cam_pos,
+							      const int *__restrict__ mat_idx, const float *__restrict__ mat_list,
+							      int mat_count, const float *__restrict__ albedo, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	d_shade_pixel<false, true>(cam, d_img, dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count,
+				   nullptr, albedo, p0 + i);
 }
 
 // the null check of every export that takes the primary arrays
@@ -349,6 +390,51 @@ extern "C" int ugrt_shade_simple(ugrt_ctx *ctx, unsigned char *d_img, const floa
 		return rc;
 	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_shade<false>, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
 				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, (float *)nullptr);
+}
+
+// k_shade<true> with the pixel's albedo in the place of the material's Kd
+__global__ __launch_bounds__(PX_THREADS) void k_texture_shade_spot(CamBlock cam, unsigned char *__restrict__ d_img,
+								    const float *__restrict__ dd_normal,
+								    const float *__restrict__ dd_t_value, const float *__restrict__ dd_dir,
+								    int *__restrict__ dd_intersect_id, const float *__restrict__ d_cam_pos,
+								    const int *__restrict__ mat_idx, const float *__restrict__ mat_list,
+								    int mat_count, float *__restrict__ dump,
+								    const float *__restrict__ albedo, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	d_shade_pixel<true, true>(cam, d_img, dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count,
+				  dump, albedo, p0 + i);
+}
+
+extern "C" int ugrt_texture_shade_spotlight(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+					    const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+					    const int *d_mat_idx, const float *d_mat_list, int num_materials, float *d_dump,
+					    const float *d_albedo)
+{
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, "texture_shade_spotlight");
+	if (rc)
+		return rc;
+	if (!d_albedo)
+		return ugrt_fail(UGRT_EINVAL, "texture_shade_spotlight: null argument");
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_texture_shade_spot, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, d_dump, d_albedo);
+}
+
+extern "C" int ugrt_texture_shade(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+				 const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+				 const int *d_mat_idx, const float *d_mat_list, int num_materials, const float *d_albedo)
+{
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, "texture_shade");
+	if (rc)
+		return rc;
+	if (!d_albedo)
+		return ugrt_fail(UGRT_EINVAL, "texture_shade: null argument");
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_texture_shade, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, d_albedo);
 }
 
 // Shader::spotlight_shade, shader.h:88-113 (d_dump may be null; the reference
@@ -589,21 +675,16 @@ static int lights_in(const char *who, int num_lights, const float *light_pos, Li
 	return UGRT_OK;
 }
 
-__global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsigned char *__restrict__ d_img,
-							      const float *__restrict__ dd_normal,
-							      const float *__restrict__ dd_t_value,
-							      const float *__restrict__ dd_dir,
-							      int *__restrict__ dd_intersect_id,
-							      const float *__restrict__ d_cam_pos,
-							      const int *__restrict__ mat_idx,
-							      const float *__restrict__ mat_list, int mat_count,
-							      LightsIn lights, const int *__restrict__ is_shadowed,
-							      size_t level, int p0, int n)
+// k_shade_lights' pixel; ALBEDO as in d_shade_pixel
+template <bool ALBEDO>
+__device__ __forceinline__ void d_shade_lights_pixel(const CamBlock &cam, unsigned char *__restrict__ d_img,
+						     const float *__restrict__ dd_normal, const float *__restrict__ dd_t_value,
+						     const float *__restrict__ dd_dir, int *__restrict__ dd_intersect_id,
+						     const float *__restrict__ d_cam_pos, const int *__restrict__ mat_idx,
+						     const float *__restrict__ mat_list, int mat_count, const LightsIn &lights,
+						     const int *__restrict__ is_shadowed, size_t level,
+						     const float *__restrict__ albedo, int pixelID)
 {
-	int i = blockIdx.x * PX_THREADS + threadIdx.x;
-	if (i >= n)
-		return;
-	int pixelID = p0 + i;
 	u32 sum[3] = { 0u, 0u, 0u };
 	const PrimaryHit hit = { dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list, mat_count, pixelID };
 	const int idx = hit.material_id();
@@ -612,7 +693,10 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsig
 		float material[6], point[3], nrm[3], pv[3], nv[3];
 		hit.point(t_value, point);
 		hit.normal(nrm);
-		d_material_kd(mat_list, idx, material);
+		if (ALBEDO)
+			d_albedo_kd(albedo, pixelID, material);
+		else
+			d_material_kd(mat_list, idx, material);
 		d_lambert_view(cam, point, nrm, pv, nv);
 		for (int l = 0; l < lights.count; l++) {
 			float color[3] = { 0.0f, 0.0f, 0.0f };
@@ -629,6 +713,62 @@ __global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsig
 	d_img[pixelID * 3 + 0] = (unsigned char)(sum[0] / (u32)lights.count);
 	d_img[pixelID * 3 + 1] = (unsigned char)(sum[1] / (u32)lights.count);
 	d_img[pixelID * 3 + 2] = (unsigned char)(sum[2] / (u32)lights.count);
+}
+
+__global__ __launch_bounds__(PX_THREADS) void k_shade_lights(CamBlock cam, unsigned char *__restrict__ d_img,
+							      const float *__restrict__ dd_normal,
+							      const float *__restrict__ dd_t_value,
+							      const float *__restrict__ dd_dir,
+							      int *__restrict__ dd_intersect_id,
+							      const float *__restrict__ d_cam_pos,
+							      const int *__restrict__ mat_idx,
+							      const float *__restrict__ mat_list, int mat_count,
+							      LightsIn lights, const int *__restrict__ is_shadowed,
+							      size_t level, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	d_shade_lights_pixel<false>(cam, d_img, dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list,
+				    mat_count, lights, is_shadowed, level, nullptr, p0 + i);
+}
+
+// k_shade_lights with the pixel's albedo in the place of the material's Kd
+__global__ __launch_bounds__(PX_THREADS) void k_texture_shade_lights(CamBlock cam, unsigned char *__restrict__ d_img,
+								     const float *__restrict__ dd_normal,
+								     const float *__restrict__ dd_t_value,
+								     const float *__restrict__ dd_dir,
+								     int *__restrict__ dd_intersect_id,
+								     const float *__restrict__ d_cam_pos,
+								     const int *__restrict__ mat_idx,
+								     const float *__restrict__ mat_list, int mat_count,
+								     LightsIn lights, const int *__restrict__ is_shadowed,
+								     size_t level, const float *__restrict__ albedo, int p0, int n)
+{
+	int i = blockIdx.x * PX_THREADS + threadIdx.x;
+	if (i >= n)
+		return;
+	d_shade_lights_pixel<true>(cam, d_img, dd_normal, dd_t_value, dd_dir, dd_intersect_id, d_cam_pos, mat_idx, mat_list,
+				   mat_count, lights, is_shadowed, level, albedo, p0 + i);
+}
+
+extern "C" int ugrt_texture_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,
+					const float *d_ray_dir, int *d_intersect_id, const float *d_cam_position,
+					const int *d_mat_idx, const float *d_mat_list, int num_materials, int num_lights,
+					const float *light_pos, const int *d_is_shadowed, const float *d_albedo)
+{
+	int rc = shade_args_ok(ctx, d_img, d_normal, d_t_value, d_ray_dir, d_intersect_id, d_cam_position, d_mat_idx,
+			       d_mat_list, "texture_shade_lights");
+	if (rc)
+		return rc;
+	if (!light_pos || !d_albedo)
+		return ugrt_fail(UGRT_EINVAL, "texture_shade_lights: null argument");
+	LightsIn lights;
+	if ((rc = lights_in("texture_shade_lights", num_lights, light_pos, &lights)))
+		return rc;
+	return ugrt_launch_pixels(ctx, UGRT_ST_SHADE, k_texture_shade_lights, ctx->cam, d_img, d_normal, d_t_value, d_ray_dir,
+				  d_intersect_id, d_cam_position, d_mat_idx, d_mat_list, num_materials, lights, d_is_shadowed,
+				  (size_t)ctx->cfg.width * (size_t)ctx->cfg.height, d_albedo);
 }
 
 extern "C" int ugrt_shade_lights(ugrt_ctx *ctx, unsigned char *d_img, const float *d_normal, const float *d_t_value,

@@ -560,6 +560,56 @@ class Context:
         check(lib.ugrt_smooth_normals(self._h, _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos), _ptr(verts), _ptr(faces),
                                       _ptr(corner_normals), _ptr(normal_in), 1 if fold else 0, _ptr(normal_out)))
 
+    # -- texture mapping ----------------------------------
+    def texture_set(self, textures):
+        """The mip atlas of `textures`, a list of uint8 host arrays [H, W, 3] (row 0: v = 0); an empty list drops it.  Level 0
+        is copied, the further levels are built on the device; the call does not wait.  get_state("texture_builds")
+        counts the calls that built."""
+        arrs = [np.ascontiguousarray(a, dtype=np.uint8) for a in textures]
+        for a in arrs:
+            if a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError("ugrt: a texture is a uint8 array [H, W, 3], not %r" % (a.shape,))
+        n = len(arrs)
+        wh = (C.c_int * max(2 * n, 1))(*[d for a in arrs for d in (a.shape[1], a.shape[0])])
+        ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in arrs])
+        check(lib.ugrt_texture_set(self._h, n, wh, ptrs))
+
+    def texture_get_level(self, tex, level):
+        """(width, height, the level's packed words r | g << 8 | b << 16 | 255 << 24 as an int32 tensor view) (tests)."""
+        w, h, p = C.c_int(), C.c_int(), C.c_void_p()
+        check(lib.ugrt_texture_get_level(self._h, int(tex), int(level), C.byref(w), C.byref(h), C.byref(p)))
+        return w.value, h.value, self._wrap_u32_uncached(p.value, w.value * h.value)
+
+    def texture_albedo(self, t, ray_dir, ids, cam_pos, verts, faces, uvs, num_uvs, uv_faces, mat_idx, mat_list, num_materials,
+                       mat_texture, mat_texture_host, max_aniso, lod_bias, albedo):
+        """The diffuse colour of every pixel's primary hit, three floats per pixel, before the shading call (ids: triangle
+        ids): Kd, times the texture of the hit's material filtered over the pixel's footprint -- up to max_aniso trilinear
+        taps along its longer axis -- where the material has one (mat_texture[m] >= 0) and the triangle has uvs.
+        mat_texture_host: the host copy of mat_texture (a sequence of ints), which the call checks against the atlas."""
+        host = np.ascontiguousarray(mat_texture_host, dtype=np.int32)
+        check(lib.ugrt_texture_albedo(self._h, _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos), _ptr(verts), _ptr(faces),
+                                      _ptr(uvs), int(num_uvs), _ptr(uv_faces), _ptr(mat_idx), _ptr(mat_list), int(num_materials),
+                                      _ptr(mat_texture), host.ctypes.data_as(C.POINTER(C.c_int)), int(max_aniso), int(lod_bias),
+                                      _ptr(albedo)))
+
+    def texture_shade(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, albedo):
+        """shade_simple with the pixel's albedo (texture_albedo) in the place of its material's Kd."""
+        check(lib.ugrt_texture_shade(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                    _ptr(mat_idx), _ptr(mat_list), num_materials, _ptr(albedo)))
+
+    def texture_shade_spotlight(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, albedo, dump=None):
+        """shade_spotlight with the pixel's albedo (texture_albedo) in the place of its material's Kd."""
+        check(lib.ugrt_texture_shade_spotlight(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                               _ptr(mat_idx), _ptr(mat_list), num_materials, _ptr(dump), _ptr(albedo)))
+
+    def texture_shade_lights(self, img, normal, t, ray_dir, ids, cam_pos, mat_idx, mat_list, num_materials, light_pos,
+                            is_shadowed, albedo):
+        """shade_lights with the pixel's albedo (texture_albedo) in the place of its material's Kd."""
+        n, pos = _points(light_pos)
+        check(lib.ugrt_texture_shade_lights(self._h, _ptr(img), _ptr(normal), _ptr(t), _ptr(ray_dir), _ptr(ids), _ptr(cam_pos),
+                                           _ptr(mat_idx), _ptr(mat_list), num_materials, n, pos, _ptr(is_shadowed),
+                                           _ptr(albedo)))
+
     # -- anti-aliasing (DESIGN.md section 6.11) --------------------------------
     def aa_edges(self, normal, t, dirs, ids, cam_pos, mat_idx, is_shadowed, normal_cos, plane_tol, edge):
         """Before the shading call (ids holds triangle ids): edge[p] = 1 where one of the up to eight neighbours of p

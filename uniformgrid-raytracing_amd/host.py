@@ -96,6 +96,30 @@ class Model:
         p = lib.ugrt_scene_sharpnesslist(self._h, C.byref(n))
         return _view(p, n.value, np.float32)
 
+    @property
+    def h_uvlist(self):
+        """u, v of every "vt" line, float32 [2T]; empty after load_cache."""
+        n = C.c_int()
+        p = lib.ugrt_scene_uvlist(self._h, C.byref(n))
+        return _view(p, 2 * n.value, np.float32)
+
+    @property
+    def h_uvfacelist(self):
+        """One index into h_uvlist per corner of h_facelist, int32 [3F]; -1: none (all -1 after load_cache)."""
+        return _view(lib.ugrt_scene_uv_facelist(self._h), self.num_faces * 3, np.int32)
+
+    @property
+    def h_texturelist(self):
+        """The texture's file name per material of the mtllib (map_Kd, else map_Ka), "" for none; texture_dir + name is its
+        path."""
+        n = C.c_int()
+        lib.ugrt_scene_reflectlist(self._h, C.byref(n))
+        return [lib.ugrt_scene_texture_name(self._h, m).decode("utf-8", "replace") for m in range(n.value)]
+
+    @property
+    def texture_dir(self):
+        return lib.ugrt_scene_texture_dir(self._h).decode("utf-8", "replace")
+
     def bounds(self):
         mn, mx = (C.c_float * 3)(), (C.c_float * 3)()
         check(lib.ugrt_scene_bounds(self._h, mn, mx))
@@ -171,3 +195,12 @@ def write_ppm(path, rgb):
     a = np.ascontiguousarray(rgb, dtype=np.uint8)
     h, w = a.shape[0], a.shape[1]
     check(lib.ugrt_write_ppm(str(path).encode(), w, h, a.ctypes.data_as(_P)))
+
+
+def read_ppm(path):
+    """The counterpart of write_ppm: a P3 or P6 file as a uint8 array [H, W, 3] in file order."""
+    w, h = C.c_int(), C.c_int()
+    check(lib.ugrt_read_ppm(str(path).encode(), C.byref(w), C.byref(h), None, 0))
+    a = np.zeros((h.value, w.value, 3), np.uint8)
+    check(lib.ugrt_read_ppm(str(path).encode(), C.byref(w), C.byref(h), a.ctypes.data_as(_P), a.size))
+    return a

@@ -57,7 +57,8 @@ import contextlib
 import numpy as np
 
 from . import (FLAG_STATIC_GEOMETRY, GRID_SPHERICAL, GRID_UNIFORM, MAX_AA_SAMPLES, MAX_AO_DIRS, MAX_AREA_SAMPLES,
-               MAX_DOF_WINDOW, MAX_FILTER_RADIUS, MAX_FRESNEL_DEPTH, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES)
+               MAX_DOF_WINDOW, MAX_FILTER_RADIUS, MAX_FRESNEL_DEPTH, MAX_GLOSSY_SAMPLES, MAX_LIGHTS, MAX_REFLECT_DEPTH, MAX_TEMPORAL_FRAMES,
+               MAX_TEXTURE_ANISO, MAX_TEXTURE_DIM, MAX_TEXTURES)
 from .host import Camera
 
 PI_F = float(np.float32(np.pi))
@@ -563,6 +564,45 @@ def trace_shadows(c, f, b, light_grid, is_shadowed=None):
                    f.is_shadowed if is_shadowed is None else is_shadowed, b._d_map, b._prefix, b.cam_pos, b._num_chunks)
 
 
+def check_textures(textures, texture_aniso=8, texture_bias=0, reflect=False, refract=False, fresnel=False, glossy=0, gi=0,
+                   aa=0, dof=0, frame_cnt=1, reflect_lights=False, two_streams=False):
+    """The keywords of texture mapping.  textures: a bool (False: off, and the other two must be
+    at their defaults); texture_aniso: an int in 1..MAX_TEXTURE_ANISO, the most taps along a footprint's longer axis (1:
+    isotropic trilinear); texture_bias: an int in -16..16 added to every pixel's level.  Returns None (off) or (texture_aniso,
+    texture_bias).  textures needs the one-stream Renderer and no reflect, refract, fresnel, glossy, gi, aa, dof or
+    reflect_lights: their kernels and ugrt_gi_apply read a hit's colour from its material's Kd (frame_cnt is taken and
+    not looked at: the spotlight frame composes).  ValueError before anything is enqueued."""
+    if not isinstance(textures, (bool, np.bool_)):
+        raise ValueError("textures must be True or False, not %r" % (textures,))
+    for name, v, lo, hi in (("texture_aniso", texture_aniso, 1, MAX_TEXTURE_ANISO), ("texture_bias", texture_bias, -16, 16)):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError("%s must be an integer in %d..%d, not %r" % (name, lo, hi, v))
+    if not textures:
+        if texture_aniso != 8 or texture_bias != 0:
+            raise ValueError("texture_aniso and texture_bias need textures=True: they shape the texture's filter")
+        return None
+    if reflect or refract or fresnel or reflect_lights:
+        raise ValueError("textures needs reflect=False: the levels' hits are shaded from their materials' Kd")
+    for name, v in (("glossy", glossy), ("gi", gi), ("aa", aa), ("dof", dof)):
+        if v:
+            raise ValueError("textures needs %s=0: the gather's hits and ugrt_gi_apply are shaded from the materials' Kd" % name)
+    if two_streams:
+        raise ValueError("textures needs the one-stream Renderer: the two-stream and banded frames are not built")
+    return int(texture_aniso), int(texture_bias)
+
+
+def texture_pass(c, f, cam_pos, tex):
+    """The albedo of a textured frame into f.albedo, directly behind the camera pass: the ids are
+    the triangles' and the context's camera is the eye's, whose rays through the neighbouring pixels give the footprint
+    (the light's camera block replaces it for the rest of the frame).  Returns the buffer the shading call reads in the
+    place of the materials' Kd."""
+    st = f._tex
+    c.texture_albedo(f.t, f.dir, f.intersect_id, cam_pos, f.d_verts, f.d_faces, st["uvs"], st["num_uvs"], st["uv_faces"],
+                     f.d_matidx, f.d_matlist, f.num_materials, st["mat_texture"], st["mat_texture_host"], tex[0], tex[1],
+                     f.albedo)
+    return f.albedo
+
+
 def smooth_pass(c, f, cam_pos, signed):
     """The shading normals of a smooth frame into f.snormal, directly before the shading call
     (the ids are the triangles' still): the corner normals mixed at every primary hit, f.normal's words elsewhere.  Returns
@@ -572,9 +612,15 @@ def smooth_pass(c, f, cam_pos, signed):
     return f.snormal
 
 
-def shade_lights(c, f, cam_pos, lights, shadows, normal=None):
+def shade_lights(c, f, cam_pos, lights, shadows, normal=None, albedo=None):
     """The Lambertian shading of every light and its shadows, averaged, in one pass.  normal: the
-    normals the pass reads (smooth_pass'), f.normal unless given."""
+    normals the pass reads (smooth_pass'), f.normal unless given.  albedo (texture_pass'): the pixels' Kd in the place of
+    their materials'."""
+    if albedo is not None:
+        c.texture_shade_lights(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
+                              f.d_matlist, f.num_materials, [pos for _, pos in lights], f.shadowed_lights if shadows else None,
+                              albedo)
+        return
     c.shade_lights(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
                    f.d_matlist, f.num_materials,
                    [pos for _, pos in lights], f.shadowed_lights if shadows else None)
@@ -828,12 +874,13 @@ def area_pass(c, f, cam_pos, samples, thru=None, sets=None, have_rays=False):
 
 
 def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_shadows=False, glossy=None, normal=None,
-                fresnel=None):
+                fresnel=None, albedo=None):
     """simpleShade | spotlight_shade, or the reflections' shading (shade_reflect at depth 1; with reflect_shadows the
     depth shading with the occluded levels darkened, at every depth), then add_shadows.  glossy (glossy_pass' gl): the
     lobe's blend directly behind the shading call, where the mirror frame has its own.  normal (smooth_pass'): the normals
     simpleShade | spotlight_shade read, f.normal unless given.  fresnel (check_fresnel's pair): shade_fresnel over
-    fresnel_pass' sums in the place of the reflections' shading."""
+    fresnel_pass' sums in the place of the reflections' shading.  albedo (texture_pass'): texture_shade |
+    texture_shade_spotlight in simpleShade's | spotlight_shade's place."""
     if fresnel:
         c.shade_fresnel(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist, f.num_materials,
                         f.f_acc)
@@ -848,6 +895,12 @@ def shade_frame(c, f, cam_pos, frame_cnt, shadows, reflect, bounces, reflect_sha
         c.shade_reflect_depth(f.image, f.normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx, f.d_matlist,
                               level_weights(f), f.num_materials, f.d_verts, f.d_faces, bounces, f.rays_levels,
                               f.active_levels, f.hit_t_levels, f.hit_id_levels)
+    elif albedo is not None and frame_cnt < 2:
+        c.texture_shade(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
+                        f.d_matlist, f.num_materials, albedo)
+    elif albedo is not None:
+        c.texture_shade_spotlight(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos,
+                                  f.d_matidx, f.d_matlist, f.num_materials, albedo)
     elif frame_cnt < 2:
         c.shade_simple(f.image, f.normal if normal is None else normal, f.t, f.dir, f.intersect_id, cam_pos, f.d_matidx,
                        f.d_matlist,
@@ -1106,8 +1159,12 @@ class _Band:
 class Renderer(_Frame, _Band):
     def __init__(self, ctx, verts, faces, matidx, mat_list, reflect=None, transmit=None, ior=None, reflect_eps=1e-3,
                  overlap=False, shards=None, helper_thread=True, aux_stream=None, batch_builds=False, spread=None,
-                 vertex_key=None):
-        """vertex_key: one int per vertex, in 0..V-1 (scenes.weld; None: every vertex is its own key), for
+                 vertex_key=None, uvs=None, uv_faces=None, textures=None, mat_texture=None):
+        """uvs [T, 2] floats, uv_faces [F, 3] ints (an index into uvs per corner of the face list; outside 0..T-1: none),
+        textures (a list of uint8 arrays [H, W, 3], row 0 at v = 0) and mat_texture (one int per material: its texture, -1:
+        none), for display(..., textures=True) (DESIGN.md section 6.18); None: no uvs, no textures.  They are checked here;
+        the atlas is built by the first textured frame, once.
+        vertex_key: one int per vertex, in 0..V-1 (scenes.weld; None: every vertex is its own key), for
         display(..., smooth=True): the faces around the vertices of one key share their normals.
         spread: per material, the tangent of the half-angle of its reflection lobe (scenes.spread_from_sharpness; None:
         zeros, mirrors), for display(..., glossy=S).
@@ -1150,6 +1207,29 @@ class Renderer(_Frame, _Band):
                     or (V and (key.min() < 0 or key.max() >= V)):
                 raise ValueError("vertex_key must hold one integer in 0..%d per vertex (%d)" % (V - 1, V))
             self._vertex_key = key.astype(np.int32)
+        # texture mapping: checked here, the device side is made by the first textured frame
+        # (_texture_stage)
+        self._tex = None
+        F = len(f) // 3
+        tl = [] if textures is None else [np.asarray(a) for a in textures]
+        if len(tl) > MAX_TEXTURES:
+            raise ValueError("textures holds %d arrays, at most %d fit" % (len(tl), MAX_TEXTURES))
+        for a in tl:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or not (1 <= a.shape[0] <= MAX_TEXTURE_DIM) \
+                    or not (1 <= a.shape[1] <= MAX_TEXTURE_DIM):
+                raise ValueError("a texture is a uint8 array [H, W, 3] with H, W in 1..%d, not %s %r"
+                                 % (MAX_TEXTURE_DIM, a.dtype, a.shape))
+        mt = np.full(self.num_materials, -1, np.int32) if mat_texture is None else np.asarray(mat_texture)
+        if mt.ndim != 1 or len(mt) != self.num_materials or not np.issubdtype(mt.dtype, np.integer) \
+                or (len(mt) and mt.max() >= len(tl)):
+            raise ValueError("mat_texture must hold one integer below %d per material (%d)" % (len(tl), self.num_materials))
+        uv = np.zeros((0, 2), np.float32) if uvs is None else np.asarray(uvs)
+        if uv.ndim != 2 or uv.shape[1] != 2 or not (np.issubdtype(uv.dtype, np.floating) or np.issubdtype(uv.dtype, np.integer)):
+            raise ValueError("uvs must be numbers [T, 2], not %r" % (uv.shape,))
+        uf = np.full((F, 3), -1, np.int32) if uv_faces is None else np.asarray(uv_faces)
+        if uf.shape != (F, 3) or not np.issubdtype(uf.dtype, np.integer):
+            raise ValueError("uv_faces must hold three integers per face (%d), not %r" % (F, uf.shape))
+        self._tex_host = (uv.astype(np.float32), uf.astype(np.int32), tl, mt.astype(np.int32))
 
     def _make_side_context(self, ctx, aux_stream, helper_thread):
         from .device import Context
@@ -1252,7 +1332,7 @@ class Renderer(_Frame, _Band):
                 temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0, glossy_sets=1, glossy_filter=0,
                 glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None, glossy_shadows=True, smooth=False,
                 smooth_cos=0.5, smooth_signed=False, dof=0, dof_aperture=0.0, dof_focus=None, dof_sets=1, dof_min=0.5,
-                dof_window=4, dof_shadows=True, fresnel=False, fresnel_cut=0.0):
+                dof_window=4, dof_shadows=True, textures=False, texture_aniso=8, texture_bias=0, fresnel=False, fresnel_cut=0.0):
         """bounces: levels of reflection with reflect=True (1..8; 1 = the single bounce).  rays_levels /
         active_levels / hit_t_levels / hit_id_levels hold every level and rays / active / hit_t / hit_id are level
         1's views.  reflect_shadows (needs reflect=True): the hits of every reflection level are shadowed (from the light
@@ -1327,6 +1407,13 @@ class Renderer(_Frame, _Band):
         (rotate_bunny, geometry_changed) or smooth_cos changed.  smooth_signed keeps the normals' signs where the primary
         tracer folds them into the positive octant.  Nothing else reads snormal: normal, the {origin, normal} of ao_rays
         and every mask and sum are the frame's without smooth.
+        textures (one-stream renderer; the plain frame, frame_cnt=2, shadows=False and setup.lights; smooth, ao, area and
+        temporal compose; no reflect, refract, fresnel, glossy, gi, aa, dof or reflect_lights; False: off): texture
+        mapping -- the shading call reads a per-pixel diffuse colour (albedo) in the place of the material's Kd: Kd times
+        the material's texture (Renderer(textures=, mat_texture=, uvs=, uv_faces=)) filtered over the pixel's footprint from
+        a mip atlas, with up to texture_aniso trilinear taps along the footprint's longer axis; texture_bias is added to
+        every level.  The atlas is built by the first textured frame, once.  A renderer without textures gives the frame
+        without the keyword, byte for byte.
         fresnel (one-stream renderer, single-light frames with reflect=True and refract=True, bounces <= 6; ao, area, gi
         and temporal compose as with the refract frame; no aa, glossy or smooth; False: off): Fresnel glass -- a glass hit
         sends the transmitted ray AND the reflected ray, weighted (1 - F) and F of the material's transmit, F = fresnel
@@ -1352,6 +1439,11 @@ class Renderer(_Frame, _Band):
         glossy_apply; shade_add_shadows, or with area shade_area / shade_area_vis in its place; gi_apply; aa_resolve;
         shade_ao / shade_ao_vis.  The primary hits' {origin, normal} (ao_rays / ao_active) are written once per frame, by
         the first of glossy, area, ao and gi that is on, and read by the others."""
+        if textures is False and texture_aniso == 8 and texture_bias == 0:
+            textures = None  # (the defaults: nothing to check, and the frame loop pays nothing for the keywords)
+        else:
+            textures = check_textures(textures, texture_aniso, texture_bias, reflect, refract, fresnel is not False, glossy, gi,
+                                      aa, dof, frame_cnt, reflect_lights, self.aux is not None)
         if smooth is False and smooth_signed is False and smooth_cos == 0.5:
             smooth = None  # (the defaults: nothing to check, and the frame loop pays nothing for the keywords)
         else:
@@ -1393,7 +1485,8 @@ class Renderer(_Frame, _Band):
                                                 self._ao_stage(ao, ao_radius, shade, ao_more))
         if getattr(setup, "lights", None) is not None:
             lights = check_lights(setup.lights, reflect, self.aux is not None)
-            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more), smooth)
+            return self._display_lights(setup, lights, shadows, shade, self._ao_stage(ao, ao_radius, shade, ao_more), smooth,
+                                        textures)
         if temporal and shade:  # (the effects' stages are made behind _temporal_begin)
             ao_asked, gi_asked, ao = ao, gi, None
         else:
@@ -1424,6 +1517,10 @@ class Renderer(_Frame, _Band):
                 area_t = self._temporal_area(tp, area, area_sets, area_radius, area_filter, area_filter_cos,
                                              area_filter_plane, setup)
         camera_pass(ctx, self, self, setup, cam)
+        albedo = None
+        if textures and shade:  # (here: the context's camera is the eye's until the light's is uploaded)
+            self._texture_stage()
+            albedo = texture_pass(ctx, self, self.cam_pos, textures)
         lcam = make_camera(setup.light_camera, setup.fovy, self.aspect)
         use_light_camera(ctx, lcam)
         if shadows and not area:
@@ -1476,7 +1573,7 @@ class Renderer(_Frame, _Band):
             self._smooth_stage(smooth[0])
             normal = smooth_pass(ctx, self, self.cam_pos, smooth[1])
         shade_frame(ctx, self, self.cam_pos, frame_cnt, shadows and not area, reflect, bounces, reflect_shadows,
-                    glossy or None, normal, fresnel or None)
+                    glossy or None, normal, fresnel or None, albedo)
         if area and tp:
             area_shade_temporal(ctx, self, tp, area_t)
         elif area and area_filter:
@@ -1499,6 +1596,19 @@ class Renderer(_Frame, _Band):
             ao_shade_temporal(ctx, self, tp, ao)
         elif ao:
             ao_shade(ctx, self, *ao)
+
+    # -- texture mapping
+    def _texture_stage(self):
+        """What texture_pass reads: the atlas, the uvs, the uv indices and the materials' textures on the device and albedo
+        [3 W*H], made on the first textured frame and kept -- the uvs ride on the face list, so rotate_bunny and
+        geometry_changed invalidate nothing here."""
+        if self._tex is None:
+            ctx, t = self.ctx, self.torch
+            uv, uf, tl, mt = self._tex_host
+            ctx.texture_set(tl)
+            self._tex = {"uvs": ctx.upload(uv.reshape(-1)) if len(uv) else None, "num_uvs": len(uv),
+                         "uv_faces": ctx.upload(uf.reshape(-1)), "mat_texture": ctx.upload(mt), "mat_texture_host": mt}
+            self.albedo = ctx.empty(3 * self.N, t.float32)
 
     # -- smooth shading (DESIGN.md section 6.15)
     def _smooth_stage(self, cos):
@@ -1802,7 +1912,7 @@ class Renderer(_Frame, _Band):
     def _upload_area_sets(self, table):
         return self.ctx.upload(table.reshape(-1))
 
-    def _display_lights(self, setup, lights, shadows, shade, ao=None, smooth=None):
+    def _display_lights(self, setup, lights, shadows, shade, ao=None, smooth=None, textures=None):
         """The reference's loop over the lights (main.cu:148-203) made real: the camera pass, per light its camera and
         shadow stage into its row of shadowed_lights, then ONE shading pass.  dd_camcoords is the last light's when
         the shading runs, as the reference's loop leaves it."""
@@ -1810,6 +1920,10 @@ class Renderer(_Frame, _Band):
         if shadows:
             self._ensure_light_buffers(len(lights))
         camera_pass(ctx, self, self, setup, make_camera(setup.camera, setup.fovy, self.aspect))
+        albedo = None
+        if textures and shade:  # (here: the context's camera is the eye's until the first light's is uploaded)
+            self._texture_stage()
+            albedo = texture_pass(ctx, self, self.cam_pos, textures)
         if shadows:
             self.shadowed_lights[:len(lights)].zero_()  # the shadow pass only sets flags: rows of earlier frames are stale
         for l, (params, _) in enumerate(lights):
@@ -1829,7 +1943,7 @@ class Renderer(_Frame, _Band):
         if smooth:
             self._smooth_stage(smooth[0])
             normal = smooth_pass(ctx, self, self.cam_pos, smooth[1])
-        shade_lights(ctx, self, self.cam_pos, lights, shadows, normal)
+        shade_lights(ctx, self, self.cam_pos, lights, shadows, normal, albedo)
         if ao:
             ao_shade(ctx, self, *ao)
 
@@ -2059,7 +2173,10 @@ class BandedRenderer(_Frame):
                 aa_cos=0.9, aa_plane=None, aa_shadows=True, temporal=0, temporal_cos=0.9, temporal_plane=None, glossy=0,
                 glossy_sets=1, glossy_filter=0, glossy_filter_cos=0.9, glossy_filter_plane=None, glossy_radius=None,
                 glossy_shadows=True, smooth=False, smooth_cos=0.5, smooth_signed=False, dof=0, dof_aperture=0.0, dof_focus=None,
-                dof_sets=1, dof_min=0.5, dof_window=4, dof_shadows=True, fresnel=False, fresnel_cut=0.0):
+                dof_sets=1, dof_min=0.5, dof_window=4, dof_shadows=True, textures=False, texture_aniso=8,
+                texture_bias=0, fresnel=False, fresnel_cut=0.0):
+        if textures is not False or texture_aniso != 8 or texture_bias != 0:
+            check_textures(textures, texture_aniso, texture_bias, two_streams=True)  # raises with textures=True
         check_dof(dof, dof_aperture, dof_focus, dof_sets, dof_min, dof_window, dof_shadows, two_streams=True)  # raises with dof > 0
         check_smooth(smooth, smooth_cos, smooth_signed, False, False, 0, 0, False, True)  # raises with smooth=True
         check_fresnel(fresnel, fresnel_cut, reflect, refract, 1, getattr(setup, "lights", None), False,

@@ -181,11 +181,16 @@ CORNELL_QUADS = [
 ]
 
 
-def write_scene(outdir, name, verts, faces, matidx, materials, glass=None, sharpness=None):
+def write_scene(outdir, name, verts, faces, matidx, materials, glass=None, sharpness=None, uvs=None, uv_faces=None,
+                textures=None):
     """Write <name>.obj, <name>.mtl, <name>.mat; returns their paths.  glass: {material index: (d, Ni)} -- the MTL
     carries these materials' dissolve and index of refraction, every other material is written as "d 1" without Ni.
     sharpness: {material index: value} -- the MTL carries these materials' "sharpness" line behind the dissolve, every
-    other material has none (the loader's default is 98)."""
+    other material has none (the loader's default is 98).
+    uvs [T, 2] and uv_faces [F, 3] (indices into uvs, -1: none): the OBJ carries "vt" lines behind its vertices and the
+    faces whose three corners have one are written as "f v/t v/t v/t".  textures: {material index: (file name, uint8 array
+    [H, W, 3])} -- the MTL carries these materials' "map_Kd" line and the arrays are written as P6 files beside it.  With
+    none of the three the files are what they were without these keywords, byte for byte."""
     os.makedirs(outdir, exist_ok=True)
     obj, mtl, mat = (os.path.join(outdir, name + e) for e in (".obj", ".mtl", ".mat"))
     with open(mtl, "w") as fp:
@@ -193,6 +198,11 @@ def write_scene(outdir, name, verts, faces, matidx, materials, glass=None, sharp
             d_ni = "d 1\n" if not glass or k not in glass else "d %.6f\nNi %.6f\n" % tuple(glass[k])
             if sharpness and k in sharpness:
                 d_ni += "sharpness %.6f\n" % sharpness[k]
+            if textures and k in textures:
+                d_ni += "map_Kd %s\n" % textures[k][0]
+                tex = np.ascontiguousarray(textures[k][1], dtype=np.uint8)
+                with open(os.path.join(outdir, textures[k][0]), "wb") as tp:
+                    tp.write(b"P6\n%d %d\n255\n" % (tex.shape[1], tex.shape[0]) + tex.tobytes())
             fp.write("newmtl %s\nKa %.6f %.6f %.6f\nKd %.6f %.6f %.6f\nKs 1.000000 1.000000 1.000000\nNs 0\n"
                      "%sr %.6f\nillum 2\n\n" % ((nm,) + tuple(ka) + tuple(kd) + (d_ni, refl)))
     with open(mat, "w") as fp:
@@ -202,13 +212,20 @@ def write_scene(outdir, name, verts, faces, matidx, materials, glass=None, sharp
     with open(obj, "w") as fp:
         fp.write("# generated by uniformgrid-raytracing_amd.scenes (seed %d)\nmtllib %s.mtl\n" % (SEED, name))
         fp.write("".join("v %.6f %.6f %.6f\n" % tuple(r) for r in verts))
+        if uvs is not None:
+            fp.write("".join("vt %.6f %.6f\n" % tuple(r) for r in np.asarray(uvs).reshape(-1, 2)))
+        t1 = None if uvs is None or uv_faces is None else np.asarray(uv_faces).reshape(-1, 3) + 1
         # usemtl only when the material changes
         change = np.flatnonzero(np.diff(matidx, prepend=-999))
         bounds = list(change) + [len(faces)]
         f1 = faces + 1
         for a, b in zip(bounds[:-1], bounds[1:]):
             fp.write("usemtl %s\n" % materials[int(matidx[a])][0])
-            fp.write("".join("f %d %d %d\n" % tuple(r) for r in f1[a:b]))
+            if t1 is None:
+                fp.write("".join("f %d %d %d\n" % tuple(r) for r in f1[a:b]))
+            else:
+                fp.write("".join("f %d/%d %d/%d %d/%d\n" % (r[0], t[0], r[1], t[1], r[2], t[2]) if t.min() > 0
+                                 else "f %d %d %d\n" % tuple(r) for r, t in zip(f1[a:b], t1[a:b])))
     return obj, mtl, mat
 
 
@@ -218,7 +235,8 @@ def _finish(outdir, name, mesh, materials, extra):
     info.update(extra)
     if outdir is not None:
         info["obj"], info["mtl"], info["mat"] = write_scene(outdir, name, verts, faces, matidx, materials,
-                                                            extra.get("glass"), extra.get("sharpness_of"))
+                                                            extra.get("glass"), extra.get("sharpness_of"), extra.get("uvs"),
+                                                            extra.get("uv_faces"), extra.get("texture_files"))
     info["verts"] = verts.astype(np.float32)  # generation values; the loaders parse the 6-decimal text
     info["faces"] = faces
     info["matidx"] = matidx
@@ -568,6 +586,70 @@ def depth(outdir=None, scale=1.0):
     info = _finish(outdir, "depth", mesh, MATERIALS_ROOM,
                    dict(cameras=cams, light_camera=light_cam, shading_light=(-10.0, 13.0, 8.0)))
     info["posts"] = posts
+    return info
+
+
+def planar_uvs(verts, faces, scale=1.0):
+    """Texture coordinates for any mesh: every face is projected along the axis its normal is closest to -- (y, z) for x,
+    (x, z) for y, (x, y) for z -- and the two coordinates are multiplied by scale (texture repeats per unit of length).
+    Returns (uvs float32 [3F, 2], uv_faces int32 [F, 3]): one uv per corner, uv_faces[f] = (3f, 3f + 1, 3f + 2)."""
+    v = np.asarray(verts, np.float64).reshape(-1, 3)
+    f = np.asarray(faces).reshape(-1, 3)
+    c = v[f]
+    axis = np.argmax(np.abs(np.cross(c[:, 1] - c[:, 0], c[:, 2] - c[:, 0])), axis=1)
+    keep = np.array([[1, 2], [0, 2], [0, 1]])[axis]
+    uv = np.take_along_axis(c, np.repeat(keep[:, None, :], 3, 1), axis=2) * float(scale)
+    return uv.reshape(-1, 2).astype(np.float32), np.arange(3 * len(f), dtype=np.int32).reshape(-1, 3)
+
+
+def checker_texture(size, cells, a=(235, 235, 235), b=(40, 40, 40)):
+    """A size x size checkerboard of cells x cells squares, uint8 [size, size, 3]."""
+    i = np.arange(size) * cells // size
+    on = ((i[:, None] + i[None, :]) & 1).astype(bool)
+    return np.where(on[..., None], np.uint8(b), np.uint8(a)).astype(np.uint8)
+
+
+def stripes_texture(size, n, a=(230, 200, 60), b=(30, 60, 160)):
+    """A size x size texture of n vertical stripes (constant along v), uint8 [size, size, 3]."""
+    on = ((np.arange(size) * n // size) & 1).astype(bool)
+    return np.repeat(np.where(on[:, None], np.uint8(b), np.uint8(a))[None], size, 0).astype(np.uint8)
+
+
+MATERIALS_TEXTURED = [
+    ("t0_floor", (0.2, 0.2, 0.2), (0.90, 0.90, 0.90), 0.0),
+    ("t1_wall", (0.2, 0.2, 0.2), (0.95, 0.90, 0.85), 0.0),
+    ("t2_box_plain", (0.2, 0.2, 0.2), (0.80, 0.25, 0.20), 0.0),
+    ("t3_box_striped", (0.2, 0.2, 0.2), (1.00, 1.00, 1.00), 0.0),
+]
+
+
+def textured(outdir=None, scale=1.0):
+    """A scene for display(textures=True).  A floor [1, 200] x [-60, 60] at z = 0 that runs to
+    the horizon under a checker of 2 x 2 texels that repeats 16 times per unit of length -- the aliasing case; a wall at
+    x = 12 seen head-on under an 8 x 8 checker that covers it once -- the magnification case; and two boxes side by side, one
+    of an untextured material, one striped.  info: uvs, uv_faces, textures (a list of uint8 arrays), mat_texture (one int per
+    material, -1: none) and texture_files {material: (file name, array)} for write_scene."""
+    mesh = Mesh()
+    n = max(2, int(8 * max(0.05, scale) ** 0.5))
+    mesh.add(*grid_quad((1, -60, 0), (199, 0, 0), (0, 120, 0), n, n), 0)
+    mesh.add(*grid_quad((12, 2.0, 0), (0, 5, 0), (0, 0, 4), 2, 2), 1)
+    add_box(mesh, (6.0, -3.2, 0.0), (7.2, -2.0, 1.2), 1, 2, faces="xyYZ")
+    add_box(mesh, (6.0, -1.6, 0.0), (7.2, -0.4, 1.2), 1, 3, faces="xyYZ")
+    verts, faces, matidx = mesh.arrays()
+    uvs, uv_faces = planar_uvs(verts, faces, 1.0)
+    per_material = {0: 16.0, 1: 0.2, 2: 1.0, 3: 2.5}
+    for m, k in per_material.items():
+        uvs[uv_faces[matidx == m].reshape(-1)] *= np.float32(k)
+    uv_faces[matidx == 2] = -1
+    textures = [checker_texture(2, 2), checker_texture(8, 8, (250, 240, 200), (120, 30, 30)), stripes_texture(64, 8)]
+    files = {0: ("floor_checker.ppm", textures[0]), 1: ("wall_checker.ppm", textures[1]), 3: ("box_stripes.ppm", textures[2])}
+    cams = {"ref": dict(eye=(0.0, 0.0, 1.5), look=(12.0, 1.0, 1.2), up=(0, 0, 1), near=0.1, far=400.0)}
+    light_cam = dict(eye=(5.0, 0.0, 12.0), look=(8.0, 0.0, 0.0), up=(0, 1, 0), near=0.1, far=400.0)
+    info = _finish(outdir, "textured", mesh, MATERIALS_TEXTURED,
+                   dict(cameras=cams, light_camera=light_cam, shading_light=(4.0, -2.0, 6.0), uvs=uvs, uv_faces=uv_faces,
+                        texture_files=files))
+    info["textures"] = textures
+    info["mat_texture"] = np.int32([0, 1, -1, 2])
     return info
 
 
